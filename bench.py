@@ -11,10 +11,18 @@ one (6N+1)-frame sequence -- and c3 / c4 strong-scaled -- one fixed sequence (64
 9 frames at 1080p) split into contiguous pair shards (8,8,...,7 at 8 ranks).  Neighbouring shards
 share one boundary frame; its per-frame encoder features come from rank r+1 by a point-to-point
 halo exchange inside the timed step (--halo recompute recomputes them instead).  Rank 0 prints one
-JSON line; at N = 1 it also carries the CPU baseline, a parity check of the same pair against the
-CPU oracle (max error, PSNR), the fp32-MFMA value and the C1 / C2 lines.
+JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c0|c1|c2|c3|c4]
+A plain run sets up, warms up, times the K steps and prints the headline record (metric, value,
+ms_per_step, ...).  --full adds everything else: the per-kernel probe and the dominant kernel's
+roofline (HIP events around its launches in the timed region), and at N = 1 the CPU baseline, a
+parity check of the same pair against the reference's output (max error, PSNR), the fp32-MFMA
+value, the C1-C4 lines and the host-inclusive line (--no-extras / --no-cpu-baseline drop parts of
+it).  --dump-outputs DIR writes what the last timed step returned (decoding's output per time t) as
+DIR/out_t<i>.npy, float32; an output over the size budget is stored as a fixed seeded sample of it.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c0|c1|c2|c3|c4] [--full]
+                  [--dump-outputs DIR]
 """
 import argparse
 import glob
@@ -402,9 +410,10 @@ def parity_records(stif, sd, device, mfma):
     return recs
 
 
-def run_config(stif, sd, cfg, args, world, rank, device, dist, mfma, trace_dom=True):
+def run_config(stif, sd, cfg, args, world, rank, device, dist, mfma, trace_dom=True, keep_last=False):
     """Warm up, time args.steps steps of one config; returns (elapsed s, probe, timer, model, frames, tq,
-    out_pix per step over all ranks)."""
+    out_pix per step over all ranks, what the last timed step returned if keep_last).  trace_dom: the
+    kernel-table probe (two more untimed steps) and HIP events around the dominant kernel in the timed region."""
     nframes, H, W, scale, times, scaling = CONFIGS[cfg]
     P = stif.parallel
     if scaling == "weak":
@@ -459,15 +468,39 @@ def run_config(stif, sd, cfg, args, world, rank, device, dist, mfma, trace_dom=T
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        last = None
+        for i in range(args.steps):
+            out = step()
+            if keep_last and i == args.steps - 1:
+                last = out
+            del out   # a step's outputs are released before the next step runs
         torch.cuda.synchronize()
         if dist:
             dist.barrier()
         elapsed = time.perf_counter() - t0
         stif.ops.TRACE = None
     out_pix = total_pairs * len(times) * HH * WW
-    return elapsed, probe, timer, model, frames, tq, out_pix
+    return elapsed, probe, timer, model, frames, tq, out_pix, last
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # all of --dump-outputs' files together (under 64 MB with their headers)
+
+
+def dump_outputs(outs, path, suffix=""):
+    """Write the outputs of one step (decoding's list, one [pairs, 3, HH, WW] tensor per time t) as
+    path/out_t<i><suffix>.npy, float32.  Each gets an equal share of DUMP_BUDGET_BYTES; a larger one is
+    stored as its elements at fixed flat positions (sorted draws of a generator seeded by i, the same
+    for every run with the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(outs)) // 4
+    for i, o in enumerate(outs):
+        flat = o.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(i).integers(0, flat.numel(), size=share))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            arr = o.detach().cpu().numpy()
+        np.save(os.path.join(path, f"out_t{i}{suffix}.npy"), arr.astype(np.float32, copy=False))
 
 
 def host_inclusive(stif, sd, cfg, device, mfma, steps=3):
@@ -513,8 +546,13 @@ def main():
     ap.add_argument("--config", default="c0", choices=sorted(CONFIGS))
     ap.add_argument("--halo", default="exchange", choices=["exchange", "recompute"],
                     help="boundary frame of a shard: features from rank r+1 (P2P) or recomputed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="N=1: skip the fp32-MFMA and C1/C2 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: kernel probe + roofline of the dominant kernel, and at N=1 the CPU "
+                         "baseline, parity / PSNR, the other operand mode, C1-C4 and the host-inclusive line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/out_t<i>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity records")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N=1: skip the fp32-MFMA and C1-C4 lines")
     ap.add_argument("--traffic", default=None,
                     help="PMC summary (tools/pmc_summary.py) giving the dominant kernel's HBM bytes/dispatch; "
                          "default: the newest profiles/pmc_rNN_<config>.json")
@@ -569,10 +607,14 @@ def main():
     stif.ops.DYNAMIC_TILES = bool(args.dynamic_tiles)
     sd = stif.weights.make_state_dict(seed=0)
     nframes, H, W, scale, times, scaling = CONFIGS[args.config]
-    elapsed, probe, timer, model, frames, tq, out_pix = run_config(stif, sd, args.config, args, world, rank, device,
-                                                                   td, args.mfma)
+    elapsed, probe, timer, model, frames, tq, out_pix, last = run_config(stif, sd, args.config, args, world, rank,
+                                                                         device, td, args.mfma, trace_dom=args.full,
+                                                                         keep_last=bool(args.dump_outputs))
     dom = timer.kind
-    hot = hot_path_kernels(probe, args.mfma)
+    hot = hot_path_kernels(probe, args.mfma) if args.full else None
+    if args.dump_outputs and last is not None:
+        dump_outputs(last, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
+    del last
     if td is not None:
         t = torch.tensor([elapsed], device=device if args.backend == "nccl" else "cpu", dtype=torch.float64)
         td.all_reduce(t, op=td.ReduceOp.MAX)
@@ -632,14 +674,15 @@ def main():
                        "parallelism": (f"sequence pair-sharded x{world}, boundary-frame features by "
                                        f"{('RCCL P2P halo exchange' if args.backend == 'nccl' else 'gloo host-staged halo exchange') if args.halo == 'exchange' else 'recompute'}"
                                        if world > 1 else "1 GPU")},
-            "roofline": roofline(kname, kdesc, dom, peak, achieved, avg_ms, avg_flops, avg_bytes, timer.seen,
-                                 traffic, n_timed=n_launch),
-            "hot_path_kernels": hot,
+        }
+        if args.full:
+            res["roofline"] = roofline(kname, kdesc, dom, peak, achieved, avg_ms, avg_flops, avg_bytes, timer.seen,
+                                       traffic, n_timed=n_launch)
+            res["hot_path_kernels"] = hot
             # every kernel kind's share of the last warm-up step and its roofline fraction (the headline
             # `roofline` above is the dominant kind's, timed over the whole timed region)
-            "top_kernels": kernel_table(probe, args.mfma, top=6) if probe.rec else [],
-        }
-    if world == 1 and not args.no_extras and td is None:
+            res["top_kernels"] = kernel_table(probe, args.mfma, top=6) if probe.rec else []
+    if args.full and world == 1 and not args.no_extras and td is None:
         # the same workload with every contraction on fp32 MFMA and without the per-call f16x3 range sync,
         # then the other configs on this one GPU (C3 / C4: the whole sequence -- the 1-GPU denominators
         # of the strong-scaling runs), and the host-inclusive line (frames from host memory, outputs back)
@@ -657,7 +700,7 @@ def main():
             a2.range_check = rc
             del model
             torch.cuda.empty_cache()
-            el, _, _, model, fr2, tq2, px = run_config(stif, sd, cfg, a2, 1, 0, device, None, mf, trace_dom=False)
+            el, _, _, model, fr2, tq2, px, _ = run_config(stif, sd, cfg, a2, 1, 0, device, None, mf, trace_dom=False)
             key = f"{cfg}_{mf}" + ("_range_check_off" if rc == "off" else "")
             extras[key] = {"value": round(px * a2.steps / el / 1e6, 4), "unit": "Mpix/s",
                            "ms_per_step": round(el / a2.steps * 1e3, 3), "steps": a2.steps}
@@ -680,7 +723,7 @@ def main():
         torch.cuda.empty_cache()
         extras[f"{args.config}_host_inclusive"] = host_inclusive(stif, sd, args.config, device, args.mfma)
         res["extra_lines"] = extras
-    if rank == 0 and world == 1 and td is None and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and td is None and not args.no_cpu_baseline:
         res["parity"], res["parity_gratings"] = parity_records(stif, sd, device, args.mfma)
         res["cpu_baseline"] = cpu_baseline()
     if rank == 0:

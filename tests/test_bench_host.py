@@ -72,3 +72,23 @@ def test_dominant_kind_is_robust_to_side_streams(bench):
     assert t.dominant() == ("dcnsep", 0)
     t.per_kind = lambda: {}
     assert t.dominant() == ("none",)
+
+
+def test_dump_outputs_whole_and_sampled(bench, tmp_path, monkeypatch):
+    """--dump-outputs: an output within its share of the budget is written whole; a larger one as its
+    elements at fixed flat positions (the same in every run), all float32 and within the budget."""
+    import torch
+    outs = [torch.arange(2 * 3 * 8 * 8, dtype=torch.float32).reshape(2, 3, 8, 8) * s for s in (1.0, -2.0)]
+    bench.dump_outputs(outs, str(tmp_path / "whole"))
+    for i, o in enumerate(outs):
+        a = np.load(tmp_path / "whole" / f"out_t{i}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, o.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 100 * 4)
+    bench.dump_outputs(outs, str(tmp_path / "s1"), "_rank1")
+    bench.dump_outputs(outs, str(tmp_path / "s2"), "_rank1")
+    for i, o in enumerate(outs):
+        a = np.load(tmp_path / "s1" / f"out_t{i}_rank1.npy")
+        assert a.dtype == np.float32 and a.shape == (100,)
+        assert np.array_equal(a, np.load(tmp_path / "s2" / f"out_t{i}_rank1.npy"))
+        # values of arange * s at sorted positions: monotonic and all drawn from the output
+        assert np.all(np.diff(a * (1 if i == 0 else -1)) >= 0) and np.isin(a, o.numpy().ravel()).all()
