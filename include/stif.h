@@ -346,6 +346,40 @@ int stif_pack_dec_mlp_ex(const float* const* feat, const float* const* flow, con
 const char* stif_last_error(void);
 const char* stif_version(void);
 
+/* ---- windowed decoding: any rectangle of the virtual HH x WW grid at the cost of that rectangle ---- */
+
+/* A query rectangle of the virtual grid, the rectangle of the grid the HRfeat buffer holds, and where
+ * stage 2 writes.  Zero-initialise, then fill: all-zero F fields mean F = the query rectangle, all-zero
+ * out fields mean a dense [n][3][hh][ww] output. */
+typedef struct {
+  int y0, x0, hh, ww;      /* query rectangle: rows [y0, y0 + hh), columns [x0, x0 + ww); hh, ww >= 1 */
+  int fy0, fx0, fh, fw;    /* F rectangle: hrfeat is [n][fh][fw][64], pixel (r, c) = grid pixel (fy0 + r, fx0 + c) */
+  long long out_item;      /* stage-2 output addressing in elements: pixel (py, px) of the query rectangle, */
+  long long out_plane;     /* channel c, item i is out[i * out_item + c * out_plane + py * out_pitch + px], */
+  int out_pitch;           /* so a tile can be written straight into a larger [n][3][HH][WW] tensor */
+} stif_dec_window;
+
+/* stif_dec_stage1_ex over the query rectangle of `win`: HH, WW and the tables (stif_dec_image's too) stay those
+ * of the whole virtual grid; pixel (py, px) of the rectangle uses the table entries y0 + py, x0 + px.  flow:
+ * [n][hh][ww][4]; hrfeat: the pixel's row in the F layout (F must contain the query rectangle; with F = the
+ * query rectangle that is [n][hh][ww][64]).  flow = NULL: feat_imnet only (HRfeat of the rectangle, e.g. of an
+ * F rectangle larger than the window stage 2 is run for).  Tables with hr_y / hr_x are STIF_E_INVALID. */
+int stif_dec_stage1_win(const float* proj, const float* mlp, const stif_dec_tables* tab, const stif_dec_image* img,
+                        const float* t, float* hrfeat, float* flow, int n, int h, int w, int HH, int WW, int flags,
+                        int* status, void* stream, const stif_dec_window* win);
+/* box[0..3] = ymin, ymax, xmin, xmax (inclusive) over all n items of every HRfeat corner (row, column) stage 2
+ * reads for the query rectangle given its flow [n][hh][ww][4] -- the clamped corners of both warped grids,
+ * zero-weight corners included.  F must contain this box. */
+int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int n, int HH, int WW, void* stream,
+                    const stif_dec_window* win);
+/* stif_dec_stage2_ex over the query rectangle: flow [n][hh][ww][4], hrfeat in the F layout, RGB written through
+ * out_item / out_plane / out_pitch.  Every HRfeat index is clamped into F before use; if one had to be, bit 1
+ * (value 2) is OR'ed into *status (F was too small: the result is wrong, no read left the buffer).  Bit 0 as
+ * stif_dec_stage2_ex. */
+int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                        const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n, int h,
+                        int w, int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,13 @@ class DecImage(C.Structure):
         (n, _P) for n in ("by0", "by1", "wy0", "wy1", "bx0", "bx1", "wx0", "wx1")]
 
 
+class DecWindow(C.Structure):
+    """stif_dec_window: query rectangle, F rectangle (all zero = the query rectangle), stage-2 output
+    addressing in elements (all zero = a dense [n, 3, hh, ww])."""
+    _fields_ = [(n, C.c_int) for n in ("y0", "x0", "hh", "ww", "fy0", "fx0", "fh", "fw")] + [
+        ("out_item", C.c_longlong), ("out_plane", C.c_longlong), ("out_pitch", C.c_int)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "stif_conv2d_nhwc": (C.c_int, [C.POINTER(ConvArgs), _P]),
@@ -86,6 +93,11 @@ EXPORTS = {
                            + [C.c_int] * 6 + [_P, _P]),
     "stif_dec_stage2_ex": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecImage), _P, _P]
                            + [C.c_int] * 6 + [_P, _P]),
+    "stif_dec_stage1_win": (C.c_int, [_P, _P, C.POINTER(DecTables), C.POINTER(DecImage), _P, _P, _P]
+                            + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
+    "stif_dec_bounds": (C.c_int, [_P, C.POINTER(DecTables), _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(DecWindow)]),
+    "stif_dec_stage2_win": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecImage), _P, _P]
+                            + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
     "stif_dec_blend4": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "stif_upsample_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "stif_resize_frames": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int,

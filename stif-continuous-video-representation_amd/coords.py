@@ -96,3 +96,49 @@ def ensemble_weights(h: int, w: int, HH: int, WW: int) -> list:
             areas.append((np.abs(np.outer(t["rel_y"], t["rel_x"]).astype(F32)) + F32(1e-9)).astype(F32))
     tot = (((areas[0] + areas[1]).astype(F32) + areas[2]).astype(F32) + areas[3]).astype(F32)
     return [(areas[3 - k] / tot).astype(F32) for k in range(4)]
+
+
+def check_window(window, HH: int, WW: int) -> tuple:
+    """A window ``(y0, x0, hh, ww)`` of the virtual HH x WW grid as four ints; ValueError unless it is a
+    non-empty rectangle inside the grid."""
+    try:
+        y0, x0, hh, ww = (int(v) for v in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"window must be (y0, x0, hh, ww), got {window!r}") from None
+    if y0 < 0 or x0 < 0 or hh < 1 or ww < 1 or y0 + hh > HH or x0 + ww > WW:
+        raise ValueError(f"window {(y0, x0, hh, ww)} is not a non-empty rectangle of the {HH} x {WW} grid")
+    return y0, x0, hh, ww
+
+
+def tile_windows(region, tile) -> list:
+    """The windows of at most ``tile = (th, tw)`` pixels that cover ``region = (y0, x0, hh, ww)``, row-major
+    (the last tile of a row / column is ragged)."""
+    y0, x0, hh, ww = region
+    try:
+        th, tw = (int(v) for v in tile)
+    except (TypeError, ValueError):
+        raise ValueError(f"tile must be (th, tw), got {tile!r}") from None
+    if th < 1 or tw < 1:
+        raise ValueError(f"tile must be at least 1 x 1, got {(th, tw)}")
+    return [(y0 + i, x0 + j, min(th, hh - i), min(tw, ww - j)) for i in range(0, hh, th) for j in range(0, ww, tw)]
+
+
+def window_from_center(center, HH: int, WW: int, size) -> tuple:
+    """The reference zoom demo's rectangle (decoding_memory, Sakuya_arch_test.py:639-652) as a window
+    ``(y0, x0, hh, ww)``: ``center`` is (row, col) in [-1, 1]^2, ``size`` the rectangle's (rows, cols).  Per
+    axis the centre pixel is ``int((c + 1) / 2 * n)`` (truncation), the rectangle starts ``size // 2`` before it,
+    and a rectangle that sticks out of the frame is shifted back inside (the low edge is tested first)."""
+    out = []
+    for c, n, s in zip(center, (HH, WW), size):
+        n, s = int(n), int(s)
+        if s < 1 or s > n:
+            raise ValueError(f"window size {s} does not fit the grid axis of {n}")
+        mid = int((float(c) + 1) / 2 * n)
+        lo, hi = mid - s // 2, mid + s - s // 2
+        if lo < 0:
+            lo, hi = 0, hi - lo
+        elif hi > n:
+            lo, hi = lo - (hi - n), n
+        out.append((lo, hi))
+    (r0, r1), (c0, c1) = out
+    return check_window((r0, c0, r1 - r0, c1 - c0), HH, WW)

@@ -22,6 +22,12 @@
 #include "abi_util.h"
 
 #include <algorithm>
+#include <climits>
+#include <cstdio>
+
+// the windowed kernels (the WIN instantiations of k_dec1 / k_dec2 / k_dec2q, and k_dec_bounds) are product code: the probe and trace builds
+// do not compile them, and their entry points fail there
+#define DEC_WINDOWS (!DEC_EXP && !DEC_TRACE)
 
 namespace {
 
@@ -103,7 +109,11 @@ struct Bilin {  // grid_sample bilinear corners (align_corners=False, zeros padd
 
 // ATen grid_sampler_2d bilinear: ix = ((x + 1) * W - 1) / 2, corner weights
 // nw = (ix_se - ix) * (iy_se - iy), ...; corners outside the map contribute 0.
-STIF_DEV Bilin bilin(float gx, float gy, int Wd, int Hd) {
+struct Corners {  // the same, as clamped corner columns / rows
+  int cx0, cx1, cy0, cy1;
+  float w00, w01, w10, w11;
+};
+STIF_DEV Corners bilin_corners(float gx, float gy, int Wd, int Hd) {
   const float ix = ((gx + 1.f) * (float)Wd - 1.f) / 2.f;
   const float iy = ((gy + 1.f) * (float)Hd - 1.f) / 2.f;
   const float fx0 = floorf(ix), fy0 = floorf(iy);
@@ -114,13 +124,66 @@ STIF_DEV Bilin bilin(float gx, float gy, int Wd, int Hd) {
   const bool vy0 = y0 >= 0 && y0 < Hd, vy1 = y1 >= 0 && y1 < Hd;
   const int cx0 = min(max(x0, 0), Wd - 1), cx1 = min(max(x1, 0), Wd - 1);
   const int cy0 = min(max(y0, 0), Hd - 1), cy1 = min(max(y1, 0), Hd - 1);
-  Bilin b;
-  b.o00 = cy0 * Wd + cx0; b.o01 = cy0 * Wd + cx1; b.o10 = cy1 * Wd + cx0; b.o11 = cy1 * Wd + cx1;
+  Corners b;
+  b.cx0 = cx0; b.cx1 = cx1; b.cy0 = cy0; b.cy1 = cy1;
   b.w00 = (vx0 && vy0) ? wx0 * wy0 : 0.f;
   b.w01 = (vx1 && vy0) ? wx1 * wy0 : 0.f;
   b.w10 = (vx0 && vy1) ? wx0 * wy1 : 0.f;
   b.w11 = (vx1 && vy1) ? wx1 * wy1 : 0.f;
   return b;
+}
+STIF_DEV Bilin bilin(float gx, float gy, int Wd, int Hd) {
+  const Corners c = bilin_corners(gx, gy, Wd, Hd);
+  Bilin b;
+  b.o00 = c.cy0 * Wd + c.cx0; b.o01 = c.cy0 * Wd + c.cx1; b.o10 = c.cy1 * Wd + c.cx0; b.o11 = c.cy1 * Wd + c.cx1;
+  b.w00 = c.w00; b.w01 = c.w01; b.w10 = c.w10; b.w11 = c.w11;
+  return b;
+}
+
+// Stage 2's two warped grids of one HR pixel: warpgrid (warplayer.py:25-39) = linspace base + flow / ((n - 1) / 2)
+// over the virtual WW x HH grid, then the decoder's clamp to (-1 + 1e-6, 1 - 1e-6) (Sakuya_arch_test.py:428,441).
+// The HRfeat corners stage 2 reads are bilin_corners(g, WW, HH) of these; k_dec_bounds reduces the box of the same
+// expressions, so the two cannot drift apart.
+struct WarpGrids {
+  float g1x, g1y, g2x, g2y;
+};
+STIF_DEV WarpGrids warp_grids(const f32x4 fv, float bx, float by, int WW, int HH) {
+  const float lo = -1.f + 1e-6f, hi = 1.f - 1e-6f;
+  const float dx = ((float)WW - 1.f) / 2.f, dy = ((float)HH - 1.f) / 2.f;
+  WarpGrids g;
+  g.g1x = fminf(fmaxf(bx + fv[0] / dx, lo), hi), g.g1y = fminf(fmaxf(by + fv[1] / dy, lo), hi);
+  g.g2x = fminf(fmaxf(bx + fv[2] / dx, lo), hi), g.g2y = fminf(fmaxf(by + fv[3] / dy, lo), hi);
+  return g;
+}
+
+// The range report of stage 2; the windowed kernels OR bit 0 in, so that bilin_hr's bit 1 survives it
+template <bool WIN>
+STIF_DEV void report_range_w(int* status, bool bad) {
+  if constexpr (WIN) {
+    if (status != nullptr && bad) atomicOr(status, 1);
+  } else {
+    report_range(status, bad);
+  }
+}
+
+// The HRfeat gather of stage 2 at grid (gx, gy).  WIN: hrfeat holds the F rectangle of the grid, [fh][fw][64]; a
+// corner outside it is clamped into it and reported (bit 1 of *status), so a too-small F gives a flagged wrong
+// result and never an out-of-range read.
+template <bool WIN>
+STIF_DEV Bilin bilin_hr(float gx, float gy, int WW, int HH, const stif_dec_window& win, int* status) {
+  if constexpr (!WIN) {
+    return bilin(gx, gy, WW, HH);
+  } else {
+    const Corners c = bilin_corners(gx, gy, WW, HH);
+    const int ry0 = c.cy0 - win.fy0, ry1 = c.cy1 - win.fy0, rx0 = c.cx0 - win.fx0, rx1 = c.cx1 - win.fx0;
+    const int y0 = min(max(ry0, 0), win.fh - 1), y1 = min(max(ry1, 0), win.fh - 1);
+    const int x0 = min(max(rx0, 0), win.fw - 1), x1 = min(max(rx1, 0), win.fw - 1);
+    if (status != nullptr && (y0 != ry0 || y1 != ry1 || x0 != rx0 || x1 != rx1)) atomicOr(status, 2);
+    Bilin b;
+    b.o00 = y0 * win.fw + x0; b.o01 = y0 * win.fw + x1; b.o10 = y1 * win.fw + x0; b.o11 = y1 * win.fw + x1;
+    b.w00 = c.w00; b.w01 = c.w01; b.w10 = c.w10; b.w11 = c.w11;
+    return b;
+  }
 }
 
 // bilinear sample of channel block [c0, c0+64) of an NHWC map with `stride` channels,
@@ -338,12 +401,16 @@ constexpr int S1 = OCC1<MODE, HRIMG> == 4 ? 4 : OCC1<MODE, HRIMG> == 3 ? 6 : SEG
 // segment for 256 pixels instead of 128), 4 for the others
 template <int MODE, bool HRIMG>
 constexpr int NW1 = OCC1<MODE, HRIMG> == 4 ? DEC1_NW : 4;
-template <int MODE, bool HRIMG, int F16>
+// WIN: the pixels are those of win's query rectangle (row-major, hh x ww per item); the tables are read at the
+// pixel's row / column of the virtual grid, flow is written at the pixel's index in the rectangle and HRfeat at its
+// place in win's F rectangle; the whole-grid instantiations (WIN false) never read win.
+template <int MODE, bool HRIMG, int F16, bool WIN>
 __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_waves_per_eu(OCC1<MODE, HRIMG>))) void k_dec1(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      stif_dec_tables tb, stif_dec_image im,
                                                      const float* __restrict__ tq, float* __restrict__ hrfeat,
                                                      float* __restrict__ flow, int n, int h, int w, int HH,
-                                                     int WW) {
+                                                     int WW, stif_dec_window win) {
+  static_assert(!(WIN && MODE == 2), "the local ensemble's remapped HRfeat operand has no windowed form");
   // two segment buffers of SEG1 tiles + the flow's last layer (plain [4][256], resident)
   constexpr bool OCC3 = S1<MODE, HRIMG> != SEG1;             // 3 or 4 workgroups per CU
   constexpr bool OCC4 = OCC1<MODE, HRIMG> == 4;
@@ -362,13 +429,15 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
     dma_tiles<DEC_NW>(B1, rm, L_W0, 4, wv, lane);
     dma_tiles<DEC_NW>(B1 + 4 * T, rm, L_W1, 4, wv, lane);
   }
-  const long long total = (long long)n * HH * WW;
+  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
+  const long long total = (long long)n * GH * GW;
   const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * DEC_NW + wv) * 32 + (lane & 31);
   const bool valid = p < total;
   const long long pc = valid ? p : total - 1;
-  const int item = (int)(pc / ((long long)HH * WW));
-  const int rem = (int)(pc - (long long)item * HH * WW);
-  const int py = rem / WW, px = rem - py * WW;
+  const int item = (int)(pc / ((long long)GH * GW));
+  const int rem = (int)(pc - (long long)item * GH * GW);
+  const int ly = rem / GW, lx = rem - ly * GW;
+  const int py = WIN ? win.y0 + ly : ly, px = WIN ? win.x0 + lx : lx;   // row / column of the virtual grid
   const float t = tq[item];
   const float* P = proj + (size_t)item * h * w * PROJ_C;
 
@@ -448,7 +517,7 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
 #pragma unroll
   for (int ot = 0; ot < 2; ++ot) hr[ot] = bias_add<F16>(hr[ot], mlp + F_B3 + ot * 32, hf);
   if (valid) {
-    float* o = hrfeat + (size_t)pc * 64;
+    float* o = hrfeat + (WIN ? ((size_t)item * win.fh + (py - win.fy0)) * win.fw + (px - win.fx0) : (size_t)pc) * 64;
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
@@ -767,12 +836,15 @@ __global__ __launch_bounds__(RW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
   }
 }
 
-template <bool HRIMG, int F16>
+// WIN: the pixels are those of win's query rectangle, flow is read at the
+// pixel's index in the rectangle, the linspace base at its row / column of the virtual grid, HRfeat in win's F
+// rectangle (bilin_hr) and the RGB goes through win's output addressing.
+template <bool HRIMG, int F16, bool WIN>
 __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DEC2_WPE))) void k_dec2(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      const float* __restrict__ hrfeat, const float* __restrict__ flow,
                                                      stif_dec_tables tb, stif_dec_image im,
                                                      const float* __restrict__ tq, float* __restrict__ out, int n,
-                                                     int h, int w, int HH, int WW, int* status) {
+                                                     int h, int w, int HH, int WW, int* status, stif_dec_window win) {
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEG * T];
   const int lane = threadIdx.x & 63, hf = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
@@ -782,25 +854,23 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   // segments: [L0: 8 tiles] [L1: 4] then per layer-2 tile kt: [W2 rows kt (2) + W3 column kt (8)],
   // then [W4: 8]
   dma_tiles<DEC2_NW>(B0, rm, E_W0, 8, wv, lane);
-  const long long total = (long long)n * HH * WW;
+  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
+  const long long total = (long long)n * GH * GW;
   const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * DEC2_NW + wv) * 32 + (lane & 31);
   const bool valid = p < total;
   const long long pc = valid ? p : total - 1;
-  const int item = (int)(pc / ((long long)HH * WW));
-  const int rem = (int)(pc - (long long)item * HH * WW);
-  const int py = rem / WW, px = rem - py * WW;
+  const int item = (int)(pc / ((long long)GH * GW));
+  const int rem = (int)(pc - (long long)item * GH * GW);
+  const int py = rem / GW, px = rem - py * GW;
   const float t = tq[item];
   const float* P = proj + (size_t)item * h * w * PROJ_C;
-  const float* HRF = hrfeat + (size_t)item * HH * WW * 64;
+  const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
 
-  // warpgrid (warplayer.py:25-39): linspace grid + flow / ((n - 1) / 2), then the decoder's
-  // clamp to (-1 + 1e-6, 1 - 1e-6) (Sakuya_arch_test.py:428,441)
+  // warpgrid and the decoder's clamp (warp_grids)
   const f32x4 fv = ld4(flow + (size_t)pc * 4);
-  const float lo = -1.f + 1e-6f, hi = 1.f - 1e-6f;
-  const float dx = ((float)WW - 1.f) / 2.f, dy = ((float)HH - 1.f) / 2.f;
-  const float bx = tb.lin_x[px], by = tb.lin_y[py];
-  const float g1x = fminf(fmaxf(bx + fv[0] / dx, lo), hi), g1y = fminf(fmaxf(by + fv[1] / dy, lo), hi);
-  const float g2x = fminf(fmaxf(bx + fv[2] / dx, lo), hi), g2y = fminf(fmaxf(by + fv[3] / dy, lo), hi);
+  const float bx = tb.lin_x[WIN ? win.x0 + px : px], by = tb.lin_y[WIN ? win.y0 + py : py];
+  const WarpGrids wg = warp_grids(fv, bx, by, WW, HH);
+  const float g1x = wg.g1x, g1y = wg.g1y, g2x = wg.g2x, g2y = wg.g2y;
 
   // ---- encode_imnet layer 0: W[:, :128] . [q_feat1 | q_feat2] + P3(grid1) + P4(grid2) + w_t t + b
   f32x16 x0[2];
@@ -827,7 +897,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
       img_mma(z, mlp + I_E2, img_sample(I, bilin(g2x, g2y, im.iw, im.ih), hf), lane);
     }
     asm volatile("" ::: "memory");
-    gather64(q, HRF, 64, 0, bilin(g1x, g1y, WW, HH), hf);   // q_feat1 -> W0 columns 0..63
+    gather64(q, HRF, 64, 0, bilin_hr<WIN>(g1x, g1y, WW, HH, win, status), hf);   // q_feat1 -> W0 columns 0..63
     dec_barrier();
     dma_tiles<DEC2_NW>(B1, rm, E_W1, 4, wv, lane);
     {
@@ -838,7 +908,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
         for (int kt = 0; kt < 2; ++kt) tile_mma<F16>(z[ot], B0 + (ot * 4 + kt) * T, qs[kt], lane);
     }
     asm volatile("" ::: "memory");
-    gather64(q, HRF, 64, 0, bilin(g2x, g2y, WW, HH), hf);   // q_feat2 -> W0 columns 64..127
+    gather64(q, HRF, 64, 0, bilin_hr<WIN>(g2x, g2y, WW, HH, win, status), hf);   // q_feat2 -> W0 columns 64..127
     const XT<F16> qs[2] = {xop<F16>(q[0]), xop<F16>(q[1])};
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot) {
@@ -909,8 +979,9 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
 #pragma unroll
   for (int c = 0; c < 3; ++c) o4[c] += __shfl_xor(o4[c], 32);   // the other lane half's 128 features
   if (valid && hf == 0) {
-    const size_t plane = (size_t)HH * WW;
-    float* o = out + (size_t)item * 3 * plane + (size_t)py * WW + px;
+    const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
+    float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
+                   : out + (size_t)item * 3 * plane + (size_t)py * WW + px;
     // stage 1's flow counts too: the warpgrid clamp above maps a NaN flow to a finite grid, so an
     // out-of-range flow_imnet operand would otherwise leave a finite but wrong pixel
     bool bad = not_finite((fv[0] + fv[1]) + (fv[2] + fv[3]));
@@ -920,7 +991,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
       bad |= not_finite(v);
       o[c * plane] = v;
     }
-    if (F16) report_range(status, bad);
+    if (F16) report_range_w<WIN>(status, bad);
   }
 }
 
@@ -1015,10 +1086,11 @@ STIF_DEV void gather_q(R32* dst, const float* __restrict__ base, int stride, int
   }
 }
 
+template <bool WIN>   // WIN: as k_dec2's
 __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec2q(
     const float* __restrict__ proj, const float* __restrict__ mlp, const float* __restrict__ hrfeat,
     const float* __restrict__ flow, stif_dec_tables tb, const float* __restrict__ tq, float* __restrict__ out, int n,
-    int h, int w, int HH, int WW, int* status) {
+    int h, int w, int HH, int WW, int* status, stif_dec_window win) {
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEGQ * T];
 #if DEC_TRACE
   const unsigned tr0 = (unsigned)__builtin_amdgcn_s_memtime();
@@ -1047,25 +1119,24 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
       dec_dma(rm, dst + j * T + (i & 3) * 256, lane, src * 4);
     }
   };
-  const long long total = (long long)n * HH * WW;
+  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
+  const long long total = (long long)n * GH * GW;
   const long long pix = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW + wv) * 16 + (lane & 15);
   const bool valid = pix < total;
   const long long pc = valid ? pix : total - 1;
-  const int item = (int)(pc / ((long long)HH * WW));
-  const int rem = (int)(pc - (long long)item * HH * WW);
-  const int py = rem / WW, px = rem - py * WW;
+  const int item = (int)(pc / ((long long)GH * GW));
+  const int rem = (int)(pc - (long long)item * GH * GW);
+  const int py = rem / GW, px = rem - py * GW;
   const float t = tq[item];
   const float* P = proj + (size_t)item * h * w * PROJ_C;
-  const float* HRF = hrfeat + (size_t)item * HH * WW * 64;
+  const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
 
   // warpgrid (warplayer.py:25-39) and the decoder's clamp (Sakuya_arch_test.py:428,441), as k_dec2
   DTR_BEGIN();
   const f32x4 fv = ld4(flow + (size_t)pc * 4);
-  const float lo = -1.f + 1e-6f, hi = 1.f - 1e-6f;
-  const float dx = ((float)WW - 1.f) / 2.f, dy = ((float)HH - 1.f) / 2.f;
-  const float bx = tb.lin_x[px], by = tb.lin_y[py];
-  const float g1x = fminf(fmaxf(bx + fv[0] / dx, lo), hi), g1y = fminf(fmaxf(by + fv[1] / dy, lo), hi);
-  const float g2x = fminf(fmaxf(bx + fv[2] / dx, lo), hi), g2y = fminf(fmaxf(by + fv[3] / dy, lo), hi);
+  const float bx = tb.lin_x[WIN ? win.x0 + px : px], by = tb.lin_y[WIN ? win.y0 + py : py];
+  const WarpGrids wg = warp_grids(fv, bx, by, WW, HH);
+  const float g1x = wg.g1x, g1y = wg.g1y, g2x = wg.g2x, g2y = wg.g2y;
 
   // ---- encode_imnet layer 0: W[:, :128] . [q_feat1 | q_feat2] + P3(grid1) + P4(grid2) + w_t t + b
   R32 x0[2];
@@ -1085,7 +1156,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
           z[ot].s[s][e] = (z[ot].s[s][e] + (g[ot].s[s][e] + wt[e] * t + bb[e])) * ACC_IN<1>;
       }
     asm volatile("" ::: "memory");
-    gather_q(g, HRF, 64, 0, bilin(g1x, g1y, WW, HH), q);   // q_feat1 -> W0 columns 0..63
+    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(g1x, g1y, WW, HH, win, status), q);   // q_feat1 -> W0 columns 0..63
     DTR_END(tr_g);
     DTR_BEGIN();
     dec_barrier();                                      // layer 0 landed in B0
@@ -1100,7 +1171,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
     }
     asm volatile("" ::: "memory");
     DTR_BEGIN();
-    gather_q(g, HRF, 64, 0, bilin(g2x, g2y, WW, HH), q);   // q_feat2 -> W0 columns 64..127
+    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(g2x, g2y, WW, HH, win, status), q);   // q_feat2 -> W0 columns 64..127
     DTR_END(tr_g);
     const XQ qs[2] = {xq(g[0]), xq(g[1])};
 #pragma unroll
@@ -1199,8 +1270,9 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
     o4[c] += __shfl_xor(o4[c], 32);
   }
   if (valid && q == 0) {
-    const size_t plane = (size_t)HH * WW;
-    float* o = out + (size_t)item * 3 * plane + (size_t)py * WW + px;
+    const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
+    float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
+                   : out + (size_t)item * 3 * plane + (size_t)py * WW + px;
     bool bad = not_finite((fv[0] + fv[1]) + (fv[2] + fv[3]));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -1208,7 +1280,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
       bad |= not_finite(v);
       o[c * plane] = v;
     }
-    report_range(status, bad);
+    report_range_w<WIN>(status, bad);
   }
 #if DEC_TRACE
   if (g_dtrace && lane == 0) {
@@ -1220,6 +1292,45 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
 #undef DTR_BEGIN
 #undef DTR_END
 }
+
+#if DEC_WINDOWS
+// k_dec_bounds: the box (rows ymin..ymax, columns xmin..xmax of the virtual grid, inclusive) of every HRfeat corner
+// stage 2 reads for win's query rectangle given its flow -- warp_grids + bilin_corners, the expressions of stage 2
+// itself on the same operands, so the box is exact; corners of weight 0 count (stage 2 loads them).  One box for
+// all n items: each lane folds its pixels, the wave reduces across lanes, lane 0 issues one atomic per bound.
+__global__ void k_dec_bounds_init(int* __restrict__ box) {
+  if (threadIdx.x < 4) box[threadIdx.x] = (threadIdx.x & 1) ? INT_MIN : INT_MAX;
+}
+__global__ __launch_bounds__(256) void k_dec_bounds(const float* __restrict__ flow, stif_dec_tables tb,
+                                                    int* __restrict__ box, long long total, int HH, int WW,
+                                                    stif_dec_window win) {
+  int ymin = INT_MAX, ymax = INT_MIN, xmin = INT_MAX, xmax = INT_MIN;
+  const int plane = win.hh * win.ww;
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
+    const int rem = (int)(p % plane);
+    const int py = rem / win.ww, px = rem - py * win.ww;
+    const WarpGrids g = warp_grids(ld4(flow + (size_t)p * 4), tb.lin_x[win.x0 + px], tb.lin_y[win.y0 + py], WW, HH);
+    const Corners a = bilin_corners(g.g1x, g.g1y, WW, HH), b = bilin_corners(g.g2x, g.g2y, WW, HH);
+    ymin = min(ymin, min(min(a.cy0, a.cy1), min(b.cy0, b.cy1)));
+    ymax = max(ymax, max(max(a.cy0, a.cy1), max(b.cy0, b.cy1)));
+    xmin = min(xmin, min(min(a.cx0, a.cx1), min(b.cx0, b.cx1)));
+    xmax = max(xmax, max(max(a.cx0, a.cx1), max(b.cx0, b.cx1)));
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    ymin = min(ymin, __shfl_xor(ymin, m));
+    ymax = max(ymax, __shfl_xor(ymax, m));
+    xmin = min(xmin, __shfl_xor(xmin, m));
+    xmax = max(xmax, __shfl_xor(xmax, m));
+  }
+  if ((threadIdx.x & 63) == 0 && ymin <= ymax) {   // a wave that saw no pixel has nothing to add
+    atomicMin(box + 0, ymin);
+    atomicMax(box + 1, ymax);
+    atomicMin(box + 2, xmin);
+    atomicMax(box + 3, xmax);
+  }
+}
+#endif
 
 __global__ __launch_bounds__(256) void k_pack_lr(const float* __restrict__ f0, const float* __restrict__ f1,
                                                  const float* __restrict__ f2, const float* __restrict__ x,
@@ -1292,11 +1403,11 @@ void launch_dec1(bool f16, long long total, hipStream_t st, const float* proj, c
   constexpr int nw = NW1<MODE, HRIMG>;
   const long long blocks = (total + nw * 32 - 1) / (nw * 32);
   if (f16)
-    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1>), dim3((unsigned)blocks), dim3(nw * 64), 0, st, proj, mlp, tb, im,
-                       t, hrfeat, flow, n, h, w, HH, WW);
+    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1, false>), dim3((unsigned)blocks), dim3(nw * 64), 0, st, proj, mlp, tb, im,
+                       t, hrfeat, flow, n, h, w, HH, WW, stif_dec_window{});
   else
-    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0>), dim3((unsigned)blocks), dim3(nw * 64), 0, st, proj, mlp, tb, im,
-                       t, hrfeat, flow, n, h, w, HH, WW);
+    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0, false>), dim3((unsigned)blocks), dim3(nw * 64), 0, st, proj, mlp, tb, im,
+                       t, hrfeat, flow, n, h, w, HH, WW, stif_dec_window{});
 }
 
 }  // namespace
@@ -1348,15 +1459,15 @@ extern "C" int stif_dec_stage2_ex(const float* proj, const float* mlp, const flo
   hipStream_t st = (hipStream_t)stream;
   if (DEC2_Q16 && f16 && !img) {
     const long long qblocks = (total + DEC2Q_NWV * 16 - 1) / (DEC2Q_NWV * 16);
-    hipLaunchKernelGGL(k_dec2q, dim3((unsigned)qblocks), dim3(DEC2Q_NWV * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
-                       out, n, h, w, HH, WW, status);
+    hipLaunchKernelGGL(k_dec2q<false>, dim3((unsigned)qblocks), dim3(DEC2Q_NWV * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
+                       out, n, h, w, HH, WW, status, stif_dec_window{});
     return stif_check_launch("stif_dec_stage2");
   }
   const dim3 g((unsigned)blocks), b(DEC2_NW * 64);
-  if (img && f16) hipLaunchKernelGGL((k_dec2<true, 1>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status);
-  else if (img) hipLaunchKernelGGL((k_dec2<true, 0>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status);
-  else if (f16) hipLaunchKernelGGL((k_dec2<false, 1>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status);
-  else hipLaunchKernelGGL((k_dec2<false, 0>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status);
+  if (img && f16) hipLaunchKernelGGL((k_dec2<true, 1, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
+  else if (img) hipLaunchKernelGGL((k_dec2<true, 0, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
+  else if (f16) hipLaunchKernelGGL((k_dec2<false, 1, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
+  else hipLaunchKernelGGL((k_dec2<false, 0, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
   return stif_check_launch("stif_dec_stage2");
 }
 
@@ -1364,6 +1475,138 @@ extern "C" int stif_dec_stage2(const float* proj, const float* mlp, const float*
                                const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n,
                                int h, int w, int HH, int WW, void* stream) {
   return stif_dec_stage2_ex(proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, 0, nullptr, stream);
+}
+
+// ---- windowed decoding
+namespace {
+
+bool rect_in(int y0, int x0, int hh, int ww, int HH, int WW) {
+  return y0 >= 0 && x0 >= 0 && hh >= 1 && ww >= 1 && hh <= HH - y0 && ww <= WW - x0;
+}
+
+// the window with its defaults filled in (F = the query rectangle, dense output), or the reason it is invalid
+const char* window_resolve(const stif_dec_window* in, int HH, int WW, stif_dec_window* o) {
+  if (!in) return "null window";
+  if (HH < 1 || WW < 1 || (long long)HH * WW > INT_MAX) return "bad virtual grid size";
+  *o = *in;
+  if (!rect_in(o->y0, o->x0, o->hh, o->ww, HH, WW)) return "the query rectangle is not inside the HH x WW grid";
+  if (!o->fy0 && !o->fx0 && !o->fh && !o->fw) {
+    o->fy0 = o->y0; o->fx0 = o->x0; o->fh = o->hh; o->fw = o->ww;
+  }
+  if (!rect_in(o->fy0, o->fx0, o->fh, o->fw, HH, WW)) return "the F rectangle is not inside the HH x WW grid";
+  if (!o->out_item && !o->out_plane && !o->out_pitch) {
+    o->out_pitch = o->ww;
+    o->out_plane = (long long)o->hh * o->ww;
+    o->out_item = 3 * o->out_plane;
+  }
+  if (o->out_pitch < o->ww) return "out_pitch < ww";
+  if (o->out_plane < 1 || o->out_item < 1) return "out_item / out_plane must be positive";
+  return nullptr;
+}
+
+bool f_holds_query(const stif_dec_window& wn) {
+  return wn.fy0 <= wn.y0 && wn.fx0 <= wn.x0 && wn.y0 + wn.hh <= wn.fy0 + wn.fh && wn.x0 + wn.ww <= wn.fx0 + wn.fw;
+}
+
+int window_fail(const char* entry, const char* why) {
+  char msg[200];
+  snprintf(msg, sizeof msg, "%s: %s", entry, why);
+  return stif_fail(STIF_E_INVALID, msg);
+}
+
+#if DEC_WINDOWS
+template <int MODE, bool HRIMG>
+void launch_dec1w(bool f16, hipStream_t st, const float* proj, const float* mlp, const stif_dec_tables& tb,
+                  const stif_dec_image& im, const float* t, float* hrfeat, float* flow, int n, int h, int w, int HH,
+                  int WW, const stif_dec_window& wn) {
+  constexpr int nw = NW1<MODE, HRIMG>;
+  const long long total = (long long)n * wn.hh * wn.ww;
+  const dim3 g((unsigned)((total + nw * 32 - 1) / (nw * 32))), b(nw * 64);
+  if (f16) hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1, true>), g, b, 0, st, proj, mlp, tb, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
+  else hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0, true>), g, b, 0, st, proj, mlp, tb, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
+}
+#endif
+
+}  // namespace
+
+extern "C" int stif_dec_stage1_win(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                   const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
+                                   int w, int HH, int WW, int flags, int* status, void* stream,
+                                   const stif_dec_window* win) {
+  (void)status;   // as stif_dec_stage1_ex: stage 2 checks what it reads
+  static const char* const me = "stif_dec_stage1_win";
+  if (!proj || !mlp || !tables_ok(tab) || !image_ok(img) || !t || !hrfeat || n < 1 || h < 1 || w < 1)
+    return window_fail(me, "bad arguments (null pointer or empty shape)");
+  if (tab->hr_y || tab->hr_x) return window_fail(me, "tables with hr_y / hr_x (local ensemble) have no windowed form");
+  stif_dec_window wn;
+  if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
+  // every pixel of the query rectangle stores its HRfeat row into the F layout
+  if (!f_holds_query(wn)) return window_fail(me, "the F rectangle does not contain the query rectangle");
+#if DEC_WINDOWS
+  const bool f16 = flags & STIF_CONV_F16X3;
+  hipStream_t st = (hipStream_t)stream;
+  const stif_dec_image im = img ? *img : stif_dec_image{};
+  if (!flow) {
+    if (img) launch_dec1w<1, true>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
+    else launch_dec1w<1, false>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
+  } else if (img) {
+    launch_dec1w<0, true>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
+  } else {
+    launch_dec1w<0, false>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
+  }
+  return stif_check_launch(me);
+#else
+  return window_fail(me, "not built into the probe / trace variants of the library");
+#endif
+}
+
+extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int n, int HH, int WW,
+                               void* stream, const stif_dec_window* win) {
+  static const char* const me = "stif_dec_bounds";
+  if (!flow || !tables_ok(tab) || !box || n < 1) return window_fail(me, "bad arguments (null pointer or n < 1)");
+  stif_dec_window wn;
+  if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
+#if DEC_WINDOWS
+  const long long total = (long long)n * wn.hh * wn.ww;
+  const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_dec_bounds_init, dim3(1), dim3(64), 0, st, box);
+  hipLaunchKernelGGL(k_dec_bounds, dim3(blocks), dim3(256), 0, st, flow, *tab, box, total, HH, WW, wn);
+  return stif_check_launch(me);
+#else
+  return window_fail(me, "not built into the probe / trace variants of the library");
+#endif
+}
+
+extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                   const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
+                                   int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                   const stif_dec_window* win) {
+  static const char* const me = "stif_dec_stage2_win";
+  if (!proj || !mlp || !hrfeat || !flow || !tables_ok(tab) || !image_ok(img) || !t || !out || n < 1 || h < 1 || w < 1)
+    return window_fail(me, "bad arguments (null pointer or empty shape)");
+  stif_dec_window wn;
+  if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
+#if DEC_WINDOWS
+  const bool f16 = flags & STIF_CONV_F16X3;
+  const long long total = (long long)n * wn.hh * wn.ww;
+  const stif_dec_image im = img ? *img : stif_dec_image{};
+  hipStream_t st = (hipStream_t)stream;
+  if (DEC2_Q16 && f16 && !img) {
+    const long long qblocks = (total + DEC2Q_NWV * 16 - 1) / (DEC2Q_NWV * 16);
+    hipLaunchKernelGGL(k_dec2q<true>, dim3((unsigned)qblocks), dim3(DEC2Q_NWV * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
+                       out, n, h, w, HH, WW, status, wn);
+    return stif_check_launch(me);
+  }
+  const dim3 g((unsigned)((total + DEC2_NW * 32 - 1) / (DEC2_NW * 32))), b(DEC2_NW * 64);
+  if (img && f16) hipLaunchKernelGGL((k_dec2<true, 1, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
+  else if (img) hipLaunchKernelGGL((k_dec2<true, 0, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
+  else if (f16) hipLaunchKernelGGL((k_dec2<false, 1, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
+  else hipLaunchKernelGGL((k_dec2<false, 0, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
+  return stif_check_launch(me);
+#else
+  return window_fail(me, "not built into the probe / trace variants of the library");
+#endif
 }
 
 #if DEC_TRACE

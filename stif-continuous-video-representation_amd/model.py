@@ -30,7 +30,7 @@ from torch import nn
 from . import _lib as L
 from . import ops
 from . import weights as W
-from .coords import ensemble_weights
+from .coords import check_window, ensemble_weights, tile_windows, window_from_center
 
 _CONST_LOCK = threading.Lock()   # _const's dict is shared by DataParallel replicas (replicate() threads)
 
@@ -117,6 +117,8 @@ class LunaTokis(nn.Module):
         self.chunk_px = int(chunk_px)
         # HR pixels per decoder pass (decoding): bounds the decoder's scratch (~9 GB at the default)
         self.dec_chunk_px = int(dec_chunk_px)
+        self.last_window_F = None            # HRfeat rectangle of the last window decoded (_decode_windowed)
+        self.window_peak_scratch_bytes = 0   # and the largest per-pass decoder scratch of that call
         # independent pair ranges run as `lanes` concurrent HIP streams (_run_lanes), so one lane's kernels
         # could fill the others' tail waves and dispatch gaps; results do not depend on it.  Default 1:
         # at C0, 2 lanes measured 5 % slower (82.5 -> 76.7, 84.6 -> 80.4 Mpix/s, same box) -- the
@@ -930,11 +932,17 @@ class LunaTokis(nn.Module):
         _drain(self._decode_steps(proj, [self._time_vec(tq, B) for tq in times], HH, WW, tab, outs, image))
         return outs
 
-    def decoding(self, times=None, scale=None):
-        """LunaTokis.decoding (:364-459): list over times of [B,3,HH,WW] (unclamped)."""
-        return self._call(self._decoding, times, scale)
+    def decoding(self, times=None, scale=None, window=None, tile=None):
+        """LunaTokis.decoding (:364-459): list over times of [B,3,HH,WW] (unclamped).
 
-    def _decoding(self, times=None, scale=None):
+        window=(y0, x0, hh, ww): only that rectangle of the virtual HH x WW grid, [B,3,hh,ww], bit-identical to
+        the crop of the full decode and at the cost of the rectangle (``_decode_windowed``).  tile=(th, tw): the
+        same output as without it, rendered by windows of at most th x tw, so the decoder scratch is bounded by
+        the largest tile's HRfeat rectangle instead of HH * WW.  Either reads a few ints back from the device per
+        window and time, so such a call cannot be captured in a hipGraph."""
+        return self._call(self._decoding, times, scale, window, tile)
+
+    def _decoding(self, times=None, scale=None, window=None, tile=None):
         if times is None:
             raise ValueError("times must be a list of query times")
         if self._feat is None:
@@ -943,6 +951,8 @@ class LunaTokis(nn.Module):
         HH, WW = (H * 4, Wd * 4) if scale is None else (int(scale[0]), int(scale[1]))
         tab = self._tab(H, Wd, HH, WW)
         tvs = [self._time_vec(tq, B) for tq in times]
+        if window is not None or tile is not None:
+            return self._decode_windowed(tvs, HH, WW, tab, window, tile)
         outs = [self._empty(B, 3, HH, WW) for _ in times]
 
         # items per decode pass: the LR projections (1 KB per LR pixel) and the HRfeat / flow scratch
@@ -961,21 +971,121 @@ class LunaTokis(nn.Module):
         self._run_lanes(B, lane, self.dec_lanes, pool="dec")
         return outs
 
-    def decoding_test(self, times=None, scale=None):
+    def decoding_test(self, times=None, scale=None, window=None, tile=None):
         """LunaTokis.decoding_test (:461-598), what forward(test=True) returns: the flow and encode
         stages sample HRinp = F.upsample(inp, x4, bilinear) instead of the LR frames; HH = H * scale
-        (integer scale, default 4).  The reference's q/3 chunking only bounds its memory."""
-        return self._call(self._decoding_test, times, scale)
+        (integer scale, default 4).  The reference's q/3 chunking only bounds its memory.
+        window / tile: as ``decoding``."""
+        return self._call(self._decoding_test, times, scale, window, tile)
 
-    def _decoding_test(self, times=None, scale=None):
+    def _decoding_test(self, times=None, scale=None, window=None, tile=None):
         if times is None:
             raise ValueError("times must be a list of query times")
+        if window is not None or tile is not None:
+            if self._feat is None:
+                raise RuntimeError("decoding needs gen_feat first")
+            _, B, H, Wd, _ = self._feat.shape
+            s = 4 if scale is None else int(scale)
+            HH, WW = H * s, Wd * s
+            image = ops.DecImageDev(self.inp, 4, HH, WW)
+            return self._decode_windowed([self._time_vec(tq, B) for tq in times], HH, WW, self._tab(H, Wd, HH, WW),
+                                         window, tile, image)
         proj = self._projection(lr_image=False)
         _, H, Wd, _ = proj.shape
         s = 4 if scale is None else int(scale)
         HH, WW = H * s, Wd * s
         image = ops.DecImageDev(self.inp, 4, HH, WW)
         return self._decode(proj, times, HH, WW, self._tab(H, Wd, HH, WW), image)
+
+    # ------------------------------------------------------------------ windowed decoding
+    def _window_steps(self, proj, tvs, HH, WW, tab, outs, rect, image=None):
+        """Decoder stages of every query time for the window ``rect`` into ``outs`` ([n,3,hh,ww] views; generator).
+        Per time: stage 1 (HRfeat + flow) over the window W; the bounding box of the HRfeat rows / columns stage 2
+        will gather, read back from the device; F = box U W; if F is larger than W, HRfeat over F by a feat-only
+        stage 1 (recomputing W's part: two launches with one layout beat a scatter of W's rows into F, and W is
+        the smaller part whenever the flows matter); stage 2 over W.  The F passes take at most
+        dec_chunk_px // |F| items each."""
+        n = proj.shape[0]
+        y0, x0, hh, ww = rect
+        mlp, fl, st = self.layers["dec.mlp"], self._dec_flags, self._status
+        win = ops.dec_window(rect, HH, WW)
+        box = torch.empty(4, device=self.device, dtype=torch.int32)
+        for t, out in zip(tvs, outs):
+            hrf = self._empty(n, hh, ww, 64)
+            flow = self._empty(n, hh, ww, 4)
+            ops.dec_stage1(proj, mlp, tab, t, hrf, flow, image, flags=fl, status=st, window=win)
+            ops.dec_bounds(flow, tab, box, win)
+            ymin, ymax, xmin, xmax = box.tolist()   # the device-to-host read (synchronises this stream)
+            fy0, fx0 = min(ymin, y0), min(xmin, x0)
+            frect = (fy0, fx0, max(ymax + 1, y0 + hh) - fy0, max(xmax + 1, x0 + ww) - fx0)
+            per = max(1, self.dec_chunk_px // (frect[2] * frect[3]))
+            self.last_window_F = frect
+            self.window_peak_scratch_bytes = max(self.window_peak_scratch_bytes,
+                                                 min(n, per) * frect[2] * frect[3] * 272)
+            wf = ops.dec_window(rect, HH, WW, frect)
+            if frect == rect:
+                ops.dec_stage2(proj, mlp, hrf, flow, tab, t, out, image, flags=fl, status=st, window=wf)
+            else:
+                del hrf   # the caching allocator reuses it for the F buffer (same stream)
+                for a in range(0, n, per):
+                    b = min(n, a + per)
+                    img = image.items(a, b) if image is not None else None
+                    hf = self._empty(b - a, frect[2], frect[3], 64)
+                    ops.dec_stage1(proj[a:b], mlp, tab, t[a:b], hf, None, img, flags=fl, status=st,
+                                   window=ops.dec_window(frect, HH, WW))
+                    ops.dec_stage2(proj[a:b], mlp, hf, flow[a:b], tab, t[a:b], out[a:b], img, flags=fl, status=st,
+                                   window=wf)
+                    del hf
+            yield
+
+    def _decode_windowed(self, tvs, HH, WW, tab, window, tile, image=None):
+        """``decoding`` / ``decoding_test`` (image given) over ``window`` (None: the whole grid), rendered by
+        tiles of at most ``tile`` (None: one).  Every tile is a window written in place into the output through
+        its strides.  ``last_window_F`` is the HRfeat rectangle (fy0, fx0, fh, fw) of the last window decoded and
+        ``window_peak_scratch_bytes`` the largest per-pass HRfeat + flow scratch of the call (items x |F| x 272 B)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise L.StifError("a windowed / tiled decode reads the HRfeat bounding box back on the host: "
+                              "it cannot be captured in a hipGraph")
+        B = tvs[0].shape[0] if tvs else self._feat.shape[1]
+        region = check_window((0, 0, HH, WW) if window is None else window, HH, WW)
+        rects = [region] if tile is None else tile_windows(region, tile)
+        ry, rx, rh, rw = region
+        outs = [self._empty(B, 3, rh, rw) for _ in tvs]
+        self.last_window_F, self.window_peak_scratch_bytes = None, 0
+        st = self._status
+        if st is not None and self._dec_flags == 0:
+            st.zero_()   # fp32 operands: only the windows' bit 1 is read below
+        per = max(1, self.dec_chunk_px // max(r[2] * r[3] for r in rects))
+
+        def lane(c0, c1):
+            for a in range(c0, c1, per):
+                b = min(c1, a + per)
+                proj = self._projection(image is None, a, b)
+                yield
+                img = image.items(a, b) if image is not None else None
+                for r in rects:
+                    views = [o[a:b, :, r[0] - ry:r[0] - ry + r[2], r[1] - rx:r[1] - rx + r[3]] for o in outs]
+                    yield from self._window_steps(proj, [t[a:b] for t in tvs], HH, WW, tab, views, r, img)
+                del proj
+        self._run_lanes(B, lane, self.dec_lanes, pool="dec")
+        if st is not None and int(st.item()) & 2:
+            raise L.StifError("windowed decode: stage 2 gathered outside its HRfeat rectangle (stif_dec_bounds and "
+                              "stage 2 disagree): the result is wrong")
+        return outs
+
+    def decoding_window(self, times=None, scale=None, center=(0.0, 0.0), size=None):
+        """The reference's zoom call (decoding_memory, Sakuya_arch_test.py:600-861): the ``size`` (default 4H x 4W)
+        rectangle of the virtual ``scale`` grid around ``center`` = (row, col) in [-1, 1]^2, placed by
+        ``coords.window_from_center`` -- the reference's rectangle arithmetic (:639-652).  The pixels are defined
+        as that crop of ``decoding``; the reference's decoding_memory builds its warp base from make_coord
+        (``warpgrid2``) instead of torch.linspace, i.e. it evaluates a slightly different function, which this
+        call does not reproduce."""
+        if self._feat is None:
+            raise RuntimeError("decoding needs gen_feat first")
+        _, _, H, Wd, _ = self._feat.shape
+        HH, WW = (H * 4, Wd * 4) if scale is None else (int(scale[0]), int(scale[1]))
+        size = (4 * H, 4 * Wd) if size is None else size
+        return self.decoding(times, scale, window=window_from_center(center, HH, WW, size))
 
     def decoding_fasttest(self, times=None, scale=None):
         """LunaTokis.decoding_fasttest (:863-960): `times` is a list of floats, the latent a batch of

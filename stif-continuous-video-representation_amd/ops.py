@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .coords import TABLE_ORDER, dec_tables
+from .coords import TABLE_ORDER, check_window, dec_tables
 
 # Optional launch tracer (bench.py sets it to time the dominant kernel with HIP events on
 # the launch stream): an object with begin(kind: tuple, flops: float) and end().
@@ -357,7 +357,15 @@ class DecImageDev:
         t = dec_tables(s * h, s * w, HH, WW)
         keys = ["b0_y", "b1_y", "w0_y", "w1_y", "b0_x", "b1_x", "w0_x", "w1_x"]
         self._t = {k: torch.from_numpy(np.ascontiguousarray(t[k])).to(x_nchw.device) for k in keys}
+        self._keys = keys
         self.c = L.DecImage(self.img.data_ptr(), s * h, s * w, *[self._t[k].data_ptr() for k in keys])
+
+    def items(self, a, b):
+        """The same image and tables for items [a, b) only (decoder passes over an item range)."""
+        o = object.__new__(DecImageDev)
+        o.img, o._t, o._keys = self.img[a:b], self._t, self._keys
+        o.c = L.DecImage(o.img.data_ptr(), self.c.ih, self.c.iw, *[o._t[k].data_ptr() for k in o._keys])
+        return o
 
 
 def dec_blend4(preds, weights, out):
@@ -374,8 +382,40 @@ def dec_pack_lr(f0, f1, f2, x, out):
             "stif_dec_pack_lr")
 
 
-def dec_stage1(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, image: "DecImageDev" = None, flags=0, status=None):
+def dec_window(rect, HH, WW, frect=None) -> L.DecWindow:
+    """A stif_dec_window for the query rectangle ``rect = (y0, x0, hh, ww)`` of the virtual HH x WW grid
+    (ValueError if it is not inside), HRfeat held over ``frect`` (None: the query rectangle itself)."""
+    y0, x0, hh, ww = check_window(rect, HH, WW)
+    win = L.DecWindow(y0, x0, hh, ww)
+    if frect is not None:
+        win.fy0, win.fx0, win.fh, win.fw = check_window(frect, HH, WW)
+    return win
+
+
+def _win_shapes(window, tables, n, hrfeat, flow):
+    """(HH, WW) of a windowed stage call after checking the buffers against the window's rectangles."""
+    HH, WW = tables.shape[2:]
+    check_window((window.y0, window.x0, window.hh, window.ww), HH, WW)
+    fh, fw = (window.fh, window.fw) if (window.fh or window.fw) else (window.hh, window.ww)
+    if tuple(hrfeat.shape) != (n, fh, fw, 64) or not hrfeat.is_contiguous():
+        raise ValueError(f"windowed decoder stage: hrfeat must be a contiguous {(n, fh, fw, 64)}, got {tuple(hrfeat.shape)}")
+    if flow is not None and (tuple(flow.shape) != (n, window.hh, window.ww, 4) or not flow.is_contiguous()):
+        raise ValueError(f"windowed decoder stage: flow must be a contiguous {(n, window.hh, window.ww, 4)}, "
+                         f"got {tuple(flow.shape)}")
+    return HH, WW
+
+
+def dec_stage1(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, image: "DecImageDev" = None, flags=0, status=None,
+               window: L.DecWindow = None):
+    """window (dec_window): the stage over that rectangle of the tables' grid -- flow [n, hh, ww, 4] (None: HRfeat
+    only), hrfeat over the window's F rectangle."""
     n, h, w, _ = proj.shape
+    if window is not None:
+        HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
+        L.check(L.lib().stif_dec_stage1_win(_vp(proj), _vp(mlp), C.byref(tables.c), C.byref(image.c) if image else None,
+                                            _vp(t), _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status),
+                                            _stream(), C.byref(window)), "stif_dec_stage1_win")
+        return
     HH, WW = hrfeat.shape[1:3]
     tr = TRACE
     if tr is not None:   # per HR px: feat_imnet layers 1-3 (36,864 MAC) + flow_imnet HRfeat/1-3 (25,600 MAC)
@@ -387,9 +427,35 @@ def dec_stage1(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, image: "DecImag
         tr.end()
 
 
+def dec_bounds(flow, tables: DecTablesDev, box, window: L.DecWindow):
+    """box (4 int32 on the device) = ymin, ymax, xmin, xmax of every HRfeat row / column stage 2 reads for the
+    window, given stage 1's flow [n, hh, ww, 4] over it."""
+    HH, WW = tables.shape[2:]
+    check_window((window.y0, window.x0, window.hh, window.ww), HH, WW)
+    n = flow.shape[0]
+    if tuple(flow.shape) != (n, window.hh, window.ww, 4) or not flow.is_contiguous():
+        raise ValueError(f"dec_bounds: flow must be a contiguous {(n, window.hh, window.ww, 4)}, got {tuple(flow.shape)}")
+    if box.dtype != torch.int32 or box.numel() != 4 or not box.is_contiguous():
+        raise ValueError("dec_bounds: box must be 4 contiguous int32")
+    L.check(L.lib().stif_dec_bounds(_vp(flow), C.byref(tables.c), _vp(box), n, HH, WW, _stream(), C.byref(window)),
+            "stif_dec_bounds")
+
+
 def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "DecImageDev" = None, flags=0,
-               status=None):
+               status=None, window: L.DecWindow = None):
+    """window (dec_window): the stage over that rectangle -- hrfeat over its F rectangle, flow [n, hh, ww, 4], and
+    out any [n, 3, hh, ww] view with unit column stride (e.g. a tile of a larger [n, 3, HH, WW] tensor)."""
     n, h, w, _ = proj.shape
+    if window is not None:
+        HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
+        if tuple(out.shape) != (n, 3, window.hh, window.ww) or (window.ww > 1 and out.stride(3) != 1):
+            raise ValueError(f"dec_stage2: out must be {(n, 3, window.hh, window.ww)} with unit column stride")
+        win = L.DecWindow.from_buffer_copy(window)
+        win.out_item, win.out_plane, win.out_pitch = out.stride(0), out.stride(1), out.stride(2)
+        L.check(L.lib().stif_dec_stage2_win(_vp(proj), _vp(mlp), _vp(hrfeat), _vp(flow), C.byref(tables.c),
+                                            C.byref(image.c) if image else None, _vp(t), _vp(out), n, h, w, HH, WW,
+                                            flags, _vp(status), _stream(), C.byref(win)), "stif_dec_stage2_win")
+        return
     HH, WW = hrfeat.shape[1:3]
     tr = TRACE
     if tr is not None:   # per HR px: encode_imnet HRfeat part + layers 1-4 (94,976 MAC)

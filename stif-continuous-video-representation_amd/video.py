@@ -44,13 +44,15 @@ def single_forward(model, imgs_in: torch.Tensor, times=None):
         return model(x, [torch.tensor([t])[None] for t in ts])
 
 
-def run_sequence(model, frames: torch.Tensor, times=None, scale=None):
-    """frames [F,3,h,w] -> list over the F-1 pairs of lists over times of [3,HH,WW]."""
+def run_sequence(model, frames: torch.Tensor, times=None, scale=None, window=None):
+    """frames [F,3,h,w] -> list over the F-1 pairs of lists over times of [3,HH,WW]; window=(y0, x0, hh, ww):
+    only that rectangle of every output frame, [3,hh,ww] (LunaTokis.decoding's window)."""
     with torch.no_grad():
         fr = pad_to_4(frames)
         model.gen_feat_window(fr)
         ts = HARNESS_TIMES if times is None else times
-        preds = model.decoding([torch.tensor([t])[None] for t in ts], scale)
+        kw = {} if window is None else {"window": window}
+        preds = model.decoding([torch.tensor([t])[None] for t in ts], scale, **kw)
     return [[p[i] for p in preds] for i in range(frames.shape[0] - 1)]
 
 
