@@ -11,8 +11,7 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -I$(PKG)/csrc -
 # issue cycles than the two v_fma_f32 it replaces (MI355X_MICROARCH.md): in same-box A/B runs the C0 step
 # is 0.7-1.5 % faster without them (Winograd transforms, SIREN sines and gathers, stride-2 / 1x1 convs,
 # upsample), and round 6 moved the fused DCN_sep kernel over as well: k_dcn_sep<0> 349 vs 362 us per
-# launch (profiles/r06_nopk_ab.log), and the tap-pipelined diagnostic variant whose output depended on
-# the co-resident workgroup is bit-stable without them.
+# launch (profiles/r06_nopk_ab.log).
 # Device-only feature: the host pass prints "not a recognized feature for this target (ignoring feature)".
 NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
 NOPK_SRC := wino decoder conv resample dcnsep dcn

@@ -25,10 +25,6 @@
 #include <climits>
 #include <cstdio>
 
-// the windowed kernels (the WIN instantiations of k_dec1 / k_dec2 / k_dec2q, and k_dec_bounds) are product code: the probe and trace builds
-// do not compile them, and their entry points fail there
-#define DEC_WINDOWS (!DEC_EXP && !DEC_TRACE)
-
 namespace {
 
 using namespace stif_dec;
@@ -300,17 +296,16 @@ STIF_DEV f32x4 img_sample(const float* __restrict__ I, const Bilin& b, int hf) {
 // waves per workgroup of k_dec1: 4-wave workgroups, DEC1_OCC per CU -- by default 4 (36 KB LDS, <= 128 VGPRs
 // each; the HRIMG variants stay at 3: 52 KB, <= 168, and MODE 2 at 2: 69 KB): the waves sharing a SIMD come from different
 // workgroups, so one's segment barrier, gather or sin stretch overlaps the others' MFMAs
+constexpr int NW1 = 4;       // k_dec1 (8-wave workgroups at four waves per SIMD: +8 %, profiles/r06_dec_ab.log)
 constexpr int DEC2_NW = 4;   // k_dec2: 8 layer-3 accumulator tiles (128 VGPRs) live
+constexpr int DEC2_WPE = 2;  // waves per SIMD k_dec2 is register-budgeted for (2 workgroups/CU, 80 KB LDS each)
 constexpr int SEG = 10;      // max tiles per segment (k_dec2)
 constexpr int SEG1 = 8;      // max tiles per segment (k_dec1)
 
 // Buffer loads with the tile offset in SGPRs: the per-lane operand is the same lane*16 for every
 // tile (flat global_load_lds would keep a 64-bit VGPR address per hoisted tile live).
-// Probe DEC_EXP 3 issues every piece with an out-of-range offset (the same instructions, no memory traffic: the
-// LDS receives zeros).  (A probe that issued no DMA at all, the former DEC_EXP 1, measured nothing: with the
-// weight buffers never written the compiler folded most of the MFMAs, LDS reads and sines that read them.)
 STIF_DEV void dec_dma(__amdgpu_buffer_rsrc_t rm, float* dst, int lane, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rm, dst, 16, DEC_EXP == 3 ? 0x80000000u : (unsigned)(lane * 16), soff, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rm, dst, 16, (unsigned)(lane * 16), soff, 0, 0);
 }
 template <int NW>
 STIF_DEV void dma_tiles(float* dst, __amdgpu_buffer_rsrc_t rm, int src, int ntiles, int wv, int lane) {
@@ -324,18 +319,6 @@ STIF_DEV void dma_tiles(float* dst, __amdgpu_buffer_rsrc_t rm, int src, int ntil
     for (int k = wv; k < ntiles * 4; k += NW)
       dec_dma(rm, dst + k * 256, lane, (src + k * 256) * 4);
   }
-}
-
-// the segment barrier of the weight stream (lds_dma_barrier); probe DEC_EXP 2 skips its vmcnt(0) wait, i.e. the
-// time the waves spend waiting for segments still in flight (wrong results)
-STIF_DEV void dec_barrier() {
-#if DEC_EXP == 2
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-#else
-  lds_dma_barrier();
-#endif
 }
 
 STIF_DEV __amdgpu_buffer_rsrc_t mlp_rsrc(const float* mlp) {
@@ -397,15 +380,11 @@ template <int MODE, bool HRIMG>
 constexpr int OCC1 = MODE == 2 ? 2 : (HRIMG && DEC1_OCC > 3) ? 3 : DEC1_OCC;
 template <int MODE, bool HRIMG>
 constexpr int S1 = OCC1<MODE, HRIMG> == 4 ? 4 : OCC1<MODE, HRIMG> == 3 ? 6 : SEG1;
-// waves per workgroup: DEC1_NW for the four-per-SIMD variants (8: two 8-wave workgroups per CU stream each weight
-// segment for 256 pixels instead of 128), 4 for the others
-template <int MODE, bool HRIMG>
-constexpr int NW1 = OCC1<MODE, HRIMG> == 4 ? DEC1_NW : 4;
 // WIN: the pixels are those of win's query rectangle (row-major, hh x ww per item); the tables are read at the
 // pixel's row / column of the virtual grid, flow is written at the pixel's index in the rectangle and HRfeat at its
 // place in win's F rectangle; the whole-grid instantiations (WIN false) never read win.
 template <int MODE, bool HRIMG, int F16, bool WIN>
-__global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_waves_per_eu(OCC1<MODE, HRIMG>))) void k_dec1(const float* __restrict__ proj, const float* __restrict__ mlp,
+__global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<MODE, HRIMG>))) void k_dec1(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      stif_dec_tables tb, stif_dec_image im,
                                                      const float* __restrict__ tq, float* __restrict__ hrfeat,
                                                      float* __restrict__ flow, int n, int h, int w, int HH,
@@ -414,7 +393,6 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
   // two segment buffers of SEG1 tiles + the flow's last layer (plain [4][256], resident)
   constexpr bool OCC3 = S1<MODE, HRIMG> != SEG1;             // 3 or 4 workgroups per CU
   constexpr bool OCC4 = OCC1<MODE, HRIMG> == 4;
-  constexpr int DEC_NW = NW1<MODE, HRIMG>;
   __shared__ __attribute__((aligned(16))) float wbuf[2 * S1<MODE, HRIMG> * T + T];
   const int lane = threadIdx.x & 63, hf = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
@@ -422,16 +400,16 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
   float* const B1 = wbuf + S1<MODE, HRIMG> * T;
   float* const W3V = wbuf + 2 * S1<MODE, HRIMG> * T;
   const __amdgpu_buffer_rsrc_t rm = mlp_rsrc(mlp);
-  if (MODE != 1) dma_tiles<DEC_NW>(W3V, rm, L_W3V, 1, wv, lane);
+  if (MODE != 1) dma_tiles<NW1>(W3V, rm, L_W3V, 1, wv, lane);
   // segment 0: feat layer 1 (4 tiles); segments 1..8: feat layer 2 tile kt + layer 3 (0, kt), (1, kt)
-  if (MODE != 2) dma_tiles<DEC_NW>(B0, rm, F_W1, 4, wv, lane);
+  if (MODE != 2) dma_tiles<NW1>(B0, rm, F_W1, 4, wv, lane);
   else {   // flow only: flow layers 0 / 1 straight into B1
-    dma_tiles<DEC_NW>(B1, rm, L_W0, 4, wv, lane);
-    dma_tiles<DEC_NW>(B1 + 4 * T, rm, L_W1, 4, wv, lane);
+    dma_tiles<NW1>(B1, rm, L_W0, 4, wv, lane);
+    dma_tiles<NW1>(B1 + 4 * T, rm, L_W1, 4, wv, lane);
   }
   const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
   const long long total = (long long)n * GH * GW;
-  const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * DEC_NW + wv) * 32 + (lane & 31);
+  const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW1 + wv) * 32 + (lane & 31);
   const bool valid = p < total;
   const long long pc = valid ? p : total - 1;
   const int item = (int)(pc / ((long long)GH * GW));
@@ -460,15 +438,15 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
       }
   }
   auto seg_feat23 = [&](float* dst, int kt) {   // W2 rows kt (2 tiles), W3 (0, kt), (1, kt): 16 pieces, as one
-    // loop with the same count on every wave (exact vmcnt bookkeeping for 4- and 8-wave workgroups)
+    // loop with the same count on every wave (exact vmcnt bookkeeping)
 #pragma unroll
-    for (int r = 0; r < 16 / DEC_NW; ++r) {
-      const int i = wv + r * DEC_NW, j = i >> 2;
+    for (int r = 0; r < 16 / NW1; ++r) {
+      const int i = wv + r * NW1, j = i >> 2;
       const int src = (j < 2 ? F_W2 + (kt * 2 + j) * T : F_W3 + ((j - 2) * 8 + kt) * T) + (i & 3) * 256;
       dec_dma(rm, dst + j * T + (i & 3) * 256, lane, src * 4);
     }
   };
-  dec_barrier();
+  lds_dma_barrier();
   const Bias32 fb1[2] = {bias_ld(mlp + F_B1, hf), bias_ld(mlp + F_B1 + 32, hf)};   // before the DMA
   __builtin_amdgcn_sched_barrier(0);
   seg_feat23(B1, 0);
@@ -488,25 +466,21 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
   // the streamed steps (kt = 7 peeled: its DMA differs, and the loop's steps must all issue the same
   // number of DMA pieces for the compiler's vmcnt bookkeeping to stay exact across the back edge)
   auto feat_step = [&](int kt, bool last) {
-    dec_barrier();
+    lds_dma_barrier();
     // this step's bias is loaded before the next segment's DMA is issued, so waiting for it does not
     // wait for the DMA (vmcnt counts in issue order)
     const Bias32 b2 = bias_ld(mlp + F_B2 + kt * 32, hf);
     __builtin_amdgcn_sched_barrier(0);
     float* cur = (kt & 1) ? B0 : B1;
     float* nxt = (kt & 1) ? B1 : B0;
-    auto dma_next = [&]() {
-      if (!last) seg_feat23(nxt, kt + 1);
-      else {   // prefetch flow layer 0 (4 tiles) + layer 1 (4 tiles; OCC3: its first output tile)
-        dma_tiles<DEC_NW>(nxt, rm, L_W0, 4, wv, lane);
-        if (!OCC4) dma_tiles<DEC_NW>(nxt + 4 * T, rm, L_W1, OCC3 ? 2 : 4, wv, lane);
-      }
-    };
-    if (!DEC_DMA_LATE) dma_next();
+    if (!last) seg_feat23(nxt, kt + 1);
+    else {   // prefetch flow layer 0 (4 tiles) + layer 1 (4 tiles; OCC3: its first output tile)
+      dma_tiles<NW1>(nxt, rm, L_W0, 4, wv, lane);
+      if (!OCC4) dma_tiles<NW1>(nxt + 4 * T, rm, L_W1, OCC3 ? 2 : 4, wv, lane);
+    }
     f32x16 acc = f32x16{0};
     tile_mma<F16>(acc, cur, x1s[0], lane);
     tile_mma<F16>(acc, cur + T, x1s[1], lane);
-    if (DEC_DMA_LATE) dma_next();
     const XT<F16> h2 = xop<F16>(bias_sin<F16>(acc, b2));
     tile_mma<F16>(hr[0], cur + 2 * T, h2, lane);
     tile_mma<F16>(hr[1], cur + 3 * T, h2, lane);
@@ -570,17 +544,17 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
     }
   }
   // flow layers 0/1 live in B1 (prefetched during the last feat segment, or at the start)
-  dec_barrier();
+  lds_dma_barrier();
   const Bias32 lb1[2] = {bias_ld(mlp + L_B1, hf), bias_ld(mlp + L_B1 + 32, hf)};   // before the DMA
   __builtin_amdgcn_sched_barrier(0);
   auto seg_flow23 = [&](float* dst, int kt) {   // W2 rows kt (2 tiles); W3 is resident (W3V)
-    dma_tiles<DEC_NW>(dst, rm, L_W2 + kt * 2 * T, 2, wv, lane);
+    dma_tiles<NW1>(dst, rm, L_W2 + kt * 2 * T, 2, wv, lane);
   };
   // OCC3: layer 1's second output tile (2 tiles) into B0, segment 0 after it
   constexpr bool L1B0 = OCC3 && !OCC4 && MODE == 0;
-  if (OCC4) dma_tiles<DEC_NW>(B0, rm, L_W1, 4, wv, lane);   // all of layer 1 into B0; segment 0 later
+  if (OCC4) dma_tiles<NW1>(B0, rm, L_W1, 4, wv, lane);   // all of layer 1 into B0; segment 0 later
   else {
-    if (L1B0) dma_tiles<DEC_NW>(B0, rm, L_W1 + 2 * T, 2, wv, lane);
+    if (L1B0) dma_tiles<NW1>(B0, rm, L_W1 + 2 * T, 2, wv, lane);
     seg_flow23(B0 + (L1B0 ? 2 * T : 0), 0);
   }
   {
@@ -593,7 +567,7 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
       for (int r = 0; r < 16; ++r) z[ot][r] = siren_sin<F16>(z[ot][r] * ACC_S<F16>);
     }
   }
-  if (L1B0 || OCC4) dec_barrier();   // layer 1 (OCC3: its second output tile) landed in B0
+  if (L1B0 || OCC4) lds_dma_barrier();   // layer 1 (OCC3: its second output tile) landed in B0
   if (OCC4) seg_flow23(B1, 0);             // every wave is done with layer 0's B1
   {
     const XT<F16> zs[2] = {xop<F16>(z[0]), xop<F16>(z[1])};
@@ -609,17 +583,16 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
   const XT<F16> x1f[2] = {xop<F16>(x1[0]), xop<F16>(x1[1])};
   float fl[4] = {0.f, 0.f, 0.f, 0.f};
   auto flow_step = [&](int kt, bool last) {   // kt = 7 peeled (see feat_step)
-    dec_barrier();
+    lds_dma_barrier();
     const Bias32 b2 = bias_ld(mlp + L_B2 + kt * 32, hf);   // before the DMA (see feat_step)
     __builtin_amdgcn_sched_barrier(0);
     // OCC4: segment 0 sits in B1, so the buffers alternate the other way round
     float* cur = OCC4 ? ((kt & 1) ? B0 : B1) : (kt & 1) ? B1 : (L1B0 && kt == 0 ? B0 + 2 * T : B0);
     float* nxt = OCC4 ? ((kt & 1) ? B1 : B0) : (kt & 1) ? B0 : B1;
-    if (!last && !DEC_DMA_LATE) seg_flow23(nxt, kt + 1);
+    if (!last) seg_flow23(nxt, kt + 1);
     f32x16 acc = f32x16{0};
     tile_mma<F16>(acc, cur, x1f[0], lane);
     tile_mma<F16>(acc, cur + T, x1f[1], lane);
-    if (!last && DEC_DMA_LATE) seg_flow23(nxt, kt + 1);
     const f32x16 h2 = bias_sin<F16>(acc, b2);
     narrow_dot<4>(fl, W3V, kt, h2, hf);   // flow_imnet.net.3 (256 -> 4, linear)
   };
@@ -634,205 +607,6 @@ __global__ __launch_bounds__((NW1<MODE, HRIMG> * 64)) __attribute__((amdgpu_wave
 #pragma unroll
     for (int e = 0; e < 4; ++e) s[e] = fl[e] + bb[e];
     st4(flow + (size_t)pc * 4, s);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Stage 1 with resident weights (DEC1_RES, split-fp16, LR-image inputs; measured, not the default): the streamed
-// k_dec1 has every 128-pixel workgroup stream all 244 KB of its weights through LDS behind per-segment barriers.
-// Here the stage runs as two persistent kernels, one 16-wave workgroup per CU, that load their network's weights
-// into LDS once and then walk 32-pixel blocks with no barrier and no stream:
-//   k_dec1f: feat_imnet (W1 | W2 | W3 = 36 tiles, 144 KB) -> HRfeat (64 per HR pixel, stored);
-//   k_dec1l: flow_imnet (W0 | W1 | W2 = 24 tiles + the plain [4][256] W3, 100 KB), its HRfeat operand read back
-//            from HBM (256 B per HR pixel) -> flow.
-// Same arithmetic, same order as k_dec1<0, false, 1> (bit-identical outputs), but 372 + 430 us vs 655 us at C0
-// (profiles/r06_dec_res.log): without stream and barriers k_dec1f runs at 0.37 and k_dec1l at 0.21 of their MFMA
-// time, so neither was what bounds stage 1.
-constexpr int RW = 16;   // waves per resident workgroup
-__global__ __launch_bounds__(RW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec1f(
-    const float* __restrict__ proj, const float* __restrict__ mlp, stif_dec_tables tb, const float* __restrict__ tq,
-    float* __restrict__ hrfeat, int n, int h, int w, int HH, int WW) {
-  __shared__ __attribute__((aligned(16))) float wr[36 * T];   // W1 (ot * 2 + kt) | W2 (kt * 2 + j) | W3 (ot * 8 + kt)
-  const int lane = threadIdx.x & 63, hf = lane >> 5;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const __amdgpu_buffer_rsrc_t rm = mlp_rsrc(mlp);
-  dma_tiles<RW>(wr, rm, F_W1, 4, wv, lane);
-  dma_tiles<RW>(wr + 4 * T, rm, F_W2, 16, wv, lane);
-  dma_tiles<RW>(wr + 20 * T, rm, F_W3, 16, wv, lane);
-  lds_dma_barrier();
-  const long long total = (long long)n * HH * WW;
-  const long long nblk = (total + 31) / 32;
-  for (long long blk = (long long)blockIdx.x * RW + wv; blk < nblk; blk += (long long)gridDim.x * RW) {
-    // the weights in LDS are loop-invariant to the compiler, which would hoist their reads out of the block loop
-    // (and spill them): a memory clobber per block keeps every read next to its MFMAs
-    asm volatile("" ::: "memory");
-    const long long p = blk * 32 + (lane & 31);
-    const bool valid = p < total;
-    const long long pc = valid ? p : total - 1;
-    const int item = (int)(pc / ((long long)HH * WW));
-    const int rem = (int)(pc - (long long)item * HH * WW);
-    const int py = rem / WW, px = rem - py * WW;
-    const float t = tq[item];
-    const float* P = proj + (size_t)item * h * w * PROJ_C;
-    // layer 0: z = P1[nearest] + w_rel . rel + w_t * t (bias folded into P1)
-    f32x16 x0[2];
-    {
-      const float ry = tb.rel_y[py], rx = tb.rel_x[px];
-      const float* p1 = P + ((size_t)tb.near_y[py] * w + tb.near_x[px]) * PROJ_C;
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int f = ot * 32 + 8 * v + 4 * hf;
-          const f32x4 z = ld4(p1 + f) + ld4(mlp + F_WRY + f) * ry + ld4(mlp + F_WRX + f) * rx + ld4(mlp + F_WT + f) * t;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) x0[ot][4 * v + e] = siren_sin<1>(z[e]);
-        }
-    }
-    // layer 1: 64 -> 64
-    f32x16 x1[2];
-    {
-      const Bias32 fb1[2] = {bias_ld(mlp + F_B1, hf), bias_ld(mlp + F_B1 + 32, hf)};
-      const XT<1> xs[2] = {xop<1>(x0[0]), xop<1>(x0[1])};
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot) {
-        f32x16 acc = f32x16{0};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) tile_mma<1>(acc, wr + (ot * 2 + kt) * T, xs[kt], lane);
-        x1[ot] = bias_sin<1>(acc, fb1[ot]);
-      }
-    }
-    // layer 2 (64 -> 256, sine) tile by tile into layer 3 (256 -> 64, linear)
-    const XT<1> x1s[2] = {xop<1>(x1[0]), xop<1>(x1[1])};
-    f32x16 hr[2] = {f32x16{0}, f32x16{0}};
-#pragma unroll 1
-    for (int kt = 0; kt < 8; ++kt) {
-      const Bias32 b2 = bias_ld(mlp + F_B2 + kt * 32, hf);
-      f32x16 acc = f32x16{0};
-      tile_mma<1>(acc, wr + (4 + kt * 2) * T, x1s[0], lane);
-      tile_mma<1>(acc, wr + (5 + kt * 2) * T, x1s[1], lane);
-      const XT<1> h2 = xop<1>(bias_sin<1>(acc, b2));
-      tile_mma<1>(hr[0], wr + (20 + kt) * T, h2, lane);
-      tile_mma<1>(hr[1], wr + (28 + kt) * T, h2, lane);
-    }
-#pragma unroll
-    for (int ot = 0; ot < 2; ++ot) hr[ot] = bias_add<1>(hr[ot], mlp + F_B3 + ot * 32, hf);
-    if (valid) {
-      float* o = hrfeat + (size_t)pc * 64;
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          f32x4 s4;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s4[e] = hr[ot][4 * v + e];
-          st4(o + ot * 32 + 8 * v + 4 * hf, s4);
-        }
-    }
-  }
-}
-
-__global__ __launch_bounds__(RW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec1l(
-    const float* __restrict__ proj, const float* __restrict__ mlp, stif_dec_tables tb, const float* __restrict__ tq,
-    const float* __restrict__ hrfeat, float* __restrict__ flow, int n, int h, int w, int HH, int WW) {
-  __shared__ __attribute__((aligned(16))) float wr[25 * T];   // W0 (ot * 2 + kt) | W1 | W2 (kt * 2 + j) | W3 [4][256]
-  const int lane = threadIdx.x & 63, hf = lane >> 5;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const __amdgpu_buffer_rsrc_t rm = mlp_rsrc(mlp);
-  dma_tiles<RW>(wr, rm, L_W0, 4, wv, lane);
-  dma_tiles<RW>(wr + 4 * T, rm, L_W1, 4, wv, lane);
-  dma_tiles<RW>(wr + 8 * T, rm, L_W2, 16, wv, lane);
-  dma_tiles<RW>(wr + 24 * T, rm, L_W3V, 1, wv, lane);
-  lds_dma_barrier();
-  const float* const W3V = wr + 24 * T;
-  const long long total = (long long)n * HH * WW;
-  const long long nblk = (total + 31) / 32;
-  for (long long blk = (long long)blockIdx.x * RW + wv; blk < nblk; blk += (long long)gridDim.x * RW) {
-    // the weights in LDS are loop-invariant to the compiler, which would hoist their reads out of the block loop
-    // (and spill them): a memory clobber per block keeps every read next to its MFMAs
-    asm volatile("" ::: "memory");
-    const long long p = blk * 32 + (lane & 31);
-    const bool valid = p < total;
-    const long long pc = valid ? p : total - 1;
-    const int item = (int)(pc / ((long long)HH * WW));
-    const int rem = (int)(pc - (long long)item * HH * WW);
-    const int py = rem / WW, px = rem - py * WW;
-    const float t = tq[item];
-    const float* P = proj + (size_t)item * h * w * PROJ_C;
-    // the pixel's own HRfeat (k_dec1f's output), in the register-tile order
-    f32x16 hr[2];
-    {
-      const float* hp = hrfeat + (size_t)pc * 64 + 4 * hf;
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const f32x4 q = ld4(hp + ot * 32 + 8 * v);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) hr[ot][4 * v + e] = q[e];
-        }
-    }
-    // layer 0: W[:, :64] . HRfeat + bilinear(P2 at the HR centre) + w_t * t + b
-    f32x16 z[2];
-    {
-      Bilin b;
-      const int y0 = tb.by0[py], y1 = tb.by1[py], x0_ = tb.bx0[px], x1_ = tb.bx1[px];
-      const float wy0 = tb.wy0[py], wy1 = tb.wy1[py], wx0 = tb.wx0[px], wx1 = tb.wx1[px];
-      b.o00 = y0 * w + x0_; b.o01 = y0 * w + x1_; b.o10 = y1 * w + x0_; b.o11 = y1 * w + x1_;
-      b.w00 = wx0 * wy0; b.w01 = wx1 * wy0; b.w10 = wx0 * wy1; b.w11 = wx1 * wy1;
-      gather64_q(z, P, PROJ_C, 64, b, hf);
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int f = ot * 32 + 8 * v + 4 * hf;
-          const f32x4 wt = ld4(mlp + L_WT + f), bb = ld4(mlp + L_B0 + f);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) z[ot][4 * v + e] = (z[ot][4 * v + e] + (wt[e] * t + bb[e])) * ACC_IN<1>;
-        }
-    }
-    {
-      const XT<1> hs[2] = {xop<1>(hr[0]), xop<1>(hr[1])};
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot) {
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) tile_mma<1>(z[ot], wr + (ot * 2 + kt) * T, hs[kt], lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) z[ot][r] = siren_sin<1>(z[ot][r] * ACC_S<1>);
-      }
-    }
-    f32x16 x1[2];
-    {
-      const Bias32 lb1[2] = {bias_ld(mlp + L_B1, hf), bias_ld(mlp + L_B1 + 32, hf)};
-      const XT<1> zs[2] = {xop<1>(z[0]), xop<1>(z[1])};
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot) {
-        f32x16 acc = f32x16{0};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) tile_mma<1>(acc, wr + (4 + ot * 2 + kt) * T, zs[kt], lane);
-        x1[ot] = bias_sin<1>(acc, lb1[ot]);
-      }
-    }
-    const XT<1> x1f[2] = {xop<1>(x1[0]), xop<1>(x1[1])};
-    float fl[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int kt = 0; kt < 8; ++kt) {
-      const Bias32 b2 = bias_ld(mlp + L_B2 + kt * 32, hf);
-      f32x16 acc = f32x16{0};
-      tile_mma<1>(acc, wr + (8 + kt * 2) * T, x1f[0], lane);
-      tile_mma<1>(acc, wr + (9 + kt * 2) * T, x1f[1], lane);
-      const f32x16 h2 = bias_sin<1>(acc, b2);
-      narrow_dot<4>(fl, W3V, kt, h2, hf);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) fl[c] += __shfl_xor(fl[c], 32);
-    if (valid && hf == 0) {
-      const f32x4 bb = ld4(mlp + L_B3);
-      f32x4 s4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s4[e] = fl[e] + bb[e];
-      st4(flow + (size_t)pc * 4, s4);
-    }
   }
 }
 
@@ -898,7 +672,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
     }
     asm volatile("" ::: "memory");
     gather64(q, HRF, 64, 0, bilin_hr<WIN>(g1x, g1y, WW, HH, win, status), hf);   // q_feat1 -> W0 columns 0..63
-    dec_barrier();
+    lds_dma_barrier();
     dma_tiles<DEC2_NW>(B1, rm, E_W1, 4, wv, lane);
     {
       const XT<F16> qs[2] = {xop<F16>(q[0]), xop<F16>(q[1])};
@@ -918,7 +692,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
       for (int r = 0; r < 16; ++r) x0[ot][r] = siren_sin<F16>(z[ot][r] * ACC_S<F16>);
     }
   }
-  dec_barrier();
+  lds_dma_barrier();
   const Bias32 eb1[2] = {bias_ld(mlp + E_B1, hf), bias_ld(mlp + E_B1 + 32, hf)};   // before the DMA
   __builtin_amdgcn_sched_barrier(0);
   auto seg_l23_first = [&](float* dst) {
@@ -950,7 +724,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
 #pragma unroll
   for (int ot = 0; ot < 8; ++ot) a3[ot] = f32x16{0};
   auto l23_step = [&](int kt, bool last) {   // kt = 7 peeled (see k_dec1's feat_step)
-    dec_barrier();
+    lds_dma_barrier();
     const Bias32 b2 = bias_ld(mlp + E_B2 + kt * 32, hf);   // before the DMA (see k_dec1)
     __builtin_amdgcn_sched_barrier(0);
     float* cur = (kt & 1) ? B1 : B0;
@@ -969,7 +743,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   l23_step(7, true);
   // layer 3 sine streamed into layer 4 (256 -> 3, linear, VALU dot products); W4 sits in B0 as
   // plain rows, followed by the layer-3 biases (E_W4V_B3; kt = 7 prefetch)
-  dec_barrier();
+  lds_dma_barrier();
   float o4[3] = {0.f, 0.f, 0.f};
 #pragma unroll
   for (int kt = 0; kt < 8; ++kt) {
@@ -1004,20 +778,13 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
 // registers between layers as in k_dec2.  The layer-3 state halves (8 tiles x 8 floats = 64 VGPRs): 128 VGPRs,
 // four waves per SIMD.
 // Weight streaming (round 6): every workgroup streams the whole 372-KB weight set through its LDS, so the
-// stream is paid once per workgroup; its memory traffic costs ~10 % of the kernel (pieces issued out of range,
-// DEC_EXP 3: profiles/r06_dec_probe3.log).  Workgroups are
-// DEC2Q_NW waves (8: 128 pixels, two per CU; 16: 256 pixels, one per CU) and a segment is the layer-2 / -3
-// weights of DEC2Q_KTS whole layer-2 tiles kt (W2 rows kt + W3 column kt: 10 tiles each), double-buffered in
-// 2 x 40 KB (KTS 1) or 2 x 80 KB (KTS 2): the weight bytes per pixel halve / quarter and one barrier per kt
-// (or per two) replaces two.  Every wave issues the same number of LDS-DMA pieces per segment (5), so the
-// compiler's vmcnt bookkeeping stays exact.
+// stream is paid once per workgroup; its memory traffic costs ~10 % of the kernel (profiles/r06_dec_probe3.log).
+// Workgroups are DEC2Q_NW waves (8: 128 pixels, two per CU; 16: 256 pixels, one per CU, 27 % slower) and a segment
+// is the layer-2 / -3 weights of DEC2Q_KTS whole layer-2 tiles kt (W2 rows kt + W3 column kt: 10 tiles each),
+// double-buffered in 2 x 40 KB (KTS 1) or 2 x 80 KB (KTS 2): one barrier per kt (or per two).  Every wave issues
+// the same number of LDS-DMA pieces per segment (5), so the compiler's vmcnt bookkeeping stays exact.
 // Gathers: each lane fetches its own quarter of a 64-channel block (16 corner loads in flight).
 constexpr int DEC2Q_NWV = DEC2Q_NW;
-#if DEC_TRACE
-// diagnostic (stif_dec_trace_set): per k_dec2q wave 8 u32 -- life, gathers (incl. the flow load), segment-barrier
-// waits, layer-2/3 span (its barriers included) -- s_memtime ticks
-__device__ unsigned* g_dtrace;
-#endif
 constexpr int KTS = DEC2Q_KTS;            // layer-2 tiles per segment
 constexpr int SEGQ = 10 * KTS;            // tiles per segment
 static_assert(40 * KTS % DEC2Q_NWV == 0 && 32 % DEC2Q_NWV == 0 && 16 % DEC2Q_NWV == 0 && 8 % KTS == 0,
@@ -1092,15 +859,6 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
     const float* __restrict__ flow, stif_dec_tables tb, const float* __restrict__ tq, float* __restrict__ out, int n,
     int h, int w, int HH, int WW, int* status, stif_dec_window win) {
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEGQ * T];
-#if DEC_TRACE
-  const unsigned tr0 = (unsigned)__builtin_amdgcn_s_memtime();
-  unsigned tr_g = 0, tr_b = 0, tr_l23 = 0, tr_x;
-#define DTR_BEGIN() tr_x = (unsigned)__builtin_amdgcn_s_memtime()
-#define DTR_END(acc) acc += (unsigned)__builtin_amdgcn_s_memtime() - tr_x
-#else
-#define DTR_BEGIN()
-#define DTR_END(acc)
-#endif
   const int lane = threadIdx.x & 63, q = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   constexpr int NW = DEC2Q_NWV;
@@ -1132,7 +890,6 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
   const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
 
   // warpgrid (warplayer.py:25-39) and the decoder's clamp (Sakuya_arch_test.py:428,441), as k_dec2
-  DTR_BEGIN();
   const f32x4 fv = ld4(flow + (size_t)pc * 4);
   const float bx = tb.lin_x[WIN ? win.x0 + px : px], by = tb.lin_y[WIN ? win.y0 + py : py];
   const WarpGrids wg = warp_grids(fv, bx, by, WW, HH);
@@ -1157,10 +914,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
       }
     asm volatile("" ::: "memory");
     gather_q(g, HRF, 64, 0, bilin_hr<WIN>(g1x, g1y, WW, HH, win, status), q);   // q_feat1 -> W0 columns 0..63
-    DTR_END(tr_g);
-    DTR_BEGIN();
-    dec_barrier();                                      // layer 0 landed in B0
-    DTR_END(tr_b);
+    lds_dma_barrier();                                      // layer 0 landed in B0
     dma_tiles<NW>(B1, rm, Q_W1, 4, wv, lane);
     {
       const XQ qs[2] = {xq(g[0]), xq(g[1])};
@@ -1170,9 +924,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
         for (int kt = 0; kt < 2; ++kt) tile_q(z[ot], B0 + (ot * 4 + kt) * T, qs[kt], lane);
     }
     asm volatile("" ::: "memory");
-    DTR_BEGIN();
     gather_q(g, HRF, 64, 0, bilin_hr<WIN>(g2x, g2y, WW, HH, win, status), q);   // q_feat2 -> W0 columns 64..127
-    DTR_END(tr_g);
     const XQ qs[2] = {xq(g[0]), xq(g[1])};
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot) {
@@ -1184,9 +936,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
         for (int e = 0; e < 4; ++e) x0[ot].s[s][e] = siren_sin<1>(z[ot].s[s][e] * ACC_S<1>);
     }
   }
-  DTR_BEGIN();
-  dec_barrier();   // layer 1 landed in B1; every wave is done with layer 0's B0
-  DTR_END(tr_b);
+  lds_dma_barrier();   // layer 1 landed in B1; every wave is done with layer 0's B0
   // layer-1 biases before the next segment's LDS-DMA: vmcnt counts in issue order, so a bias load issued
   // after the DMA would wait for the DMA too (as k_dec1 / k_dec2 do)
   const R32 eb1[2] = {bias_q(mlp + E_B1, q), bias_q(mlp + E_B1 + 32, q)};
@@ -1211,9 +961,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
   for (int ot = 0; ot < 8; ++ot) a3[ot].s[0] = a3[ot].s[1] = f32x4{0.f, 0.f, 0.f, 0.f};
   constexpr int NSEG = 8 / KTS;
   auto l23_step = [&](int sg, bool last) {
-    DTR_BEGIN();
-    dec_barrier();   // segment sg landed; every wave is done with the other buffer
-    DTR_END(tr_b);
+    lds_dma_barrier();   // segment sg landed; every wave is done with the other buffer
     R32 b2[KTS];
 #pragma unroll
     for (int k = 0; k < KTS; ++k) b2[k] = bias_q(mlp + E_B2 + (sg * KTS + k) * 32, q);   // before the DMA
@@ -1224,7 +972,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
       if (!last) seg_l23(nxt, sg + 1);
       else dma_tiles<NW>(nxt, rm, E_W4V, 1, wv, lane);
     };
-    if (!DEC_DMA_LATE) dma_next();
+    dma_next();
 #pragma unroll
     for (int k = 0; k < KTS; ++k) {
       const float* sk = cur + k * 10 * T;
@@ -1232,24 +980,17 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
       acc.s[0] = acc.s[1] = f32x4{0.f, 0.f, 0.f, 0.f};
       tile_q(acc, sk, x1s[0], lane);
       tile_q(acc, sk + T, x1s[1], lane);
-      if (DEC_DMA_LATE && k == 0) dma_next();
       const XQ h2 = xq(bias_sin_q(acc, b2[k]));
 #pragma unroll
       for (int ot = 0; ot < 8; ++ot) tile_q(a3[ot], sk + (2 + ot) * T, h2, lane);
     }
   };
-#if DEC_TRACE
-  const unsigned tr_l0 = (unsigned)__builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll 1
   for (int sg = 0; sg < NSEG - 1; ++sg) l23_step(sg, false);
   l23_step(NSEG - 1, true);
-#if DEC_TRACE
-  tr_l23 = (unsigned)__builtin_amdgcn_s_memtime() - tr_l0;
-#endif
   // layer 3 sine streamed into layer 4 (256 -> 3, VALU dot products over this lane's 64 features); W4 rows
   // and the layer-3 biases in the buffer the last segment did not use (k_dec2's tile)
-  dec_barrier();
+  lds_dma_barrier();
   float* const B4 = ((NSEG - 1) & 1) ? B0 : B1;
   float o4[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -1282,18 +1023,8 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
     }
     report_range_w<WIN>(status, bad);
   }
-#if DEC_TRACE
-  if (g_dtrace && lane == 0) {
-    typedef unsigned u32x4t __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<u32x4t*>(g_dtrace + ((size_t)blockIdx.x * NW + wv) * 8) =
-        u32x4t{(unsigned)__builtin_amdgcn_s_memtime() - tr0, tr_g, tr_b, tr_l23};
-  }
-#endif
-#undef DTR_BEGIN
-#undef DTR_END
 }
 
-#if DEC_WINDOWS
 // k_dec_bounds: the box (rows ymin..ymax, columns xmin..xmax of the virtual grid, inclusive) of every HRfeat corner
 // stage 2 reads for win's query rectangle given its flow -- warp_grids + bilin_corners, the expressions of stage 2
 // itself on the same operands, so the box is exact; corners of weight 0 count (stage 2 loads them).  One box for
@@ -1330,7 +1061,6 @@ __global__ __launch_bounds__(256) void k_dec_bounds(const float* __restrict__ fl
     atomicMax(box + 3, xmax);
   }
 }
-#endif
 
 __global__ __launch_bounds__(256) void k_pack_lr(const float* __restrict__ f0, const float* __restrict__ f1,
                                                  const float* __restrict__ f2, const float* __restrict__ x,
@@ -1400,13 +1130,12 @@ template <int MODE, bool HRIMG>
 void launch_dec1(bool f16, long long total, hipStream_t st, const float* proj, const float* mlp,
                  const stif_dec_tables& tb, const stif_dec_image& im, const float* t, float* hrfeat, float* flow, int n,
                  int h, int w, int HH, int WW) {
-  constexpr int nw = NW1<MODE, HRIMG>;
-  const long long blocks = (total + nw * 32 - 1) / (nw * 32);
+  const long long blocks = (total + NW1 * 32 - 1) / (NW1 * 32);
   if (f16)
-    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1, false>), dim3((unsigned)blocks), dim3(nw * 64), 0, st, proj, mlp, tb, im,
+    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1, false>), dim3((unsigned)blocks), dim3(NW1 * 64), 0, st, proj, mlp, tb, im,
                        t, hrfeat, flow, n, h, w, HH, WW, stif_dec_window{});
   else
-    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0, false>), dim3((unsigned)blocks), dim3(nw * 64), 0, st, proj, mlp, tb, im,
+    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0, false>), dim3((unsigned)blocks), dim3(NW1 * 64), 0, st, proj, mlp, tb, im,
                        t, hrfeat, flow, n, h, w, HH, WW, stif_dec_window{});
 }
 
@@ -1429,11 +1158,6 @@ extern "C" int stif_dec_stage1_ex(const float* proj, const float* mlp, const sti
     else launch_dec1<2, false>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
   } else if (img) {
     launch_dec1<0, true>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
-  } else if (DEC1_RES && f16) {   // resident-weight feat and flow kernels (persistent, one workgroup per CU)
-    const long long nblk = (total + 31) / 32;
-    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(stif_num_cus(), (nblk + RW - 1) / RW));
-    hipLaunchKernelGGL(k_dec1f, dim3(grid), dim3(RW * 64), 0, st, proj, mlp, *tab, t, hrfeat, n, h, w, HH, WW);
-    hipLaunchKernelGGL(k_dec1l, dim3(grid), dim3(RW * 64), 0, st, proj, mlp, *tab, t, hrfeat, flow, n, h, w, HH, WW);
   } else {
     launch_dec1<0, false>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
   }
@@ -1514,18 +1238,15 @@ int window_fail(const char* entry, const char* why) {
   return stif_fail(STIF_E_INVALID, msg);
 }
 
-#if DEC_WINDOWS
 template <int MODE, bool HRIMG>
 void launch_dec1w(bool f16, hipStream_t st, const float* proj, const float* mlp, const stif_dec_tables& tb,
                   const stif_dec_image& im, const float* t, float* hrfeat, float* flow, int n, int h, int w, int HH,
                   int WW, const stif_dec_window& wn) {
-  constexpr int nw = NW1<MODE, HRIMG>;
   const long long total = (long long)n * wn.hh * wn.ww;
-  const dim3 g((unsigned)((total + nw * 32 - 1) / (nw * 32))), b(nw * 64);
+  const dim3 g((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32))), b(NW1 * 64);
   if (f16) hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1, true>), g, b, 0, st, proj, mlp, tb, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
   else hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0, true>), g, b, 0, st, proj, mlp, tb, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
 }
-#endif
 
 }  // namespace
 
@@ -1542,7 +1263,6 @@ extern "C" int stif_dec_stage1_win(const float* proj, const float* mlp, const st
   if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
   // every pixel of the query rectangle stores its HRfeat row into the F layout
   if (!f_holds_query(wn)) return window_fail(me, "the F rectangle does not contain the query rectangle");
-#if DEC_WINDOWS
   const bool f16 = flags & STIF_CONV_F16X3;
   hipStream_t st = (hipStream_t)stream;
   const stif_dec_image im = img ? *img : stif_dec_image{};
@@ -1555,9 +1275,6 @@ extern "C" int stif_dec_stage1_win(const float* proj, const float* mlp, const st
     launch_dec1w<0, false>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
   }
   return stif_check_launch(me);
-#else
-  return window_fail(me, "not built into the probe / trace variants of the library");
-#endif
 }
 
 extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int n, int HH, int WW,
@@ -1566,16 +1283,12 @@ extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, in
   if (!flow || !tables_ok(tab) || !box || n < 1) return window_fail(me, "bad arguments (null pointer or n < 1)");
   stif_dec_window wn;
   if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
-#if DEC_WINDOWS
   const long long total = (long long)n * wn.hh * wn.ww;
   const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_dec_bounds_init, dim3(1), dim3(64), 0, st, box);
   hipLaunchKernelGGL(k_dec_bounds, dim3(blocks), dim3(256), 0, st, flow, *tab, box, total, HH, WW, wn);
   return stif_check_launch(me);
-#else
-  return window_fail(me, "not built into the probe / trace variants of the library");
-#endif
 }
 
 extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
@@ -1587,7 +1300,6 @@ extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const fl
     return window_fail(me, "bad arguments (null pointer or empty shape)");
   stif_dec_window wn;
   if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
-#if DEC_WINDOWS
   const bool f16 = flags & STIF_CONV_F16X3;
   const long long total = (long long)n * wn.hh * wn.ww;
   const stif_dec_image im = img ? *img : stif_dec_image{};
@@ -1604,16 +1316,7 @@ extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const fl
   else if (f16) hipLaunchKernelGGL((k_dec2<false, 1, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
   else hipLaunchKernelGGL((k_dec2<false, 0, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
   return stif_check_launch(me);
-#else
-  return window_fail(me, "not built into the probe / trace variants of the library");
-#endif
 }
-
-#if DEC_TRACE
-extern "C" int stif_dec_trace_set(unsigned* p) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_dtrace), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int stif_dec_blend4(const float* const* pred, const float* const* wgt, float* out, int n, int HH, int WW,
                                void* stream) {

@@ -77,7 +77,7 @@ STIF_DEV void stage_image(__amdgpu_buffer_rsrc_t rs, float* dst, int iy0, int ix
     const unsigned off = __umul24((unsigned)(y * W + x), cs4) + cb;
     // select, not branch: every lane's offset is computed, out-of-range ones replaced
     const unsigned voff = (((unsigned)y < (unsigned)H) & ((unsigned)x < (unsigned)W)) ? off : 0x80000000u;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + (r * OM_RP + 63 * m) * 4, 16, voff, 0, 0, WINO_NT);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + (r * OM_RP + 63 * m) * 4, 16, voff, 0, 0, 0);
   }
 }
 
@@ -103,11 +103,6 @@ struct Tile {
 // Wave i = transform row i for both 32-cout halves (2 waves per SIMD, ~250 VGPRs).
 // dynamic schedule: the value each XCD counter holds before the launch (the host keeps the counters'
 // running totals, so nothing resets them at the end of a launch)
-#if WINO_TRACE
-// diagnostic (stif_wino_trace_set): per wave of the RELU-epilogue f16x3 k_wino (the ResidualBlock conv1) 4 u32 --
-// life, phase-end waits (vmcnt + barrier), epilogue (output-transform exchange + stores), tiles -- s_memtime ticks
-__device__ unsigned* g_wtrace;
-#endif
 struct SchedBase {
   unsigned b[8];
 };
@@ -217,13 +212,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     const int cy0 = (t.oy0 >> 1) - 1, cx0 = (t.ox0 >> 1) - 1;
     const float sc = a.in1_scale;
     const float w3 = 0.75f * sc, w1 = 0.25f * sc;
-    if (WINO_UPQ == 0) {   // per-pixel form (A/B reference)
-      for (int f = tid; f < HR * HC * 8; f += 256) {
-        const int ch = f & 7, pc = f >> 3, r = pc / HC, c = pc - HC * (pc / HC);
-        st4(dst + (r * OM_RP + col_slot(c) * PITCH + ch) * 4, expand_px(t, r, c, ch));
-      }
-      return;
-    }
     for (int f = tid; f < 3 * 17 * 8; f += 256) {
       const int ch = f & 7, q = f >> 3, qr = q / 17, qc = q - 17 * (q / 17);
       const int k = cy0 + qr, m = cx0 + qc;   // coarse rows k, k + 1 and columns m, m + 1
@@ -247,7 +235,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
       }
     }
   };
-  auto up_phase = [&](int p) { return IN1 == 2 && WINO_EXP != 4 && p * PSUB >= NC0; };
+  auto up_phase = [&](int p) { return IN1 == 2 && p * PSUB >= NC0; };
 
   // rows of the 4x4 patch feeding transform row i: (B^T d)_i = d[rA] + sB * d[rB]
   const int rA = (wi == 0) ? 0 : (wi == 2 ? 2 : 1);
@@ -296,10 +284,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   int Tn = T + nl;                                        // the next tile (static for the first two)
   const int dbase = xcd * per + 2 * nl;                   // dynamic tile d = dbase + counter value
   int par = 0;
-#if WINO_TRACE
-  const unsigned tr0 = (unsigned)__builtin_amdgcn_s_memtime();
-  unsigned tr_wait = 0, tr_epi = 0, tr_x = 0, ntile = 0;
-#endif
   if (T < tend) {
   Tile cur = tile_of(T);
   const float* wsl = wbase(cur);
@@ -360,31 +344,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         // the phase's first LDS reads go out before the next phase's LDS-DMA is issued, so the DMA
         // issue (~1K cycles per wave) overlaps their latency instead of preceding it
         xread(buf, 0, rd);
-        if (WINO_EXP != 1) {
-          if (p + 1 < NP) stage(cur, p + 1, (gp + 1) & 1);
-          else if (has_next) stage(nxt, 0, (gp + 1) & 1);
-        }
-        // probe 7 (the fused ResidualBlock's conv1 cost floor): the RELU conv does a third chunk-pair pass per
-        // phase (chunks 0, 1 again) = 1.5x its transform / split / MFMA work, the work of a conv1 over the
-        // 1-px halo of the next conv's tile, and stores nothing (as probe 5)
-        constexpr int SPN = (WINO_EXP == 7 && EPI == STIF_EPI_RELU) ? PSUB / 2 + 1 : PSUB / 2;
+        if (p + 1 < NP) stage(cur, p + 1, (gp + 1) & 1);
+        else if (has_next) stage(nxt, 0, (gp + 1) & 1);
 #pragma unroll
-        for (int sp = 0; sp < SPN; ++sp) {
+        for (int sp = 0; sp < PSUB / 2; ++sp) {
           // chunk pair (2 sp, 2 sp + 1): lane half h holds channels 4h..4h+3 of both, i.e. the 8
           // K values of a 32x32x16 f16 MFMA; transform both, split all four j, then fetch the next
           // pair's first chunk so its LDS reads hide under this pair's MFMAs
           f32x4 va[4], vb[4];
           xform(rd, va);
-          xread(buf, (2 * sp + 1) % PSUB, rd);
+          xread(buf, 2 * sp + 1, rd);
           xform(rd, vb);
-          const int q = p * (PSUB / 2) + sp % (PSUB / 2);
+          const int q = p * (PSUB / 2) + sp;
           const float* wq = wsl + (size_t)q * 16384;
           const float* wq1 = q + 1 < NQ ? wq + 16384 : wnx;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             f16x8 ah, al;
             split_f16x3(va[j], vb[j], ah, al);
-            if (j == XREAD_J && 2 * sp + 2 < 2 * SPN) xread(buf, (2 * sp + 2) % PSUB, rd);
+            if (j == XREAD_J && 2 * sp + 2 < PSUB) xread(buf, 2 * sp + 2, rd);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
               acc[j][u] = mfma16h(ah, bh[j & 1][u], acc[j][u]);
@@ -394,7 +372,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             // refill the slot with block j + 2: (pair q, j + 2) or (pair q + 1, j - 2)
             const float* wn = j < 2 ? wq + (j + 2) * 1024 : wq1 + (j - 2) * 1024;
 #pragma unroll
-            for (int u = 0; u < 2 && WINO_EXP != 2; ++u) {
+            for (int u = 0; u < 2; ++u) {
               bh[j & 1][u] = ldh8(wn + (u * 2) * 256);
               bl[j & 1][u] = ldh8(wn + (u * 2 + 1) * 256);
             }
@@ -403,14 +381,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         }
         // every load older than the last two blocks' B refills (8) -- the phase's LDS-DMA among
         // them -- has landed
-#if WINO_TRACE
-        tr_x = (unsigned)__builtin_amdgcn_s_memtime();
-#endif
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         __syncthreads();
-#if WINO_TRACE
-        tr_wait += (unsigned)__builtin_amdgcn_s_memtime() - tr_x;
-#endif
         publish(p);
         if (IN1 == 2 && p + 1 < NP && up_phase(p + 1)) {
           expand(cur, (gp + 1) & 1);
@@ -464,24 +436,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     // thread combines and stores (pixel, 4-cout) vectors as coalesced 16-B accesses (8 lanes = one
     // pixel's 128 B).  Row swizzle R ^ (bit2(tile) ^ b) keeps both the b32 writes (lane halves 4
     // tiles apart) and the b128 reads (16-lane groups = b 0/1 of one tile) conflict-free.
-#if WINO_TRACE
-    const unsigned tr_e0 = (unsigned)__builtin_amdgcn_s_memtime();
-    ++ntile;
-#endif
     float* ex = smem + ((gp - 1) & 1) * BUF_F;
-    if (WINO_EXP == 3) {
-      f32x16 sm = f32x16{0};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sm += acc[j][0] + acc[j][1];
-      float tot = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tot += sm[r];
-      a.out[cur.g][(size_t)cur.n * a.out_item + ((size_t)(cur.oy0 * a.Wo + cur.ox0) * a.cout) + tid] = tot;
-      __syncthreads();
-      if (!has_next) break;
-      advance();
-      continue;
-    }
     f32x16 yv[2][2];   // [local half][b]
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -567,27 +522,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cn), ro2, voff(nt, k), 0, 0);
           continue;
         }
-        if ((WINO_EXP != 5 && WINO_EXP != 7) || EPI != STIF_EPI_RELU)   // probes 5, 7: the ResidualBlock's conv1 stores nothing
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, y), ro,
-                                                 voff(nt, k), 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, y), ro,
+                                               voff(nt, k), 0, 0);
       }
     }
     if (F16) report_range(a.status, not_finite(chk));   // a non-finite output makes the sum non-finite
     __syncthreads();   // exchange buffer free for the next tile's staging
-#if WINO_TRACE
-    tr_epi += (unsigned)__builtin_amdgcn_s_memtime() - tr_e0;
-#endif
     if (!has_next) break;
     advance();
   }
   }
-#if WINO_TRACE
-  if (g_wtrace && (tid & 63) == 0 && F16 && EPI == STIF_EPI_RELU) {
-    typedef unsigned u32x4t __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<u32x4t*>(g_wtrace + ((size_t)blockIdx.x * 4 + wi) * 4) =
-        u32x4t{(unsigned)__builtin_amdgcn_s_memtime() - tr0, tr_wait, tr_epi, ntile};
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -642,7 +586,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         __builtin_amdgcn_make_buffer_rsrc((void*)src, (short)0, (int)((size_t)H * W * 256), 0x00020000);
     stage_image(rs, smem + buf * BUF_F, t.oy0 - 1, t.ox0 - 1, H, W, 64, p * 32, wi, 4, lpx, lck);
   };
-
 
   // input transform row i (k_wino's xread / xform) -> split A operands of chunk pair q
   const int rA = (wi == 0) ? 0 : (wi == 2 ? 2 : 1);
@@ -736,7 +679,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
       for (int e = 0; e < 4; ++e)
         if (EPI == STIF_EPI_OFFMASK) y[e] = (m3 + e) % 3 == 2 ? sigmoid_fast(y[e]) : y[e];
       const int oy = t.oy0 + k;
-      const bool ok = (oy < a.Ho) & (ox < a.Wo) & cok & (WINO_EXP != 6);   // probe 6: k_wino_om stores nothing
+      const bool ok = (oy < a.Ho) & (ox < a.Wo) & cok;
       const unsigned vo = ok ? (unsigned)(((oy * a.Wo + ox) * a.cout + cob) * 4) : 0x80000000u;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, y), ro,
                                              vo, 0, 0);
@@ -760,9 +703,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         const bool nn = n + 1 < ntn;
         ldb(nn ? wr : wrn, nn ? n + 1 : 0, b + RING - 16, s);
       }
-#if WINO_OM_SCHED
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      __builtin_amdgcn_sched_barrier(0);   // keeps the B loads early
     }
   };
 
@@ -846,7 +787,7 @@ int launch(const stif_conv_args& a, hipStream_t st) {
   if (tiles > 0x7fffffff) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: too many tiles");
   if ((long long)a.H * a.W * std::max(a.C0, std::max(a.C1, a.cout)) * 4 >= 0x7fffffffLL)
     return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: item larger than 2 GB (buffer addressing)");
-  if constexpr (WINO_OM && EPI == STIF_EPI_OFFMASK) if ((a.flags & STIF_CONV_F16X3) && a.C0 == 64 && !a.in1_mode) {
+  if constexpr (EPI == STIF_EPI_OFFMASK) if ((a.flags & STIF_CONV_F16X3) && a.C0 == 64 && !a.in1_mode) {
     const long long sp = tiles / ((a.cout + 63) / 64);   // spatial tiles: all couts per workgroup
     const int g2 = 8 * (int)std::min<long long>((sp + 7) / 8, (long long)WG_PER_CU * stif_num_cus() / 8);
     hipLaunchKernelGGL((k_wino_om<EPI>), dim3(g2), dim3(256), 0, st, a, (int)sp);
@@ -872,12 +813,6 @@ int launch(const stif_conv_args& a, hipStream_t st) {
 }
 
 }  // namespace
-
-#if WINO_TRACE
-extern "C" int stif_wino_trace_set(unsigned* p) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_wtrace), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int stif_conv3x3_wino(const stif_conv_args* pa, void* stream) {
   if (!pa) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: null args");

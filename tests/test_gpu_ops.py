@@ -600,8 +600,9 @@ def test_dcn_sep_fused_reports_range(ops, L, which):
 def test_dcn_sep_fused_launches_deterministic_odd_shapes(ops, L, shape):
     """Round-5 review item 4: launch groups of 2-8 weight sets with odd H / W (partial tiles in both directions,
     several workgroups per CU and so two per CU sharing it) and 1-5 items; every launch re-run three times into
-    fresh NaN buffers reproduces its output bit for bit.  (The tap-pipelined diagnostic variant, DCNSEP_TAPPIPE=1,
-    fails this whenever two workgroups share a CU -- DESIGN.md section 3d.)"""
+    fresh NaN buffers reproduces its output bit for bit.  (The tap-pipelined variant of phase 2, built with packed
+    fp32, failed this whenever two workgroups shared a CU -- DESIGN.md section 3d; the variant was removed from the
+    kernel source, 2e2f059 is the last commit that builds it.)"""
     B, H, W, G = shape
     groups = []
     for i in range(G):
