@@ -380,6 +380,49 @@ int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat
                         const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n, int h,
                         int w, int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win);
 
+/* ---- evaluation: PSNR / SSIM of decoded frames against ground truth (myutils.py:1151-1174, util.py:105-174) ---- */
+
+/* stif_metric_args.flags */
+#define STIF_METRIC_Y 1      /* score the Y channel of bgr2ycbcr (data/util.py:181-202, not rounded); else the three
+                                channels (PSNR over all of them at once, SSIM = mean of the per-channel SSIMs) */
+#define STIF_METRIC_SSIM 2   /* also the SSIM sums (11 x 11 Gaussian, sigma 1.5, windows inside the image only) */
+#define STIF_METRIC_FLOAT 4  /* myutils.calc_psnr (:269-271): squared error of the unquantised floats, data range 1,
+                                against gt_f32; excludes _Y and _SSIM; gt_u8 is ignored */
+
+/* Zero-initialise, then fill.  pred: the engine's output frames, fp32 RGB planes, unclamped; element (item i,
+ * plane c, row y, column x) is pred[i * pred_item + c * pred_plane + y * pred_pitch + x], so the top-left crop of a
+ * padded [n][3][HH][WW] output is scored in place.  pred_item = pred_plane = pred_pitch = 0 means a dense
+ * [n][3][H][W].  gt_u8: cv2-style uint8 BGR HWC frames, byte (i, y, x, c) at gt_u8[i * gt_item + y * gt_pitch +
+ * 3 * x + c]; gt_item = gt_pitch = 0 means dense [n][H][W][3].  gt_f32 (STIF_METRIC_FLOAT): fp32 RGB planes
+ * addressed like pred through gtf_item / gtf_plane / gtf_pitch.
+ * Quantised modes score q = rintf(clamp(pred, 0, 1) * 255.f) (utils.util.tensor2img: fp32, half to even)
+ * against the ground truth's exact integers, in fp64. */
+typedef struct {
+  const float* pred;
+  long long pred_item, pred_plane, pred_pitch;   /* elements */
+  const unsigned char* gt_u8;
+  long long gt_item, gt_pitch;                   /* bytes */
+  const float* gt_f32;
+  long long gtf_item, gtf_plane, gtf_pitch;      /* elements */
+  int n, H, W;
+  int flags;                                     /* STIF_METRIC_* */
+} stif_metric_args;
+
+/* Bytes of workspace stif_metric_psnr_ssim needs (four doubles per 32 x 32 tile of every scored plane); 0 for
+ * sizes < 1 or an invalid flag combination.  Pure host. */
+size_t stif_metric_workspace_size(int n, int H, int W, int flags);
+/* out: device array [n][4] = { sum of squared errors, pixels summed (H W, or 3 H W in RGB / float mode), sum of
+ * the SSIM map, windows summed ((H-10)(W-10) per plane; 0 without STIF_METRIC_SSIM or when H < 11 or W < 11) }
+ * per item; PSNR = 20 log10(255 / sqrt(sse / npix)) (float mode: -10 log10(sse / npix + 1e-8)), SSIM =
+ * ssim_sum / nwin (stif_amd.metrics.finish).  Two launches on `stream`, no host read-back (graph-capturable), no
+ * floating-point atomics: repeated calls give identical bits.  Every argument is validated before the first
+ * launch: STIF_E_INVALID for null pointers, sizes < 1, a pitch below the row length, overlapping planes or items,
+ * bad flags; STIF_E_WORKSPACE for a missing or short workspace. */
+int stif_metric_psnr_ssim(const stif_metric_args* args, double* out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* The normalised 1-D window (cv2.getGaussianKernel(11, 1.5)) as the host computes it for the kernel. */
+int stif_metric_window(double k[11]);
+
 #ifdef __cplusplus
 }
 #endif

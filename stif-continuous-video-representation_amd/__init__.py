@@ -9,6 +9,7 @@ Layout:
   coords.py   fp32 query-grid tables of the decoder
   weights.py  state-dict spec + deterministic weight generator
   video.py    custom_video_test-style sliding-window driver
+  metrics.py  on-device PSNR / SSIM of decoded frames against ground truth (the reference's evaluation loop)
 (integration/_ext.py at the repo root is the DCNv2 `_ext` shim over ops.dcn_v2_forward)
   parallel.py frame-pair sharding over ranks
   serving.py  option files, define_G / load_network / VideoSRModel (checkpoint drop-in)
@@ -20,7 +21,7 @@ from . import coords  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent parts load lazily so that weight/coords utilities work without torch/GPU
-    if name in ("ops", "model", "video", "parallel", "_lib", "serving", "train"):
+    if name in ("ops", "model", "video", "parallel", "_lib", "serving", "train", "metrics"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     if name == "LunaTokis":

@@ -71,8 +71,24 @@ class DecWindow(C.Structure):
         ("out_item", C.c_longlong), ("out_plane", C.c_longlong), ("out_pitch", C.c_int)]
 
 
+METRIC_Y, METRIC_SSIM, METRIC_FLOAT = 1, 2, 4   # stif_metric_args.flags (stif.h STIF_METRIC_*)
+
+
+class MetricArgs(C.Structure):
+    """stif_metric_args: all-zero strides mean dense [n][3][H][W] planes / dense [n][H][W][3] bytes."""
+    _fields_ = [
+        ("pred", _P), ("pred_item", C.c_longlong), ("pred_plane", C.c_longlong), ("pred_pitch", C.c_longlong),
+        ("gt_u8", _P), ("gt_item", C.c_longlong), ("gt_pitch", C.c_longlong),
+        ("gt_f32", _P), ("gtf_item", C.c_longlong), ("gtf_plane", C.c_longlong), ("gtf_pitch", C.c_longlong),
+        ("n", C.c_int), ("H", C.c_int), ("W", C.c_int), ("flags", C.c_int),
+    ]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
+    "stif_metric_workspace_size": (C.c_size_t, [C.c_int] * 4),
+    "stif_metric_psnr_ssim": (C.c_int, [C.POINTER(MetricArgs), _P, _P, C.c_size_t, _P]),
+    "stif_metric_window": (C.c_int, [C.POINTER(C.c_double)]),
     "stif_conv2d_nhwc": (C.c_int, [C.POINTER(ConvArgs), _P]),
     "stif_conv3x3_wino": (C.c_int, [C.POINTER(ConvArgs), _P]),
     "stif_upsample2x_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,

@@ -10,6 +10,10 @@ The harness's data formats either side of the model run on the GPU too:
 ``resize_frames`` = ``data.util.imresize_np(frame, 1/2, True)`` on cv2-style uint8 BGR frames
 + ``/255`` + BGR->RGB + NCHW (:88-93), ``frames_to_u8`` = ``(clamp(0,1)*255).astype(uint8)`` HWC
 (:101-102); ``run_folder`` is the whole script (LR / HR / bicubic outputs, PIL file I/O).
+
+``evaluate_sequence`` / ``evaluate_folder`` add the reference's evaluation loop (myutils.py:1151-1174):
+run_sequence, then PSNR / SSIM of every output frame that has a ground truth, scored on the device
+(stif_amd.metrics), and the "AVG PSNR / AVG SSIM" means.
 """
 from __future__ import annotations
 
@@ -154,3 +158,64 @@ def run_folder(model, in_dir: str, out_dir: str, times=None):
             Image.fromarray(lr_u8[0]).resize((4 * w, 4 * h), Image.BICUBIC).save(
                 os.path.join(out_dir, "bicubic", f"{idx_bic}.jpg"))
             idx_bic += 1
+
+
+# ----------------------------------------------------------------------------- evaluation
+def evaluate_sequence(model, frames: torch.Tensor, gt, times=None, scale=None, channels: str = "y"):
+    """run_sequence + the reference's scoring loop (myutils.py:1155-1174) on the device.  gt[pair][time] is the
+    ground truth of that output frame, uint8 BGR [H, W, 3] (numpy or torch, as cv2.imread), or None to skip it.
+    When pad_to_4 padded the input the outputs are larger than the ground truth: the top-left H x W crop of the
+    output is scored in place, through the metric's stride arguments.  Returns {"psnr", "ssim": lists over pairs
+    of lists over times (None where skipped), "avg_psnr", "avg_ssim": means over the scored frames (the
+    reference's "AVG PSNR / AVG SSIM"), "count"}."""
+    from . import metrics as M
+    outs = run_sequence(model, frames, times, scale)
+    flags = M.mode_flags(channels, True)
+    where, sums = [], []
+    for i, row in enumerate(outs):
+        for k, o in enumerate(row):
+            g = gt[i][k] if i < len(gt) and k < len(gt[i]) else None
+            if g is None:
+                continue
+            g = torch.as_tensor(np.ascontiguousarray(g) if isinstance(g, np.ndarray) else g)
+            H, W = g.shape[:2]
+            if H > o.shape[1] or W > o.shape[2]:
+                raise ValueError(f"gt[{i}][{k}] is {H}x{W}, larger than the {o.shape[1]}x{o.shape[2]} output")
+            sums.append(M.sums(o[None, :, :H, :W], g[None], flags))
+            where.append((i, k))
+    psnr = [[None] * len(row) for row in outs]
+    ssim = [[None] * len(row) for row in outs]
+    if sums:
+        p, s = M.finish(torch.cat(sums, 0).cpu().numpy())     # one read-back for the whole sequence
+        for (i, k), pv, sv in zip(where, p, s):
+            psnr[i][k], ssim[i][k] = float(pv), float(sv)
+    n = len(where)
+    return {"psnr": psnr, "ssim": ssim, "count": n,
+            "avg_psnr": float(np.mean(p)) if n else float("nan"),
+            "avg_ssim": float(np.mean(s)) if n else float("nan")}
+
+
+def _frame_key(name: str):
+    stem = os.path.splitext(name)[0]
+    return (0, int(stem), name) if stem.isdigit() else (1, 0, name)
+
+
+def evaluate_folder(model, lr_dir: str, gt_dir: str, times=None, scale=None, channels: str = "y"):
+    """evaluate_sequence for frames on disk: lr_dir holds the low-resolution input frames, gt_dir the ground
+    truth of the output frames in output order (pair-major, then time: the numbering run_folder writes under
+    HR/); output frames beyond the last file in gt_dir are not scored.  Files are read with PIL and flipped to
+    BGR as run_folder does; numeric names sort by value.  Prints the two averages in the reference's format."""
+    from PIL import Image
+
+    def read(d, name):
+        return np.ascontiguousarray(np.asarray(Image.open(os.path.join(d, name)).convert("RGB"))[:, :, ::-1])
+
+    lr = np.stack([read(lr_dir, nm) for nm in sorted(os.listdir(lr_dir), key=_frame_key)])
+    dev = getattr(model, "device", "cuda")
+    frames = torch.from_numpy(np.ascontiguousarray(lr[:, :, :, ::-1])).to(dev).permute(0, 3, 1, 2).float() / 255.0
+    nt = len(HARNESS_TIMES if times is None else times)
+    gts = [read(gt_dir, nm) for nm in sorted(os.listdir(gt_dir), key=_frame_key)]
+    gt = [[gts[i * nt + k] if i * nt + k < len(gts) else None for k in range(nt)] for i in range(len(lr) - 1)]
+    res = evaluate_sequence(model, frames.contiguous(), gt, times, scale, channels)
+    print("AVG PSNR: {:.4f}, AVG SSIM: {:.4f}".format(res["avg_psnr"], res["avg_ssim"]))
+    return res
