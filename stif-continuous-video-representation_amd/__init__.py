@@ -5,6 +5,7 @@ Layout:
   csrc/       HIP kernels (conv, DCN, decoder) + C ABI (include/stif.h) + host packing
   _lib.py     ctypes binding of libstif_hip.so (no fallback: missing library -> error)
   ops.py      torch-buffer wrappers of the C ABI
+  packing.py  state dict -> packed kernel weights (pack_model, a pure function)
   model.py    LunaTokis host (reference API: forward / gen_feat / decoding / load_state_dict)
   coords.py   fp32 query-grid tables of the decoder
   weights.py  state-dict spec + deterministic weight generator
@@ -21,7 +22,7 @@ from . import coords  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent parts load lazily so that weight/coords utilities work without torch/GPU
-    if name in ("ops", "model", "video", "parallel", "_lib", "serving", "train", "metrics"):
+    if name in ("ops", "packing", "model", "video", "parallel", "_lib", "serving", "train", "metrics"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     if name == "LunaTokis":

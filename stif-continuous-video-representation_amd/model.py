@@ -5,8 +5,8 @@ Mirrors ``codes/models/modules/Sakuya_arch_test.py:LunaTokis`` -- constructor
 ``forward(x, times, scale=None, test=False)`` (:1222-1231), ``gen_feat`` (:313-362),
 ``decoding`` (:364-459), ``load_state_dict(sd, strict=True)`` over the reference's
 442 keys -- as an ``nn.Module`` whose parameters are those 442 tensors, but every layer
-runs through libstif_hip.so on repacked copies (see ops.py); no torch.nn layer is on
-the path.
+runs through libstif_hip.so (ops.py) on repacked copies (packing.py); no torch.nn layer
+is on the path.
 
 Work is batched across everything the reference runs sequentially but that is
 independent: both PCD_Align directions (different weights -> launch groups), both
@@ -31,6 +31,7 @@ from . import _lib as L
 from . import ops
 from . import weights as W
 from .coords import check_window, ensemble_weights, tile_windows, window_from_center
+from .packing import pack_model
 
 _CONST_LOCK = threading.Lock()   # _const's dict is shared by DataParallel replicas (replicate() threads)
 
@@ -42,12 +43,23 @@ def _np(v):
 
 
 def _drain(gen):
-    """Run a stage generator (see LunaTokis._run_lanes) to completion; returns its return value."""
+    """Run a stage generator (see LunaTokis._lockstep) to completion; returns its return value."""
     while True:
         try:
             next(gen)
         except StopIteration as e:
             return e.value
+
+
+def _split(n, k):
+    """Items [0, n) as up to ``k`` contiguous ranges of ceil(n / k) items (the last one may be shorter)."""
+    per = -(-n // max(1, min(k, n)))
+    return [(c0, min(n, c0 + per)) for c0 in range(0, n, per)]
+
+
+def _hr_size(H, Wd, scale):
+    """(HH, WW) of decoding's virtual grid: ``scale`` itself, x4 by default."""
+    return (H * 4, Wd * 4) if scale is None else (int(scale[0]), int(scale[1]))
 
 
 class _Container(nn.Module):
@@ -91,7 +103,7 @@ class LunaTokis(nn.Module):
         self.register_buffer("_range_status", torch.zeros(1, dtype=torch.int32, device=dev), persistent=False)
         self._host = None
         self._layers_key = None
-        self.layers = {}
+        self.layers, self._dec_flags = {}, 0      # the layer set in use and its decoder operand flags (_use)
         self._feat = None
         self.inp = None
         self._tables = {}
@@ -106,7 +118,6 @@ class LunaTokis(nn.Module):
         # f16x3: DCN_sep as one kernel (offset/mask conv + sigmoid + deformable conv, k_dcn_sep); False =
         # the offset/mask conv (k_wino_om) and the deformable conv (k_dcn) as two launches
         self.fused_dcn = bool(fused_dcn)
-        self._dec_flags = L.CONV_F16X3 if mfma == "f16x3" else 0   # decoder SIREN layers likewise
         # f16x3 activations outside the split range: "rerun" the call in fp32 (warning), "raise", or "off"
         if range_check not in ("rerun", "raise", "off"):
             raise ValueError("range_check must be 'rerun', 'raise' or 'off'")
@@ -210,148 +221,29 @@ class LunaTokis(nn.Module):
             else:
                 host[k] = params[k].detach().cpu().numpy().astype(np.float32)
         self._host = host
-        self._pack()
-        return type("IncompatibleKeys", (), {"missing_keys": missing, "unexpected_keys": unexpected})()
-
-    # ------------------------------------------------------------------ weight packing
-    def _pack(self):
-        """Pack every layer for the kernels into non-persistent buffers of ``_pk`` (on the parameters'
-        device).  f16x3 packings whose weights leave the split range fall back to fp32 per layer."""
-        h, dev = self._host, self.device
-        meta = {}
-        bufs = []
-
-        def put(name, pc, extra=None):
-            meta[name] = (len(bufs), pc.cout, pc.cin, pc.ks, pc.mode) if extra is None else (len(bufs),) + extra
-            bufs.append(pc.w)
-            bufs.append(pc.b if pc.b is not None else torch.zeros(1, device=dev))
-
-        def conv(name, mode=L.PACK_PLAIN):
-            put(name, ops.pack_conv(h[name + ".weight"], h[name + ".bias"], mode, dev))
-
-        # 3x3 / stride-1 / 64-cout convs run by Winograd F(2x2,3x3) (stif_conv3x3_wino; the
-        # cat(., up(.)) ones on a materialised x2-upsampled second input), as do the offset/mask
-        # (64 -> 216) and ConvLSTMCell (128 -> 256, gate epilogue) convs; the strided convs keep the
-        # direct kernel, the 1x1 cat convs (fusion, conv_1x1) run k_conv1x1 (f16x3) or the direct
-        # kernel (f32).
-        f16 = L.PACK_F16X3 if self.mfma == "f16x3" else 0
-        wino = (L.PACK_WINO | f16) if self.winograd else L.PACK_PLAIN
-
-        put("conv_first", ops.PackedConv(torch.from_numpy(h["conv_first.weight"]).to(dev),
-                                         torch.from_numpy(h["conv_first.bias"]).to(dev), 64, 3, 3, L.PACK_PLAIN))
-        for i in range(self.front_RBs):
-            conv(f"feature_extraction.{i}.conv1", wino)
-            conv(f"feature_extraction.{i}.conv2", wino)
-        for n in ("fea_L2_conv1", "fea_L3_conv1"):      # 3x3 stride-2 64 -> 64
-            conv(n, L.PACK_PLAIN | f16)
-        for n in ("fea_L2_conv2", "fea_L3_conv2"):
-            conv(n, wino)
-
-        def pcd(prefix):
-            for d in (1, 2):
-                for ln, cin, _ in W._PCD_LAYERS:
-                    n = f"{prefix}{ln}_{d}"
-                    if cin is None:
-                        om = n + ".conv_offset_mask"
-                        if f16 and self.fused_dcn:
-                            # the fused DCN_sep kernel (k_dcn_sep); out of the split range -> the two-kernel path
-                            try:
-                                pom = ops.pack_conv(h[om + ".weight"], h[om + ".bias"], L.PACK_DCNSEP | L.PACK_F16X3,
-                                                    dev, range_fallback=False)
-                                pcore = ops.pack_conv(h[n + ".weight"], h[n + ".bias"], L.PACK_DCNPAIR | L.PACK_F16X3,
-                                                      dev, range_fallback=False)
-                                put(n, pcore)
-                                put(om, pom)
-                                continue
-                            except L.StifError as e:
-                                if e.code != L.E_RANGE:
-                                    raise
-                        conv(n, L.PACK_PLAIN | f16)     # the DCN core (k_dcn)
-                        conv(om, (L.PACK_WINO_OFFMASK | f16) if self.winograd else L.PACK_OFFMASK)
-                    else:
-                        conv(n, wino)
-
-        pcd("pcd_align.")
-        conv("fusion", L.PACK_PLAIN | f16)
-        conv("ConvBLSTM.forward_net.cell_list.0.conv", (L.PACK_WINO_LSTM | f16) if self.winograd else L.PACK_LSTM)
-        for p in ("ConvBLSTM.forward_net.pcd_h.", "ConvBLSTM.forward_net.pcd_c."):
-            for n in ("fea_L2_conv1", "fea_L3_conv1"):
-                conv(p + n, L.PACK_PLAIN | f16)
-            conv(p + "fusion", L.PACK_PLAIN | f16)
-            for n in ("fea_L2_conv2", "fea_L3_conv2"):
-                conv(p + n, wino)
-            pcd(p + "pcd_align.")
-        conv("ConvBLSTM.conv_1x1", L.PACK_PLAIN | f16)
-        for i in range(self.back_RBs):
-            conv(f"recon_trunk.{i}.conv1", wino)
-            conv(f"recon_trunk.{i}.conv2", wino)
-        # decoder: the SIREN MLPs, then the LR projections (their sine-layer scale follows the MLP's
-        # operand mode: omega_0 / (2 pi) -- revolutions -- with f16x3, stif.h STIF_DEC_REVOLUTIONS)
-        mlp, flags = self._pack_mlp(self._dec_flags)
-        self._dec_flags = flags
-        for lr_image in (True, False):
-            put("dec.proj" if lr_image else "dec.proj_hrimg", self._pack_proj(lr_image, bool(flags & L.CONV_F16X3)))
-        meta["dec.mlp"] = (len(bufs), flags)
-        bufs.append(mlp)
-        bufs.append(torch.zeros(1, device=dev))
-        self._pk = _Container()
-        for i, b in enumerate(bufs):
-            self._pk.register_buffer(f"b{i}", b, persistent=False)
-        self._meta = meta
-        self._meta32 = None
-        self._layers_key = None
+        self._pk, self._meta = self._packed(self.mfma)
+        self._meta32 = None        # the fp32 copy, the decoder tables and the constant maps follow the weights
         self._tables = {}
         self._consts = OrderedDict()
+        self._use(self._build_layers(self._pk, self._meta), self._meta)
+        self._layers_key = self._pk.b0.data_ptr()
+        return type("IncompatibleKeys", (), {"missing_keys": missing, "unexpected_keys": unexpected})()
 
-    def _pack_mlp(self, flags):
-        """All SIREN layers (stif_pack_dec_mlp_ex); an out-of-range weight for f16x3 -> fp32 packing."""
-        h, lib = self._host, L.lib()
+    # ------------------------------------------------------------------ packed layers
+    def _packed(self, mfma):
+        """The host weights packed for the kernels (packing.pack_model) on the parameters' device, as
+        non-persistent buffers b0..bN of a new container (so they move and replicate with the module), and
+        their meta."""
+        bufs, meta = pack_model(self._host, self.device, mfma=mfma, winograd=self.winograd, fused_dcn=self.fused_dcn,
+                                front_RBs=self.front_RBs, back_RBs=self.back_RBs)
+        pk = _Container()
+        for i, b in enumerate(bufs):
+            pk.register_buffer(f"b{i}", b, persistent=False)
+        return pk, meta
 
-        def siren_ptrs(prefix, n_sine):
-            arrs = []
-            for i in range(n_sine):
-                arrs += [h[f"{prefix}net.{i}.linear.weight"], h[f"{prefix}net.{i}.linear.bias"]]
-            arrs += [h[f"{prefix}net.{n_sine}.weight"], h[f"{prefix}net.{n_sine}.bias"]]
-            return arrs, (L._P * len(arrs))(*[a.ctypes.data for a in arrs])
-
-        fa, fp = siren_ptrs("feat_imnet.", 3)
-        la, lp = siren_ptrs("flow_imnet.", 3)
-        ea, ep = siren_ptrs("encode_imnet.", 4)
-        mlp = np.empty(lib.stif_dec_mlp_floats(), np.float32)
-        try:
-            L.check(lib.stif_pack_dec_mlp_ex(fp, lp, ep, mlp.ctypes.data, flags), "stif_pack_dec_mlp_ex")
-        except L.StifError as e:
-            if e.code != L.E_RANGE or not flags:
-                raise
-            flags = 0
-            L.check(lib.stif_pack_dec_mlp_ex(fp, lp, ep, mlp.ctypes.data, 0), "stif_pack_dec_mlp_ex")
-        return torch.from_numpy(mlp).to(self.device), flags
-
-    def _pack_proj(self, lr_image=True, revolutions=False):
-        """LR projection of the decoder's first layers (stif_pack_dec_proj_ex); lr_image=False leaves
-        the LR frames out of P2..P4 for decoding_test, which samples the x4-upsampled frames;
-        revolutions: sine-layer scale omega_0 / (2 pi), matching an f16x3-packed MLP."""
-        h, dev, lib = self._host, self.device, L.lib()
-
-        def pack(mode):
-            wd = np.empty(lib.stif_conv_weight_floats(256, 200, 1, mode), np.float32)
-            bd = np.empty(lib.stif_conv_bias_floats(256, L.PACK_PLAIN), np.float32)
-            L.check(lib.stif_pack_dec_proj_ex(h["feat_imnet.net.0.linear.weight"].ctypes.data,
-                                              h["feat_imnet.net.0.linear.bias"].ctypes.data,
-                                              h["flow_imnet.net.0.linear.weight"].ctypes.data,
-                                              h["encode_imnet.net.0.linear.weight"].ctypes.data,
-                                              int(lr_image) | (mode & L.PACK_F16X3) | (L.DEC_REVOLUTIONS if revolutions else 0),
-                                              wd.ctypes.data, bd.ctypes.data),
-                    "stif_pack_dec_proj_ex")
-            return ops.PackedConv(torch.from_numpy(wd).to(dev), torch.from_numpy(bd).to(dev), 256, 200, 1, mode)
-
-        if self.mfma == "f16x3":   # k_conv1x1; a weight outside the split range -> fp32 packing
-            try:
-                return pack(L.PACK_PLAIN | L.PACK_F16X3)
-            except L.StifError as e:
-                if e.code != L.E_RANGE:
-                    raise
-        return pack(L.PACK_PLAIN)
+    def _use(self, layers, meta):
+        """Make ``layers`` (built from ``meta``) the layer set the kernels run with."""
+        self.layers, self._dec_flags = layers, meta["dec.mlp"][1]
 
     def _build_layers(self, pk, meta):
         bufs = pk._buffers
@@ -364,14 +256,7 @@ class LunaTokis(nn.Module):
     def _layers_fp32(self):
         """The f16x3 layers re-packed in fp32 (range fallback), as non-persistent buffers of ``_pk32``."""
         if self._meta32 is None or self._pk32.b0.device != self.device:
-            keep = (self.mfma, self._dec_flags, self._pk, self._meta)
-            self.mfma, self._dec_flags = "f32", 0
-            try:
-                self._pack()
-                self._pk32, self._meta32 = self._pk, self._meta
-            finally:
-                self.mfma, self._dec_flags, self._pk, self._meta = keep
-                self._layers_key = None
+            self._pk32, self._meta32 = self._packed("f32")
         return self._build_layers(self._pk32, self._meta32)
 
     # ------------------------------------------------------------------ call wrapper
@@ -390,7 +275,7 @@ class LunaTokis(nn.Module):
         with torch.cuda.device(dev):
             key = self._pk.b0.data_ptr()
             if self._layers_key != key:
-                self.layers = self._build_layers(self._pk, self._meta)
+                self._use(self._build_layers(self._pk, self._meta), self._meta)
                 self._layers_key = key
             check = self.range_check != "off" and (self.mfma == "f16x3")
             # inside a hipGraph capture the status word is still zeroed and written by the captured
@@ -408,12 +293,12 @@ class LunaTokis(nn.Module):
                     warnings.warn("LunaTokis: an f16x3 operand left the split-fp16 range; re-running this call "
                                   "with fp32 MFMA operands", RuntimeWarning, stacklevel=3)
                     self.range_reruns += 1
-                    keep = (self.layers, self._dec_flags, self._layers_key)
-                    self.layers, self._dec_flags = self._layers_fp32(), 0
+                    keep = self.layers
+                    self._use(self._layers_fp32(), self._meta32)
                     try:
                         out = fn(*args, **kwargs)
                     finally:
-                        self.layers, self._dec_flags, self._layers_key = keep
+                        self._use(keep, self._meta)
             finally:
                 self._active = False
         return out
@@ -508,25 +393,21 @@ class LunaTokis(nn.Module):
             ss.append(torch.cuda.Stream(device=dev))
         return ss[:k]
 
-    def _run_lanes(self, n, make, lanes=None, pool="lanes"):
-        """Items [0, n) in up to ``self.lanes`` contiguous ranges; ``make(c0, c1)`` is a generator
-        issuing one range's launches (each ``yield`` a point where another lane may issue).  Each
-        range runs on its own stream, forked from and joined back into the current one, and the
-        generators advance round-robin, so every stream has queued work from the start and the
-        kernels of one lane fill the last waves and the dispatch gaps of the others.  Every kernel
-        computes each item independently of the batch it is launched in, so the results are
-        bit-identical for any lane count."""
-        k = max(1, min(self.lanes if lanes is None else lanes, n))
-        per = -(-n // k)
-        ranges = [(c0, min(n, c0 + per)) for c0 in range(0, n, per)]
-        if len(ranges) == 1:
-            _drain(make(0, n))
+    def _lockstep(self, gens, pool):
+        """Advance the generators ``gens`` in lock step (generator: one yield per round).  Each ``yield``
+        of a generator is a point where the others may issue.  One generator runs on the current stream,
+        with no stream call at all (the default path, and what a hipGraph capture sees).  Several run on
+        one stream each of ``pool``, forked from and joined back into the current stream, and advance
+        round-robin (a finished one drops out), so every stream has queued work from the start and the
+        kernels of one fill the last waves and the dispatch gaps of the others."""
+        if len(gens) == 1:
+            yield from gens[0]
             return
         main = torch.cuda.current_stream()
-        streams = self._streams(len(ranges), pool)
+        streams = self._streams(len(gens), pool)
         for s in streams:
             s.wait_stream(main)
-        live = [(s, make(c0, c1)) for s, (c0, c1) in zip(streams, ranges)]
+        live = list(zip(streams, gens))
         while live:
             nxt = []
             for s, g in live:
@@ -537,34 +418,30 @@ class LunaTokis(nn.Module):
                     except StopIteration:
                         pass
             live = nxt
+            if live:
+                yield
         for s in streams:
             main.wait_stream(s)
+
+    def _run_lanes(self, n, make, lanes=None, pool="lanes"):
+        """Items [0, n) in up to ``self.lanes`` contiguous ranges, each on its own stream (_lockstep);
+        ``make(c0, c1)`` is a generator issuing one range's launches.  Every kernel computes each item
+        independently of the batch it is launched in, so the results are bit-identical for any lane
+        count."""
+        _drain(self._lockstep([make(c0, c1) for c0, c1 in _split(n, self.lanes if lanes is None else lanes)], pool))
 
     def _resblocks(self, x, tmp, names, lanes=1):
         """A stack of ResidualBlock_noBN on x [n, H, W, 64] in place (generator, one yield per block).
         The items are independent chains, so with ``lanes`` > 1 they are split into that many
         contiguous ranges on their own streams, issued block by block round-robin: one range's tail
         waves and dispatch gaps overlap the other's work.  Bit-identical for any split."""
-        n = x.shape[0]
-        k = max(1, min(lanes, n))
-        if k == 1:
-            for name in names:
-                self._resblock(x, tmp, name)
-                yield
+        ranges = _split(x.shape[0], lanes)
+        if len(ranges) > 1:
+            yield from self._lockstep([self._resblocks(x[c0:c1], tmp[c0:c1], names) for c0, c1 in ranges], "trunk")
             return
-        per = -(-n // k)
-        ranges = [(c0, min(n, c0 + per)) for c0 in range(0, n, per)]
-        main = torch.cuda.current_stream()
-        ss = self._streams(len(ranges), pool="trunk")
-        for s in ss:
-            s.wait_stream(main)
         for name in names:
-            for s, (c0, c1) in zip(ss, ranges):
-                with torch.cuda.stream(s):
-                    self._resblock(x[c0:c1], tmp[c0:c1], name)
+            self._resblock(x, tmp, name)
             yield
-        for s in ss:
-            main.wait_stream(s)
 
     def _resblock(self, x, tmp, name):
         """ResidualBlock_noBN (module_util.py:48-52), x updated in place."""
@@ -683,9 +560,6 @@ class LunaTokis(nn.Module):
         if side is not None:
             main.wait_stream(side)   # before any buffer of this call can be freed and reused on main
 
-    def _bilstm(self, X):
-        return _drain(self._bilstm_steps([X[0], X[1], X[2]]))
-
     def _bilstm_steps(self, X, feats=None):
         """BiDeformableConvLSTM.forward (:256-266) with DeformableConvLSTM.forward (:192-242) for
         both directions batched.  X: the 3 latent inputs [B, H, W, 64] (t-major; views with one common
@@ -739,23 +613,13 @@ class LunaTokis(nn.Module):
             self._conv([dict(layer=lay[pf + "cell_list.0.conv"], in0=xin[d], in1=T[0, j], res=T[1, j],
                              out=hs[d, t], out2=cs[d]) for j, d in enumerate(ds)], epi=L.EPI_LSTM, in1_mode=1)
 
-        if self.lstm_lanes < 2:
+        def steps(ds):
             for t in range(3):
-                step(t, (0, 1))
+                step(t, ds)
                 yield
-        else:
-            # the two directions are independent recurrences: one stream each, step by step round-robin
-            main = torch.cuda.current_stream()
-            ss = self._streams(2, pool="lstm")
-            for s in ss:
-                s.wait_stream(main)
-            for t in range(3):
-                for s, d in zip(ss, (0, 1)):
-                    with torch.cuda.stream(s):
-                        step(t, (d,))
-                yield
-            for s in ss:
-                main.wait_stream(s)
+
+        # lstm_lanes = 2: the two directions are independent recurrences, one stream each, step by step
+        yield from self._lockstep([steps((0, 1))] if self.lstm_lanes < 2 else [steps((0,)), steps((1,))], "lstm")
         if feats is None:
             feats = self._empty(3, B, H, Wd, 64)
         self._conv([dict(layer=lay["ConvBLSTM.conv_1x1"], in0=hs[0, t], in1=hs[1, 2 - t], out=feats[t])
@@ -764,7 +628,7 @@ class LunaTokis(nn.Module):
 
     def _gen_feat_core(self, fea1, fea2, out):
         """Everything after the per-frame features: PCD + fusion, BiConvLSTM, recon trunk, into
-        out [3, B, H, W, 64] (generator: yields between stages, see _run_lanes).
+        out [3, B, H, W, 64] (generator: yields between stages, see _lockstep).
         fea1 / fea2: [L1, L2, L3] of the pairs' first / second frames (item = pair)."""
         B, H, Wd, _ = fea1[0].shape
         X1 = self._empty(B, H, Wd, 64)                  # the fused middle latent input
@@ -948,28 +812,31 @@ class LunaTokis(nn.Module):
         if self._feat is None:
             raise RuntimeError("decoding needs gen_feat first")
         _, B, H, Wd, _ = self._feat.shape
-        HH, WW = (H * 4, Wd * 4) if scale is None else (int(scale[0]), int(scale[1]))
+        HH, WW = _hr_size(H, Wd, scale)
         tab = self._tab(H, Wd, HH, WW)
         tvs = [self._time_vec(tq, B) for tq in times]
         if window is not None or tile is not None:
             return self._decode_windowed(tvs, HH, WW, tab, window, tile)
         outs = [self._empty(B, 3, HH, WW) for _ in times]
-
         # items per decode pass: the LR projections (1 KB per LR pixel) and the HRfeat / flow scratch
         # (272 B per HR pixel) of at most dec_chunk_px HR pixels -- a 63-pair 720p sequence on one GPU
         # would otherwise need ~300 GB of scratch; every pixel is decoded independently, so chunking
         # does not change a bit
-        per = max(1, self.dec_chunk_px // (HH * WW))
+        self._decode_passes(B, max(1, self.dec_chunk_px // (HH * WW)), True, lambda proj, a, b: self._decode_steps(
+            proj, [t[a:b] for t in tvs], HH, WW, tab, [o[a:b] for o in outs]))
+        return outs
 
+    def _decode_passes(self, B, per, lr_image, body):
+        """The items [0, B) over the ``dec`` lanes, in passes of ``per``: the LR projection of a pass's items
+        [a, b), then ``body(proj, a, b)`` (a generator issuing their decode), then the projection is dropped."""
         def lane(c0, c1):
             for a in range(c0, c1, per):
                 b = min(c1, a + per)
-                proj = self._projection(True, a, b)
+                proj = self._projection(lr_image, a, b)
                 yield
-                yield from self._decode_steps(proj, [t[a:b] for t in tvs], HH, WW, tab, [o[a:b] for o in outs])
+                yield from body(proj, a, b)
                 del proj
         self._run_lanes(B, lane, self.dec_lanes, pool="dec")
-        return outs
 
     def decoding_test(self, times=None, scale=None, window=None, tile=None):
         """LunaTokis.decoding_test (:461-598), what forward(test=True) returns: the flow and encode
@@ -981,21 +848,18 @@ class LunaTokis(nn.Module):
     def _decoding_test(self, times=None, scale=None, window=None, tile=None):
         if times is None:
             raise ValueError("times must be a list of query times")
-        if window is not None or tile is not None:
-            if self._feat is None:
-                raise RuntimeError("decoding needs gen_feat first")
-            _, B, H, Wd, _ = self._feat.shape
-            s = 4 if scale is None else int(scale)
-            HH, WW = H * s, Wd * s
-            image = ops.DecImageDev(self.inp, 4, HH, WW)
-            return self._decode_windowed([self._time_vec(tq, B) for tq in times], HH, WW, self._tab(H, Wd, HH, WW),
-                                         window, tile, image)
-        proj = self._projection(lr_image=False)
-        _, H, Wd, _ = proj.shape
+        if self._feat is None:
+            raise RuntimeError("decoding needs gen_feat first")
+        _, B, H, Wd, _ = self._feat.shape
         s = 4 if scale is None else int(scale)
         HH, WW = H * s, Wd * s
+        windowed = window is not None or tile is not None
+        proj = None if windowed else self._projection(lr_image=False)   # a windowed decode projects per pass
         image = ops.DecImageDev(self.inp, 4, HH, WW)
-        return self._decode(proj, times, HH, WW, self._tab(H, Wd, HH, WW), image)
+        tab = self._tab(H, Wd, HH, WW)
+        if windowed:
+            return self._decode_windowed([self._time_vec(tq, B) for tq in times], HH, WW, tab, window, tile, image)
+        return self._decode(proj, times, HH, WW, tab, image)
 
     # ------------------------------------------------------------------ windowed decoding
     def _window_steps(self, proj, tvs, HH, WW, tab, outs, rect, image=None):
@@ -1057,17 +921,12 @@ class LunaTokis(nn.Module):
             st.zero_()   # fp32 operands: only the windows' bit 1 is read below
         per = max(1, self.dec_chunk_px // max(r[2] * r[3] for r in rects))
 
-        def lane(c0, c1):
-            for a in range(c0, c1, per):
-                b = min(c1, a + per)
-                proj = self._projection(image is None, a, b)
-                yield
-                img = image.items(a, b) if image is not None else None
-                for r in rects:
-                    views = [o[a:b, :, r[0] - ry:r[0] - ry + r[2], r[1] - rx:r[1] - rx + r[3]] for o in outs]
-                    yield from self._window_steps(proj, [t[a:b] for t in tvs], HH, WW, tab, views, r, img)
-                del proj
-        self._run_lanes(B, lane, self.dec_lanes, pool="dec")
+        def tiles(proj, a, b):
+            img = image.items(a, b) if image is not None else None
+            for r in rects:
+                views = [o[a:b, :, r[0] - ry:r[0] - ry + r[2], r[1] - rx:r[1] - rx + r[3]] for o in outs]
+                yield from self._window_steps(proj, [t[a:b] for t in tvs], HH, WW, tab, views, r, img)
+        self._decode_passes(B, per, image is None, tiles)
         if st is not None and int(st.item()) & 2:
             raise L.StifError("windowed decode: stage 2 gathered outside its HRfeat rectangle (stif_dec_bounds and "
                               "stage 2 disagree): the result is wrong")
@@ -1083,7 +942,7 @@ class LunaTokis(nn.Module):
         if self._feat is None:
             raise RuntimeError("decoding needs gen_feat first")
         _, _, H, Wd, _ = self._feat.shape
-        HH, WW = (H * 4, Wd * 4) if scale is None else (int(scale[0]), int(scale[1]))
+        HH, WW = _hr_size(H, Wd, scale)
         size = (4 * H, 4 * Wd) if size is None else size
         return self.decoding(times, scale, window=window_from_center(center, HH, WW, size))
 
@@ -1113,7 +972,7 @@ class LunaTokis(nn.Module):
             raise ValueError("decoding_localensemble batches the query times: the latent must have batch 1")
         proj = self._projection()
         _, H, Wd, _ = proj.shape
-        HH, WW = (H * 4, Wd * 4) if scale is None else (int(scale[0]), int(scale[1]))
+        HH, WW = _hr_size(H, Wd, scale)
         key = ("ens", str(self.device), H, Wd, HH, WW)
         if key not in self._tables:
             self._tables[key] = [torch.from_numpy(a).to(self.device) for a in ensemble_weights(H, Wd, HH, WW)]

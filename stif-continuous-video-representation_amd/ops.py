@@ -48,6 +48,23 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _launch(what: str, trace, fn, *args):
+    """Call the library entry ``fn`` and check its status (errors name ``what``).  ``trace``: None, or the
+    arguments of TRACE.begin -- (kind, flops[, nbytes]) -- which callers compute only when TRACE is set."""
+    tr = TRACE if trace is not None else None
+    if tr is not None:
+        tr.begin(*trace)
+    L.check(fn(*args), what)
+    if tr is not None:
+        tr.end()
+
+
+def _pixels_contiguous(t: torch.Tensor) -> bool:
+    """The pixels of each item of NHWC ``t`` are contiguous (strides of size-1 dims never address anything)."""
+    _, h, w, c = t.shape
+    return (c <= 1 or t.stride(3) == 1) and (w <= 1 or t.stride(2) == c) and (h <= 1 or t.stride(1) == w * c)
+
+
 def _item_stride(ts: Sequence[Optional[torch.Tensor]], what: str) -> int:
     strides = {t.stride(0) for t in ts if t is not None}
     if len(strides) > 1:
@@ -57,9 +74,7 @@ def _item_stride(ts: Sequence[Optional[torch.Tensor]], what: str) -> int:
             continue
         if t.dtype != torch.float32 or not t.is_cuda:
             raise ValueError(f"{what}: expected float32 CUDA tensors")
-        _, h, w, c = t.shape
-        # strides of size-1 dims never address anything
-        if (c > 1 and t.stride(3) != 1) or (w > 1 and t.stride(2) != c) or (h > 1 and t.stride(1) != w * c):
+        if not _pixels_contiguous(t):
             raise ValueError(f"{what}: pixels of an item must be contiguous NHWC")
     return strides.pop() if strides else 0
 
@@ -157,23 +172,21 @@ def conv2d(groups, *, epi=L.EPI_NONE, in1_mode=0, in1_scale=1.0, stride=None, st
     a.sched = _vp(sched)
     if sched is not None:
         a.flags |= L.CONV_DYNAMIC
-    tr = TRACE
-    if tr is not None:
+    trace = None
+    if TRACE is not None:
         # algorithmic (direct-convolution) FLOPs, whichever algorithm runs
         # algorithmic HBM bytes: every input read once, every output written once
         px_in, px_out = H * W * nitems * len(groups), Ho * Wo * nitems * len(groups)
         c_in = C0 + (C1 if in1_mode == 1 else C1 / 4.0 if in1_mode == 2 else 0)
         c_out = 128 if epi == L.EPI_LSTM else lay.cout
         c_res = 64 if epi in (L.EPI_RES, L.EPI_LSTM) else 0
-        tr.begin(("wino" if wino else "conv", ks, stride, epi, in1_mode, lay.cout),
+        trace = (("wino" if wino else "conv", ks, stride, epi, in1_mode, lay.cout),
                  2.0 * lay.cout * (C0 + C1) * ks * ks * Ho * Wo * nitems * len(groups),
                  4.0 * (c_in * px_in + (c_out + c_res) * px_out))
     if wino:
-        L.check(L.lib().stif_conv3x3_wino(C.byref(a), _stream()), "stif_conv3x3_wino")
+        _launch("stif_conv3x3_wino", trace, L.lib().stif_conv3x3_wino, C.byref(a), _stream())
     else:
-        L.check(L.lib().stif_conv2d_nhwc(C.byref(a), _stream()), "stif_conv2d_nhwc")
-    if tr is not None:
-        tr.end()
+        _launch("stif_conv2d_nhwc", trace, L.lib().stif_conv2d_nhwc, C.byref(a), _stream())
 
 
 def upsample2x(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0):
@@ -182,20 +195,10 @@ def upsample2x(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0):
     n, h, w, c = x.shape
     if tuple(out.shape) != (n, 2 * h, 2 * w, c):
         raise ValueError(f"upsample2x: out shape {tuple(out.shape)} != {(n, 2 * h, 2 * w, c)}")
-    for t in (x, out):
-        # strides of size-1 dims never address anything, so they are not checked
-        _, th, tw, _ = t.shape
-        if (c > 1 and t.stride(3) != 1) or (tw > 1 and t.stride(2) != c) or (th > 1 and t.stride(1) != tw * c):
-            raise ValueError("upsample2x: pixels must be contiguous")
-    tr = TRACE
-    if tr is not None:
-        tr.begin(("up2",), 0.0)
-    L.check(L.lib().stif_upsample2x_nhwc(_vp(x), _vp(out), n, h, w, c, float(scale),
-                                         x.stride(0) if n > 1 else h * w * c,
-                                         out.stride(0) if n > 1 else 4 * h * w * c, _stream()),
-            "stif_upsample2x_nhwc")
-    if tr is not None:
-        tr.end()
+    if not (_pixels_contiguous(x) and _pixels_contiguous(out)):
+        raise ValueError("upsample2x: pixels must be contiguous")
+    _launch("stif_upsample2x_nhwc", (("up2",), 0.0), L.lib().stif_upsample2x_nhwc, _vp(x), _vp(out), n, h, w, c,
+            float(scale), x.stride(0) if n > 1 else h * w * c, out.stride(0) if n > 1 else 4 * h * w * c, _stream())
 
 
 def conv_first(x_nchw: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor):
@@ -228,13 +231,11 @@ def dcn(groups, *, epi=L.EPI_NONE, status=None):
     f16 = g0["layer"].mode & L.PACK_F16X3
     a.flags = L.CONV_F16X3 if f16 else 0
     a.status = _vp(status)
-    tr = TRACE
-    if tr is not None:
-        tr.begin(("dcn", epi), 2.0 * 64 * 576 * H * W * nitems * len(groups),
+    trace = None
+    if TRACE is not None:
+        trace = (("dcn", epi), 2.0 * 64 * 576 * H * W * nitems * len(groups),
                  4.0 * (64 + 216 + 64) * H * W * nitems * len(groups))
-    L.check(L.lib().stif_dcn_nhwc(C.byref(a), _stream()), "stif_dcn_nhwc")
-    if tr is not None:
-        tr.end()
+    _launch("stif_dcn_nhwc", trace, L.lib().stif_dcn_nhwc, C.byref(a), _stream())
 
 
 def dcn_sep_fusable(om_layer: PackedConv, layer: PackedConv) -> bool:
@@ -270,15 +271,13 @@ def dcn_sep(groups, *, epi=L.EPI_NONE, status=None):
     a.ngroups, a.nitems, a.H, a.W, a.epi = len(groups), nitems, H, W, epi
     a.flags = L.CONV_F16X3
     a.status = _vp(status)
-    tr = TRACE
-    if tr is not None:
+    trace = None
+    if TRACE is not None:
         px = H * W * nitems * len(groups)
         # algorithmic: the offset/mask conv (216 x 576 MACs) + the deformable conv (64 x 576) per pixel;
         # HBM bytes: the offset feature, the DCN input and the output read / written once (768 B / px)
-        tr.begin(("dcnsep", epi), 2.0 * (216 + 64) * 576 * px, 4.0 * 3 * 64 * px)
-    L.check(L.lib().stif_dcn_sep_nhwc(C.byref(a), _stream()), "stif_dcn_sep_nhwc")
-    if tr is not None:
-        tr.end()
+        trace = (("dcnsep", epi), 2.0 * (216 + 64) * 576 * px, 4.0 * 3 * 64 * px)
+    _launch("stif_dcn_sep_nhwc", trace, L.lib().stif_dcn_sep_nhwc, C.byref(a), _stream())
 
 
 def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
@@ -410,21 +409,17 @@ def dec_stage1(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, image: "DecImag
     """window (dec_window): the stage over that rectangle of the tables' grid -- flow [n, hh, ww, 4] (None: HRfeat
     only), hrfeat over the window's F rectangle."""
     n, h, w, _ = proj.shape
+    trace = None
     if window is not None:
         HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
-        L.check(L.lib().stif_dec_stage1_win(_vp(proj), _vp(mlp), C.byref(tables.c), C.byref(image.c) if image else None,
-                                            _vp(t), _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status),
-                                            _stream(), C.byref(window)), "stif_dec_stage1_win")
-        return
-    HH, WW = hrfeat.shape[1:3]
-    tr = TRACE
-    if tr is not None:   # per HR px: feat_imnet layers 1-3 (36,864 MAC) + flow_imnet HRfeat/1-3 (25,600 MAC)
-        tr.begin(("dec1",), 2.0 * 62464 * n * HH * WW)
-    L.check(L.lib().stif_dec_stage1_ex(_vp(proj), _vp(mlp), C.byref(tables.c), C.byref(image.c) if image else None,
-                                       _vp(t), _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream()),
-            "stif_dec_stage1")
-    if tr is not None:
-        tr.end()
+        what, fn, tail = "stif_dec_stage1_win", L.lib().stif_dec_stage1_win, (C.byref(window),)
+    else:
+        HH, WW = hrfeat.shape[1:3]
+        what, fn, tail = "stif_dec_stage1", L.lib().stif_dec_stage1_ex, ()
+        if TRACE is not None:   # per HR px: feat_imnet layers 1-3 (36,864 MAC) + flow_imnet HRfeat/1-3 (25,600 MAC)
+            trace = (("dec1",), 2.0 * 62464 * n * HH * WW)
+    _launch(what, trace, fn, _vp(proj), _vp(mlp), C.byref(tables.c), C.byref(image.c) if image else None, _vp(t),
+            _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream(), *tail)
 
 
 def dec_bounds(flow, tables: DecTablesDev, box, window: L.DecWindow):
@@ -446,22 +441,18 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
     """window (dec_window): the stage over that rectangle -- hrfeat over its F rectangle, flow [n, hh, ww, 4], and
     out any [n, 3, hh, ww] view with unit column stride (e.g. a tile of a larger [n, 3, HH, WW] tensor)."""
     n, h, w, _ = proj.shape
+    trace = None
     if window is not None:
         HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
         if tuple(out.shape) != (n, 3, window.hh, window.ww) or (window.ww > 1 and out.stride(3) != 1):
             raise ValueError(f"dec_stage2: out must be {(n, 3, window.hh, window.ww)} with unit column stride")
         win = L.DecWindow.from_buffer_copy(window)
         win.out_item, win.out_plane, win.out_pitch = out.stride(0), out.stride(1), out.stride(2)
-        L.check(L.lib().stif_dec_stage2_win(_vp(proj), _vp(mlp), _vp(hrfeat), _vp(flow), C.byref(tables.c),
-                                            C.byref(image.c) if image else None, _vp(t), _vp(out), n, h, w, HH, WW,
-                                            flags, _vp(status), _stream(), C.byref(win)), "stif_dec_stage2_win")
-        return
-    HH, WW = hrfeat.shape[1:3]
-    tr = TRACE
-    if tr is not None:   # per HR px: encode_imnet HRfeat part + layers 1-4 (94,976 MAC)
-        tr.begin(("dec2",), 2.0 * 94976 * n * HH * WW)
-    L.check(L.lib().stif_dec_stage2_ex(_vp(proj), _vp(mlp), _vp(hrfeat), _vp(flow), C.byref(tables.c),
-                                       C.byref(image.c) if image else None, _vp(t), _vp(out), n, h, w, HH, WW, flags,
-                                       _vp(status), _stream()), "stif_dec_stage2")
-    if tr is not None:
-        tr.end()
+        what, fn, tail = "stif_dec_stage2_win", L.lib().stif_dec_stage2_win, (C.byref(win),)
+    else:
+        HH, WW = hrfeat.shape[1:3]
+        what, fn, tail = "stif_dec_stage2", L.lib().stif_dec_stage2_ex, ()
+        if TRACE is not None:   # per HR px: encode_imnet HRfeat part + layers 1-4 (94,976 MAC)
+            trace = (("dec2",), 2.0 * 94976 * n * HH * WW)
+    _launch(what, trace, fn, _vp(proj), _vp(mlp), _vp(hrfeat), _vp(flow), C.byref(tables.c),
+            C.byref(image.c) if image else None, _vp(t), _vp(out), n, h, w, HH, WW, flags, _vp(status), _stream(), *tail)

@@ -224,6 +224,35 @@ def test_lanes_are_bit_identical(models):
         assert torch.equal(res[k][2], ref[2]), k
 
 
+def test_lockstep_schedules_generators_on_pool_streams(stif):
+    """LunaTokis._lockstep, the one fork / round-robin / join primitive under lanes, trunk lanes and the
+    two-stream BiConvLSTM (no kernel runs here): one generator stays on the current stream and creates no
+    stream; several advance round-robin, each on its own stream of the pool, a finished one dropping out."""
+    m = stif.LunaTokis(64, 6, 8, 5, 40)
+    main = torch.cuda.current_stream().cuda_stream
+    log = []
+
+    def lane(i, n):
+        for r in range(n):
+            log.append((i, r, torch.cuda.current_stream().cuda_stream))
+            yield
+
+    assert sum(1 for _ in m._lockstep([lane(0, 3)], "lanes")) == 3
+    assert log == [(0, 0, main), (0, 1, main), (0, 2, main)] and m._lane_streams == {}
+    seen = []
+    for _ in range(2):
+        del log[:]
+        assert sum(1 for _ in m._lockstep([lane(0, 3), lane(1, 1), lane(2, 2)], "lanes")) == 3   # one yield per round
+        assert [e[:2] for e in log] == [(0, 0), (1, 0), (2, 0), (0, 1), (2, 1), (0, 2)]
+        streams = [{s for i, _, s in log if i == k} for k in range(3)]
+        assert all(len(s) == 1 for s in streams)
+        seen.append([s.pop() for s in streams])
+        assert len(set(seen[-1])) == 3 and main not in seen[-1]
+        assert torch.cuda.current_stream().cuda_stream == main
+    assert seen[0] == seen[1] == [s.cuda_stream for s in m._streams(3, "lanes")]
+    assert list(m._lane_streams) == [("lanes", str(m.device))]
+
+
 @pytest.mark.parametrize("mf", ["f16x3", "f32"])
 def test_zero_state_l1_skip_is_bit_identical(models, mf):
     """PCD alignment of the ConvLSTM's first step: a unit whose sampled L1 map is the all-zero initial
