@@ -423,6 +423,52 @@ int stif_metric_psnr_ssim(const stif_metric_args* args, double* out, void* works
 /* The normalised 1-D window (cv2.getGaussianKernel(11, 1.5)) as the host computes it for the kernel. */
 int stif_metric_window(double k[11]);
 
+/* ---- video I/O: planar Y'CbCr (the frame payload of a YUV4MPEG2 stream) <-> the model's fp32 RGB planes ---- */
+
+enum { STIF_YUV_BT601 = 0, STIF_YUV_BT709 = 1 };   /* stif_yuv_format.matrix: (Kr, Kb) = (0.299, 0.114) / (0.2126, 0.0722) */
+
+/* Zero-initialise, then fill.  Three planes per frame, luma width x height and chroma ceil(width / 2^sub_x) x
+ * ceil(height / 2^sub_y); 4:4:4 = (0, 0), 4:2:2 = (1, 0), 4:2:0 = (1, 1).  depth 8: samples are bytes; 9..16:
+ * little-endian uint16 (as Y4M stores them), planes / pitches / frame stride 2-byte aligned.  Sample values:
+ * luma = yoff + yrange Y', chroma = 2^(depth-1) + crange C, with Y' = Kr R + Kg G + Kb B in [0, 1] and
+ * Cb = (B - Y') / (2 (1 - Kb)), Cr = (R - Y') / (2 (1 - Kr)) in [-1/2, 1/2]; (yoff, yrange, crange) =
+ * (16, 219, 224) * 2^(depth-8) with full_range = 0 and (0, 2^depth - 1, 2^depth - 1) with full_range = 1.  No
+ * transfer function is applied: samples are display-referred, like the harness's 8-bit frames.
+ * Both entry points take the three plane pointers of frame 0; frame i's planes start i * frame_stride bytes later.
+ * pitch_y = pitch_c = 0 means dense rows, frame_stride = 0 means the dense Y4M frame, height * pitch_y +
+ * 2 * chroma height * pitch_c bytes (Y | U | V).
+ * Chroma siting: a chroma sample is taken to sit at the centre of its 2^sub_x x 2^sub_y box of luma pixels, in
+ * every subsampled layout.  That is exact for Y4M's 420jpeg; for 420mpeg2 / 420 (horizontally co-sited) and
+ * 420paldv (co-sited, Cb / Cr on alternate lines) it shifts the chroma by at most half a luma pixel. */
+typedef struct {
+  int width, height;           /* luma size, >= 1 (odd sizes give partial chroma boxes at the right / bottom edge) */
+  int sub_x, sub_y;            /* log2 chroma subsampling, 0 or 1 */
+  int depth;                   /* 8..16 bits per sample */
+  int matrix;                  /* STIF_YUV_BT601 / STIF_YUV_BT709 */
+  int full_range;              /* 0 limited ("TV"), 1 full ("PC") */
+  long long pitch_y, pitch_c;  /* bytes between rows of the luma / chroma planes; 0 = dense */
+  long long frame_stride;      /* bytes between frames; 0 = dense Y | U | V */
+} stif_yuv_format;
+
+/* n planar frames -> fp32 RGB planes in [0, 1]: element (i, c, y, x) is written at out[i * out_item +
+ * c * out_plane + y * out_pitch + x] (the addressing of stif_metric_args.pred; all zero = a dense [n][3][H][W]), so
+ * frames land directly in the top-left of a zero-filled, padded-to-4 [n][3][h_n][w_n] model input and nothing
+ * outside the width x height rectangles is written.  Subsampled chroma is upsampled bilinearly (weights 3/4, 1/4
+ * per subsampled axis, edge samples replicated; exact in fp32), then range expansion, matrix, clamp to [0, 1].
+ * Validated before the launch: STIF_E_INVALID for a null pointer, n / width / height < 1, sub_x / sub_y / matrix /
+ * full_range outside their values, depth outside 8..16, a pitch below the row length, a frame stride below a
+ * plane's extent, misaligned 16-bit planes, overlapping out planes / items. */
+int stif_yuv_to_rgb(const stif_yuv_format* fmt, const void* y, const void* u, const void* v, int n, float* out,
+                    long long out_item, long long out_plane, long long out_pitch, void* stream);
+/* n fp32 RGB frames (unclamped; element (i, c, y, x) at rgb[i * rgb_item + c * rgb_plane + y * rgb_pitch + x], all
+ * zero = dense, so the top-left crop of a padded decoder output is converted in place) -> planar frames.  RGB is
+ * clamped to [0, 1]; each chroma sample is the mean of Cb / Cr over the pixels of its box that exist, taken before
+ * the quantisation; samples are rounded half to even (rintf, the rule of stif_metric_psnr_ssim's tensor2img) and
+ * clamped to [0, 2^depth - 1].  Arithmetic is fp32 up to 10 bits and fp64 above (fp32's rounding error reaches
+ * 4e-3 of a sample step at 16 bits).  Validation as stif_yuv_to_rgb. */
+int stif_rgb_to_yuv(const stif_yuv_format* fmt, const float* rgb, long long rgb_item, long long rgb_plane,
+                    long long rgb_pitch, int n, void* y, void* u, void* v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

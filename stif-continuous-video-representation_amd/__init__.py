@@ -9,7 +9,8 @@ Layout:
   model.py    LunaTokis host (reference API: forward / gen_feat / decoding / load_state_dict)
   coords.py   fp32 query-grid tables of the decoder
   weights.py  state-dict spec + deterministic weight generator
-  video.py    custom_video_test-style sliding-window driver
+  video.py    custom_video_test-style sliding-window driver; streaming renderer (any length, any frame rate)
+  y4m.py      YUV4MPEG2 reader / writer (pure host; the device side is ops.yuv_to_rgb / rgb_to_yuv)
   metrics.py  on-device PSNR / SSIM of decoded frames against ground truth (the reference's evaluation loop)
 (integration/_ext.py at the repo root is the DCNv2 `_ext` shim over ops.dcn_v2_forward)
   parallel.py frame-pair sharding over ranks
@@ -22,7 +23,7 @@ from . import coords  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent parts load lazily so that weight/coords utilities work without torch/GPU
-    if name in ("ops", "packing", "model", "video", "parallel", "_lib", "serving", "train", "metrics"):
+    if name in ("ops", "packing", "model", "video", "parallel", "_lib", "serving", "train", "metrics", "y4m"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     if name == "LunaTokis":

@@ -84,8 +84,19 @@ class MetricArgs(C.Structure):
     ]
 
 
+YUV_BT601, YUV_BT709 = 0, 1   # stif_yuv_format.matrix (stif.h STIF_YUV_*)
+
+
+class YuvFormat(C.Structure):
+    """stif_yuv_format: zero pitches / frame stride mean dense rows / the dense Y4M frame Y | U | V."""
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "sub_x", "sub_y", "depth", "matrix", "full_range")] + [
+        ("pitch_y", C.c_longlong), ("pitch_c", C.c_longlong), ("frame_stride", C.c_longlong)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
+    "stif_yuv_to_rgb": (C.c_int, [C.POINTER(YuvFormat), _P, _P, _P, C.c_int, _P] + [C.c_longlong] * 3 + [_P]),
+    "stif_rgb_to_yuv": (C.c_int, [C.POINTER(YuvFormat), _P] + [C.c_longlong] * 3 + [C.c_int, _P, _P, _P, _P]),
     "stif_metric_workspace_size": (C.c_size_t, [C.c_int] * 4),
     "stif_metric_psnr_ssim": (C.c_int, [C.POINTER(MetricArgs), _P, _P, C.c_size_t, _P]),
     "stif_metric_window": (C.c_int, [C.POINTER(C.c_double)]),

@@ -826,6 +826,28 @@ class LunaTokis(nn.Module):
             proj, [t[a:b] for t in tvs], HH, WW, tab, [o[a:b] for o in outs]))
         return outs
 
+    def decoding_pairs(self, pairs, times=None, scale=None):
+        """``decoding`` for the items ``pairs`` (indices into the current latent, in that order) only: list over
+        times of [len(pairs),3,HH,WW]; a query time holds one value or one per selected pair.  Items are decoded
+        independently, so each output equals that item's slice of a ``decoding`` of the whole latent bit for bit.
+        The latent is left as it is (the video stream renderer decodes the pairs of a chunk that share a number
+        of query times in one call)."""
+        feat, inp = self.__dict__.get("_feat"), self.__dict__.get("inp")
+        if feat is None:
+            raise RuntimeError("decoding needs gen_feat first")
+        pairs = [int(i) for i in pairs]
+        B = feat.shape[1]
+        if not pairs or min(pairs) < 0 or max(pairs) >= B:
+            raise ValueError(f"pairs must be indices into the {B} items of the latent, got {pairs}")
+        if pairs == list(range(B)):
+            return self.decoding(times, scale)
+        idx = torch.tensor(pairs, device=feat.device, dtype=torch.long)
+        self._feat, self.inp = feat.index_select(1, idx), inp.index_select(0, idx)
+        try:
+            return self.decoding(times, scale)
+        finally:
+            self._feat, self.inp = feat, inp
+
     def _decode_passes(self, B, per, lr_image, body):
         """The items [0, B) over the ``dec`` lanes, in passes of ``per``: the LR projection of a pass's items
         [a, b), then ``body(proj, a, b)`` (a generator issuing their decode), then the projection is dropped."""

@@ -456,3 +456,86 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
             trace = (("dec2",), 2.0 * 94976 * n * HH * WW)
     _launch(what, trace, fn, _vp(proj), _vp(mlp), _vp(hrfeat), _vp(flow), C.byref(tables.c),
             C.byref(image.c) if image else None, _vp(t), _vp(out), n, h, w, HH, WW, flags, _vp(status), _stream(), *tail)
+
+
+# ----------------------------------------------------------------------------- video I/O (planar YUV <-> RGB)
+_YUV_MATRIX = {"bt601": L.YUV_BT601, "bt709": L.YUV_BT709}
+
+
+def _yuv_planes(frames, fmt):
+    """(stif_yuv_format, y, u, v pointers of frame 0, n) for ``frames``: a uint8 device tensor [n, fmt.frame_bytes]
+    (or [fmt.frame_bytes]) of dense Y4M frame payloads Y | U | V, or three uint8 plane tensors (y, u, v), each
+    [n, rows, row bytes] with contiguous rows -- views of one buffer, so that they share the frame stride."""
+    f = L.YuvFormat(fmt.width, fmt.height, fmt.sub_x, fmt.sub_y, fmt.depth, _YUV_MATRIX[fmt.matrix],
+                    int(bool(fmt.full_range)))
+    cw, ch = fmt.chroma_size
+    bps = fmt.bytes_per_sample
+    if isinstance(frames, (tuple, list)):
+        y, u, v = frames
+        n = y.shape[0]
+        for t, rows, rb in ((y, fmt.height, fmt.width * bps), (u, ch, cw * bps), (v, ch, cw * bps)):
+            if t.dtype != torch.uint8 or not t.is_cuda or tuple(t.shape) != (n, rows, rb) or (rb > 1 and t.stride(2) != 1):
+                raise ValueError(f"yuv planes must be uint8 CUDA tensors [n, rows, row bytes]; expected {(n, rows, rb)}, "
+                                 f"got {t.dtype} {tuple(t.shape)}")
+        if u.stride(1) != v.stride(1) or (n > 1 and not y.stride(0) == u.stride(0) == v.stride(0)):
+            raise ValueError("yuv planes must share the chroma pitch and the frame stride (views of one buffer)")
+        f.pitch_y, f.pitch_c = y.stride(1), u.stride(1)
+        f.frame_stride = y.stride(0) if n > 1 else 0
+        return f, y.data_ptr(), u.data_ptr(), v.data_ptr(), n
+    t = frames
+    if t.dim() == 1:
+        t = t[None]
+    if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 2 or t.shape[1] != fmt.frame_bytes or not t.is_contiguous():
+        raise ValueError(f"yuv frames must be a contiguous uint8 CUDA tensor [n, {fmt.frame_bytes}], got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    ysz, csz = fmt.height * fmt.width * bps, ch * cw * bps
+    p = t.data_ptr()
+    return f, p, p + ysz, p + ysz + csz, t.shape[0]
+
+
+def _rgb_strides(t, n, H, W, what):
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 4 or t.shape[0] != n or t.shape[1] != 3:
+        raise ValueError(f"{what} must be a float32 CUDA tensor [{n}, 3, H, W], got {t.dtype} {tuple(t.shape)}")
+    if t.shape[3] > 1 and t.stride(3) != 1:
+        raise ValueError(f"{what}: the last dimension must be contiguous")
+    item = t.stride(0) if n > 1 else 2 * t.stride(1) + (H - 1) * t.stride(2) + W   # one item: never used
+    return item, t.stride(1), t.stride(2)
+
+
+def yuv_to_rgb(frames, fmt, out=None):
+    """Planar YUV frames (see ``_yuv_planes``; ``fmt``: a y4m.YuvFormat) -> fp32 RGB in [0, 1] (stif_yuv_to_rgb).
+    out: None for a new [n, 3, H, W], or any float32 [n, 3, >= H, >= W] with contiguous rows -- the frames are
+    written into its top-left corner through its strides and the rest of it is left as it is, so a zero-filled
+    tensor padded to a multiple of 4 is the model's input with no further copy."""
+    f, y, u, v, n = _yuv_planes(frames, fmt)
+    H, W = fmt.height, fmt.width
+    if out is None:
+        dev = (frames[0] if isinstance(frames, (tuple, list)) else frames).device
+        out = torch.empty(n, 3, H, W, device=dev, dtype=torch.float32)
+    elif out.dim() != 4 or out.shape[2] < H or out.shape[3] < W:
+        raise ValueError(f"yuv_to_rgb: out must be [n, 3, >= {H}, >= {W}], got {tuple(out.shape)}")
+    item, plane, pitch = _rgb_strides(out, n, H, W, "yuv_to_rgb: out")
+    _launch("stif_yuv_to_rgb", None, L.lib().stif_yuv_to_rgb, C.byref(f), y, u, v, n, _vp(out), item, plane, pitch,
+            _stream())
+    return out
+
+
+def rgb_to_yuv(rgb, fmt, out=None):
+    """fp32 RGB frames [n, 3, H, W] (unclamped; any view with contiguous rows, e.g. the top-left crop of a padded
+    decoder output) -> planar YUV frames of ``fmt`` (stif_rgb_to_yuv): a uint8 [n, fmt.frame_bytes] tensor of dense
+    Y4M frame payloads (``out``, or a new one), or the three plane tensors passed as ``out`` (see ``_yuv_planes``)."""
+    if rgb.dim() == 3:
+        rgb = rgb[None]
+    n = rgb.shape[0]
+    H, W = fmt.height, fmt.width
+    if tuple(rgb.shape[2:]) != (H, W):
+        raise ValueError(f"rgb_to_yuv: rgb is {tuple(rgb.shape)}, the format {H} x {W}")
+    item, plane, pitch = _rgb_strides(rgb, n, H, W, "rgb_to_yuv: rgb")
+    if out is None:
+        out = torch.empty(n, fmt.frame_bytes, device=rgb.device, dtype=torch.uint8)
+    f, y, u, v, n_out = _yuv_planes(out, fmt)
+    if n_out != n:
+        raise ValueError(f"rgb_to_yuv: out holds {n_out} frames, rgb {n}")
+    _launch("stif_rgb_to_yuv", None, L.lib().stif_rgb_to_yuv, C.byref(f), _vp(rgb), item, plane, pitch, n, y, u, v,
+            _stream())
+    return out

@@ -14,6 +14,11 @@ The harness's data formats either side of the model run on the GPU too:
 ``evaluate_sequence`` / ``evaluate_folder`` add the reference's evaluation loop (myutils.py:1151-1174):
 run_sequence, then PSNR / SSIM of every output frame that has a ground truth, scored on the device
 (stif_amd.metrics), and the "AVG PSNR / AVG SSIM" means.
+
+``frame_schedule`` / ``render_stream`` / ``render_y4m`` render whole videos: any length in bounded memory (frames
+are taken a chunk at a time, each encoded once), any rational output frame rate (every pair gets its own query
+times), raw YUV4MPEG2 in and out (stif_amd.y4m, ops.yuv_to_rgb / rgb_to_yuv).  They compose gen_feat_window and
+decoding; the harness functions above keep the reference's behaviour, truncating quantisation included.
 """
 from __future__ import annotations
 
@@ -219,3 +224,247 @@ def evaluate_folder(model, lr_dir: str, gt_dir: str, times=None, scale=None, cha
     res = evaluate_sequence(model, frames.contiguous(), gt, times, scale, channels)
     print("AVG PSNR: {:.4f}, AVG SSIM: {:.4f}".format(res["avg_psnr"], res["avg_ssim"]))
     return res
+
+
+# ----------------------------------------------------------------------------- streaming whole videos
+def frame_schedule(fps_in, fps_out, n_frames=None):
+    """Where the output frames of a frame-rate conversion fall, in exact Fraction arithmetic: yields (pair, t)
+    for output frame j = 0, 1, ...: its instant j / fps_out lies in input pair p = floor(j fps_in / fps_out)
+    (between input frames p and p + 1) at t = j fps_in / fps_out - p in [0, 1).  Any positive rational rates;
+    with fps_out < fps_in some pairs receive no frame.  n_frames=None: endless, to be consumed as pairs become
+    available.  n_frames = n: the floor((n - 1) fps_out / fps_in) + 1 frames of an n-frame clip, where an output
+    falling exactly on the last input instant is pair n - 2 at t = 1 (there is no pair n - 1)."""
+    from fractions import Fraction
+    fi, fo = Fraction(fps_in), Fraction(fps_out)
+    if fi <= 0 or fo <= 0:
+        raise ValueError("frame rates must be positive")
+    if n_frames is not None and n_frames < 2:
+        raise ValueError("a clip needs at least two frames")
+    step = fi / fo
+    j = 0
+    while True:
+        pos = j * step
+        p = pos.numerator // pos.denominator
+        t = pos - p
+        if n_frames is not None and p >= n_frames - 1:
+            if p == n_frames - 1 and t == 0:
+                yield n_frames - 2, Fraction(1)
+            return
+        yield p, t
+        j += 1
+
+
+def _padded_size(h, w):
+    return int(4 * math.ceil(h / 4)), int(4 * math.ceil(w / 4))
+
+
+def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw):
+    """render_stream's core.  ``chunks`` yields device tensors [k, 3, h_n, w_n] of new input frames, already
+    zero-padded to a multiple of 4 (k >= 1; the pairs of a chunk are its frames plus the previous chunk's last).
+    Gradients are switched off around the model calls only, never across a yield."""
+    hn, wn = _padded_size(h, w)
+    OH, OW = out_hw
+    grid = (int(round(OH * hn / h)), int(round(OW * wn / w)))      # virtual grid of the padded frame
+    sched = frame_schedule(fps_in, fps_out)
+    pending = next(sched)
+    base = 0                      # index of the first pair of the current chunk
+    last, last_feats = None, None
+    B = 0                         # pairs of the latent the model holds after a chunk (for the closing t = 1 frame)
+
+    def fuse(x, feats, a, b):
+        with torch.no_grad():
+            model.gen_feat_window(x[a:b + 1], frame_feats=tuple(f[a:b + 1] for f in feats))
+        return b - a
+
+    for x in chunks:
+        with torch.no_grad():
+            feats = model.frame_features(x)                         # every frame is encoded exactly once
+            if last is not None:
+                x = torch.cat([last, x])
+                feats = tuple(torch.cat([a, b]) for a, b in zip(last_feats, feats))
+            last, last_feats = x[-1:].clone(), tuple(f[-1:].clone() for f in feats)
+        P = x.shape[0] - 1
+        if P == 0:
+            continue                                                # a first chunk of one frame: no pair yet
+        per = [[] for _ in range(P)]                                # query times of each pair of the chunk
+        while pending[0] < base + P:
+            per[pending[0] - base].append(pending[1])
+            pending = next(sched)
+        # runs of consecutive pairs that have queries share one latent; pairs without an output are not run
+        a = 0
+        while a < P:
+            if not per[a]:
+                a += 1
+                continue
+            b = a
+            while b < P and per[b]:
+                b += 1
+            B = fuse(x, feats, a, b)
+            yield from _decode_run(model, per[a:b], grid, OH, OW)
+            a = b
+        base += P
+        if not per[-1] and pending == (base, 0):
+            # the next output falls exactly on this chunk's last frame: if the stream ends here it is the last
+            # pair at t = 1, so its latent is made now, while both of its frames are held (should the stream
+            # go on, this one pair was fused for nothing; only a lower output rate can come here)
+            B = fuse(x, feats, P - 1, P)
+        del x, feats
+    if base == 0:
+        raise ValueError("render_stream needs at least two frames")
+    if pending == (base, 0):
+        # the stream ended on an output instant: the last pair (the last item of the model's latent) at t = 1
+        yield from _decode_run(model, [[]] * (B - 1) + [[1]], grid, OH, OW)
+
+
+def _decode_run(model, per, grid, OH, OW):
+    """Decode the model's current latent (one item per entry of ``per``) at each item's own query times and yield
+    the top-left OH x OW crops in display order.  Items are grouped by their number of queries, one decoding call
+    per group with per-item times, so no frame is decoded that is not yielded."""
+    groups = {}
+    for i, ts in enumerate(per):
+        if ts:
+            groups.setdefault(len(ts), []).append(i)
+    outs = {}
+    for cnt, idx in groups.items():
+        times = [torch.tensor([float(per[i][k]) for i in idx], dtype=torch.float32) for k in range(cnt)]
+        with torch.no_grad():
+            preds = model.decoding_pairs(idx, times, grid)
+        for j, i in enumerate(idx):
+            outs[i] = [p[j] for p in preds]
+        del preds
+    for i in sorted(outs):
+        for o in outs.pop(i):
+            yield o[:, :OH, :OW]
+
+
+def _out_size(h, w, scale, out_size):
+    if out_size is not None:
+        OH, OW = int(out_size[0]), int(out_size[1])
+    else:
+        OH, OW = int(round(h * scale)), int(round(w * scale))
+    if OH < 1 or OW < 1:
+        raise ValueError(f"bad output size {OH} x {OW}")
+    return OH, OW
+
+
+def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_pairs=8):
+    """Render a video of any length at any output frame rate in bounded memory.  ``frames``: an iterable of RGB
+    float [3, h, w] frames in [0, 1] (host or device) at ``fps_in``; yields device float [3, OH, OW] frames
+    (unclamped) at ``fps_out`` in display order, (OH, OW) = ``out_size`` or (h, w) * ``scale``.  The output frames
+    are those of ``frame_schedule``; each equals the crop of ``run_sequence(model, clip, times=[t])[pair][0]`` bit
+    for bit, whatever the chunking.
+
+    Frames are taken ``chunk_pairs`` at a time (one more for the first chunk), padded to a multiple of 4 as the
+    harness does, and encoded exactly once (``frame_features``); the last frame of a chunk and its features are
+    carried into the next.  The decoder's virtual grid is that of the padded frame, (round(OH h_n / h),
+    round(OW w_n / w)), and the yielded frame its top-left OH x OW crop -- for h, w multiples of 4 exactly
+    ``decoding(scale=(OH, OW))``.  Alive at a time: at most chunk_pairs + 1 input frames, one chunk's features and
+    latents, and the decoded frames of one chunk that have not been yielded yet."""
+    import itertools
+    if chunk_pairs < 1:
+        raise ValueError("chunk_pairs must be >= 1")
+    it = iter(frames)
+    head = list(itertools.islice(it, 1))
+    if not head:
+        raise ValueError("render_stream needs at least two frames")
+    if head[0].dim() != 3 or head[0].shape[0] != 3:
+        raise ValueError(f"frames must be [3, h, w], got {tuple(head[0].shape)}")
+    h, w = head[0].shape[1:]
+    hn, wn = _padded_size(h, w)
+    dev = getattr(model, "device", "cuda")
+
+    def chunks():
+        want = chunk_pairs + 1
+        while True:
+            new = head + list(itertools.islice(it, want - len(head)))
+            if not new:
+                return
+            head.clear()
+            want = chunk_pairs
+            x = torch.zeros(len(new), 3, hn, wn, device=dev, dtype=torch.float32)
+            while new:
+                f = new.pop()
+                if tuple(f.shape) != (3, h, w):
+                    raise ValueError(f"frame of shape {tuple(f.shape)} in a {h} x {w} stream")
+                x[len(new), :, :h, :w] = f
+                del f
+            yield x
+
+    return _render_chunks(model, chunks(), h, w, fps_in, fps_out, _out_size(h, w, scale, out_size))
+
+
+def render_y4m(model, src, dst, fps_out=None, multiplier=8, scale=4, chunk_pairs=8, matrix="auto", out_size=None):
+    """Render a YUV4MPEG2 stream to another: reader -> upload -> yuv_to_rgb -> render_stream -> rgb_to_yuv ->
+    download -> writer.  src / dst: paths or binary file objects (pipes work: nothing seeks).  The output runs at
+    ``fps_out`` (default: ``multiplier`` x the input rate) and (h, w) * ``scale`` (or ``out_size`` = (OH, OW)); it
+    keeps the input's chroma layout, depth, range, matrix ("auto": BT.709 for an input luma >= 1280 wide or >= 720
+    high, else BT.601) and X tags, so colours survive the round trip.  Uploads and downloads go through pinned host
+    buffers, one chunk of input frames / one chunk's worth of output frames at a time.  Returns (frames read,
+    frames written)."""
+    from fractions import Fraction
+
+    from . import ops, y4m
+    reader = y4m.Y4MReader(src, matrix)
+    try:
+        fmt = reader.fmt
+        fps_in = reader.fps
+        fps_o = Fraction(fps_out) if fps_out is not None else fps_in * Fraction(multiplier)
+        h, w = fmt.height, fmt.width
+        hn, wn = _padded_size(h, w)
+        OH, OW = _out_size(h, w, scale, out_size)
+        fmt_out = fmt.resized(OW, OH)
+        dev = getattr(model, "device", "cuda")
+        first_n = chunk_pairs + 1
+        pin_in = torch.empty(first_n, fmt.frame_bytes, dtype=torch.uint8).pin_memory()
+        host_in = pin_in.numpy()
+        uploaded = torch.cuda.Event()
+
+        def chunks():
+            want = first_n
+            while True:
+                k = 0
+                uploaded.synchronize()                    # the previous chunk has left the pinned buffer
+                while k < want:
+                    fr = reader.read_frame()
+                    if fr is None:
+                        break
+                    host_in[k] = fr
+                    k += 1
+                if k == 0:
+                    return
+                want = chunk_pairs
+                yuv = pin_in[:k].to(dev, non_blocking=True)
+                uploaded.record()
+                x = torch.zeros(k, 3, hn, wn, device=dev, dtype=torch.float32)
+                ops.yuv_to_rgb(yuv, fmt, out=x)            # straight into the padded model input
+                del yuv
+                yield x
+
+        per_chunk = max(1, math.ceil(chunk_pairs * fps_o / fps_in))
+        ybuf = torch.empty(per_chunk, fmt_out.frame_bytes, device=dev, dtype=torch.uint8)
+        pin_out = torch.empty(per_chunk, fmt_out.frame_bytes, dtype=torch.uint8).pin_memory()
+        writer = y4m.Y4MWriter(dst, fmt_out, fps_o, reader.extra_tags, reader.interlace, reader.aspect,
+                               reader.range_tagged)
+        try:
+            def flush(k):
+                pin_out[:k].copy_(ybuf[:k], non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                host = pin_out.numpy()
+                for j in range(k):
+                    writer.write(host[j])
+
+            k = 0
+            for frame in _render_chunks(model, chunks(), h, w, fps_in, fps_o, (OH, OW)):
+                ops.rgb_to_yuv(frame[None], fmt_out, out=ybuf[k:k + 1])   # the crop, converted in place
+                del frame
+                k += 1
+                if k == per_chunk:
+                    flush(k)
+                    k = 0
+            if k:
+                flush(k)
+            return reader.frames_read, writer.frames_written
+        finally:
+            writer.close()
+    finally:
+        reader.close()
