@@ -461,6 +461,42 @@ def upsample_bilinear(x, s, dtype=np.float64):
     return top * lh0[:, None] + bot * lh1[:, None]
 
 
+def decode_stage2(feat, inp, hrfeat, flow, t, sd, HH, WW, dtype=np.float64, img=None):
+    """Stage 2 of the decoder on its own (Sakuya_arch_test.py:424-457, warplayer.py:25-39): from given
+    ``hrfeat`` [B,HH,WW,64] (stage 1's HRfeat), ``flow`` [B,HH,WW,4] (stage 1's flow, in HR pixels: x1, y1, x2, y2)
+    and a time per item ``t`` [B], the two warped grids -- torch.linspace base + flow / ((n - 1) / 2), clamped to
+    +-(1 - 1e-6) -- the bilinear gathers (zero padding) of HRfeat, the latent and the image at them, and
+    encode_imnet on the 525 inputs -> [B,3,HH,WW].  feat [B,3,64,H,W] (or [B,192,H,W]), inp [B,2,3,H,W] (or
+    [B,6,H,W]); ``img``: decoding_test's HRinp [B,6,sH,sW], sampled instead of ``inp``.  ``_decode`` ends in it."""
+    B = feat.shape[0]
+    H, W = feat.shape[-2:]
+    featc = np.asarray(feat, dtype).reshape(B, 192, H, W)          # cat(feat[:,0..2]) (:365)
+    img = np.asarray(inp, dtype).reshape(B, 6, H, W) if img is None else np.asarray(img, dtype)
+    lo, hi = F32(-1 + 1e-6), F32(1 - 1e-6)
+    Q = HH * WW
+    qy = np.repeat(np.arange(HH), WW)
+    qx = np.tile(np.arange(WW), HH)
+    gxs, gys = linspace_f32(WW), linspace_f32(HH)                     # warpgrid base (warplayer.py:27-31)
+    hr_img = np.asarray(hrfeat, dtype).reshape(B, Q, 64).transpose(0, 2, 1).reshape(B, 64, HH, WW)
+    flow = np.asarray(flow, dtype).reshape(B, Q, 4)
+    pe = np.broadcast_to(np.asarray(t, dtype).reshape(-1, 1, 1), (B, Q, 1))
+    fx = flow[..., [0, 2]]
+    fy = flow[..., [1, 3]]
+    # warpgrid (warplayer.py:25-39): base linspace grid + flow / ((n-1)/2); then clamp (:428,441)
+    bx = gxs[qx].astype(dtype)[None]
+    by = gys[qy].astype(dtype)[None]
+    feats = []
+    imgs = []
+    for k in range(2):
+        g_x = np.clip(bx + fx[..., k] / ((WW - 1.0) / 2.0), lo, hi)
+        g_y = np.clip(by + fy[..., k] / ((HH - 1.0) / 2.0), lo, hi)
+        feats.append((bilinear_sample(hr_img, g_x, g_y, dtype), bilinear_sample(featc, g_x, g_y, dtype)))
+        imgs.append(bilinear_sample(img, g_x, g_y, dtype))
+    x3 = np.concatenate([feats[0][0], feats[1][0], feats[0][1], feats[1][1], imgs[0], imgs[1], pe], -1)  # 525
+    pred = siren(x3, sd, "encode_imnet.", 4, dtype)                # (:456)
+    return np.ascontiguousarray(pred.transpose(0, 2, 1).reshape(B, 3, HH, WW))
+
+
 def _decode(feat, inp, times, sd, HH, WW, dtype, capture=None, img=None, shift=None):
     """The decoder body shared by decoding / decoding_test / decoding_fasttest /
     decoding_localensemble (Sakuya_arch_test.py:364-459, 461-598, 863-1085).
@@ -500,13 +536,11 @@ def _decode(feat, inp, times, sd, HH, WW, dtype, capture=None, img=None, shift=N
     # nearest HR pixel of the (shifted) query: identity without a shift (:406-409)
     hy = np.clip(nearest_index(sy, HH), 0, HH - 1)
     hx = np.clip(nearest_index(sx, WW), 0, WW - 1)
-    gxs, gys = linspace_f32(WW), linspace_f32(HH)                     # warpgrid base (warplayer.py:27-31)
     preds = []
     for t in times:
         pe = np.full((B, Q, 1), t, dtype)
         x1 = np.concatenate([q_feat, q_inp, rel, pe], -1)             # 201 (:399)
         hrfeat = siren(x1, sd, "feat_imnet.", 3, dtype)               # [B,Q,64] (:400)
-        hr_img = hrfeat.transpose(0, 2, 1).reshape(B, 64, HH, WW)
         q_hr = hrfeat[:, hy[qy] * WW + hx[qx]]
         q_inp2 = bilinear_sample(img, gx, gy, dtype)                  # (:410-413)
         q_feat0 = bilinear_sample(featc, gx, gy, dtype)               # (:414-417)
@@ -514,21 +548,8 @@ def _decode(feat, inp, times, sd, HH, WW, dtype, capture=None, img=None, shift=N
         if capture is not None:
             capture.setdefault("hrfeat", []).append(hrfeat)
             capture.setdefault("flow", []).append(flow)
-        fx = flow[..., [0, 2]]
-        fy = flow[..., [1, 3]]
-        # warpgrid (warplayer.py:25-39): base linspace grid + flow / ((n-1)/2); then clamp (:428,441)
-        bx = gxs[qx].astype(dtype)[None]
-        by = gys[qy].astype(dtype)[None]
-        feats = []
-        imgs = []
-        for k in range(2):
-            g_x = np.clip(bx + fx[..., k] / ((WW - 1.0) / 2.0), lo, hi)
-            g_y = np.clip(by + fy[..., k] / ((HH - 1.0) / 2.0), lo, hi)
-            feats.append((bilinear_sample(hr_img, g_x, g_y, dtype), bilinear_sample(featc, g_x, g_y, dtype)))
-            imgs.append(bilinear_sample(img, g_x, g_y, dtype))
-        x3 = np.concatenate([feats[0][0], feats[1][0], feats[0][1], feats[1][1], imgs[0], imgs[1], pe], -1)  # 525
-        pred = siren(x3, sd, "encode_imnet.", 4, dtype)                # (:456)
-        preds.append(pred.transpose(0, 2, 1).reshape(B, 3, HH, WW))
+        preds.append(decode_stage2(featc, inpc, hrfeat.reshape(B, HH, WW, 64), flow.reshape(B, HH, WW, 4),
+                                   np.full(B, t, dtype), sd, HH, WW, dtype, img=img))      # (:424-457)
     return preds, area
 
 

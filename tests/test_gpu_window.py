@@ -16,6 +16,9 @@ GRIDS = [(37, 45), (64, 80)]                 # non-integer scale with nearest-in
 # flow_imnet's last layer is used as make_state_dict(seed=0) gives it (factor 1): warpgrid's linspace base sits up
 # to half a pixel off the pixel centre, so the gathers leave an interior window by a pixel even for small flows
 FLOW_SCALE = 1.0
+# the same layer times 64: flows up to about 4 HR pixels (make_state_dict's last flow layer is U(+-0.005) over 256
+# sines plus a +-0.05 bias), so the F rectangle is set by the flows and not by the half-pixel base offset
+LARGE_FLOW_SCALE = 64.0
 
 
 def windows(HH, WW):
@@ -39,10 +42,10 @@ WNAMES = sorted(windows(37, 45))
 class Lat:
     """One model per operand mode with the shared latent, and its full-frame decodes (computed once)."""
 
-    def __init__(self, stif, sd, mode):
+    def __init__(self, stif, sd, mode, flow_scale=FLOW_SCALE):
         sd = dict(sd)
         for k in ("flow_imnet.net.3.weight", "flow_imnet.net.3.bias"):
-            sd[k] = (np.asarray(sd[k]) * F32(FLOW_SCALE)).astype(F32)
+            sd[k] = (np.asarray(sd[k]) * F32(flow_scale)).astype(F32)
         self.sd = sd
         self.m = stif.LunaTokis(64, 6, 8, 5, 40, mfma=mode)
         self.m.load_state_dict(sd, strict=True)
@@ -68,10 +71,10 @@ class Lat:
 def lats(stif, sd):
     cache = {}
 
-    def get(mode):
-        if mode not in cache:
-            cache[mode] = Lat(stif, sd, mode)
-        return cache[mode]
+    def get(mode, flow_scale=FLOW_SCALE):
+        if (mode, flow_scale) not in cache:
+            cache[mode, flow_scale] = Lat(stif, sd, mode, flow_scale)
+        return cache[mode, flow_scale]
     return get
 
 
@@ -82,7 +85,10 @@ CASES = [("decoding", g) for g in GRIDS] + [("decoding_test", (64, 80))]
 @pytest.mark.parametrize("kind,grid", CASES, ids=[f"{k}-{g[0]}x{g[1]}" for k, g in CASES])
 @pytest.mark.parametrize("mode", ["f16x3", "f32"])
 def test_window_is_the_crop_of_the_full_decode(lats, mode, kind, grid, wname):
-    la = lats(mode)
+    crop_of_the_full_decode(lats(mode), mode, kind, grid, wname)
+
+
+def crop_of_the_full_decode(la, mode, kind, grid, wname):
     y0, x0, hh, ww = windows(*grid)[wname]
     full = la.full_frame(kind, grid)
     got = la.decode(kind, grid, window=(y0, x0, hh, ww))
@@ -94,6 +100,25 @@ def test_window_is_the_crop_of_the_full_decode(lats, mode, kind, grid, wname):
         assert tuple(g.shape) == (2, 3, hh, ww)
         assert torch.equal(g, f[:, :, y0:y0 + hh, x0:x0 + ww]), (mode, kind, grid, wname, la.m.last_window_F)
     assert la.m.range_reruns == 0
+
+
+@pytest.mark.parametrize("wname", ["interior", "top_left", "bottom_right", "sub_wave", "three_workgroups"])
+@pytest.mark.parametrize("grid", GRIDS, ids=[f"{g[0]}x{g[1]}" for g in GRIDS])
+@pytest.mark.parametrize("mode", ["f16x3", "f32"])
+def test_window_is_the_crop_of_the_full_decode_with_large_flows(lats, mode, grid, wname):
+    """The same bit-for-bit equality on a latent whose flows really leave the window (flow_imnet's last layer times
+    LARGE_FLOW_SCALE): the interior window's F rectangle exceeds it by 3 pixels or more on some side, so the
+    data-dependent feat-only pass over F and stage 2's gathers rows away from their pixel are what is compared.
+    (Large flows against the oracle: tests/test_gpu_decoder_stages.py.)"""
+    la = lats(mode, LARGE_FLOW_SCALE)
+    crop_of_the_full_decode(la, mode, "decoding", grid, wname)
+    if wname == "interior":
+        y0, x0, hh, ww = windows(*grid)[wname]
+        fy0, fx0, fh, fw = la.m.last_window_F
+        grown = (y0 - fy0, x0 - fx0, fy0 + fh - (y0 + hh), fx0 + fw - (x0 + ww))
+        print("large flows", mode, grid, "interior window", (y0, x0, hh, ww), "last_window_F", la.m.last_window_F,
+              "grown by (top, left, bottom, right)", grown)
+        assert max(grown) >= 3, (la.m.last_window_F, grown)
 
 
 @pytest.mark.parametrize("mode", ["f16x3", "f32"])

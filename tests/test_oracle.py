@@ -255,3 +255,93 @@ def test_chunked_dcn_shim_equals_unchunked_and_oracle():
     ref = O.dcn_v2_forward(inp.numpy().astype(np.float64), wt.numpy().astype(np.float64), bs.numpy().astype(np.float64),
                            off.numpy(), m.numpy(), 3, 3, 1, 1, 1, 1, 1, 1, dg)
     assert np.abs(b.numpy() - ref).max() <= 1e-5 * scale
+
+
+# ----------------------------------------------------------------------------- decoder stage 2 on its own
+def _stage2_case(kind, HH=37, WW=45):
+    import stage2_inputs as S
+    feat, inp = S.latent(2, 16, 20)
+    return feat, inp, S.hrfeat(2, HH, WW), S.flows(kind, 2, HH, WW), np.array([0.3, 0.7], np.float32)
+
+
+def _replicate_sample(img, gx, gy, dtype=np.float64):
+    """O.bilinear_sample with the out-of-range corners replicated from the border instead of zero."""
+    B, C, H, W = img.shape
+    ix = ((np.asarray(gx, dtype) + 1) * W - 1) / 2
+    iy = ((np.asarray(gy, dtype) + 1) * H - 1) / 2
+    x0, y0 = np.floor(ix), np.floor(iy)
+    flat = np.asarray(img, dtype).reshape(B, C, H * W).transpose(0, 2, 1)
+    b = np.arange(B)[:, None]
+    out = 0
+    for xx, yy, ww in ((x0, y0, (x0 + 1 - ix) * (y0 + 1 - iy)), (x0 + 1, y0, (ix - x0) * (y0 + 1 - iy)),
+                       (x0, y0 + 1, (x0 + 1 - ix) * (iy - y0)), (x0 + 1, y0 + 1, (ix - x0) * (iy - y0))):
+        idx = np.clip(yy.astype(np.int64), 0, H - 1) * W + np.clip(xx.astype(np.int64), 0, W - 1)
+        out = out + flat[b, idx] * ww[..., None]
+    return out
+
+
+STAGE2_MUTANTS = ["divisor_n_over_2", "replicate_padding", "pixel_centre_base", "xy_swapped", "grids_swapped"]
+
+
+@pytest.mark.parametrize("kind", ["uniform", "huge"])
+def test_stage2_inputs_tell_a_wrong_stage2_from_a_right_one(sd, monkeypatch, kind):
+    """The synthetic inputs of the GPU stage-2 tests discriminate: with several-pixel (uniform) or edge-clamped
+    (huge) flows, each of five wrong restatements of stage 2 -- divisor n/2 for (n-1)/2, replicate for zero
+    padding, a pixel-centre warp base for torch.linspace, flow x/y swapped, the two grids swapped -- breaks the
+    project's oracle bound |d| <= 1e-4 |ref| + 1e-6 by at least 10x at a pixel 4 or more away from the border.
+    (With the sub-pixel flows of make_state_dict's initialisation an interior pixel never sees the zero padding.)
+    About the reference and the inputs only: nothing of the kernels is asked."""
+    import stage2_inputs as S
+    HH, WW = 37, 45
+    feat, inp, hrf, flow, t = _stage2_case(kind, HH, WW)
+    ref = O.decode_stage2(feat, inp, hrf, flow, t, sd, HH, WW)
+    assert ref.shape == (2, 3, HH, WW) and np.isfinite(ref).all()
+    worst = {}
+    for name in STAGE2_MUTANTS:
+        f = flow
+        with monkeypatch.context() as mp:
+            if name == "divisor_n_over_2":       # flow / (n / 2) = (flow (n - 1) / n) / ((n - 1) / 2)
+                f = (flow.astype(np.float64) * np.array([(WW - 1) / WW, (HH - 1) / HH] * 2)).astype(np.float32)
+            elif name == "replicate_padding":
+                mp.setattr(O, "bilinear_sample", _replicate_sample)
+            elif name == "pixel_centre_base":
+                mp.setattr(O, "linspace_f32", O.make_coord_1d)
+            elif name == "xy_swapped":
+                f = np.ascontiguousarray(flow[..., [1, 0, 3, 2]])
+            else:
+                f = np.ascontiguousarray(flow[..., [2, 3, 0, 1]])
+            mut = O.decode_stage2(feat, inp, hrf, f, t, sd, HH, WW)
+        worst[name] = float(S.bound_ratio(mut, ref)[:, :, 4:HH - 4, 4:WW - 4].max())
+    print(kind, {k: round(v, 1) for k, v in worst.items()})
+    assert min(worst.values()) >= 10, worst
+    assert np.array_equal(O.decode_stage2(feat, inp, hrf, flow, t, sd, HH, WW), ref)     # the patches are undone
+
+
+@pytest.mark.parametrize("grid", [(37, 45), (64, 80)], ids=["37x45", "64x80"])
+def test_stage2_edge_and_integer_flows_are_what_they_claim(grid):
+    """In the kernel's fp32 arithmetic the `edge` flows put grids exactly on +-(1 - 1e-6), one ulp inside it and
+    outside it (clamped), and the `integer` flows are whole pixels; `huge` clamps on both sides."""
+    import stage2_inputs as S
+    HH, WW = grid
+    g = S.warped_grid_f32(S.flows("edge", 2, HH, WW), HH, WW)[0]
+    for v in (S.HI, S.HI_IN, S.LO, S.LO_IN):
+        assert (g == v).sum() > 50, (v, int((g == v).sum()))
+    assert (g > S.HI).sum() > 50 and (g < S.LO).sum() > 50
+    f = S.flows("integer", 2, HH, WW)
+    assert np.array_equal(f, np.rint(f)) and np.abs(f).max() >= 3
+    g = S.warped_grid_f32(S.flows("huge", 2, HH, WW), HH, WW)[0]
+    assert (g > 1).mean() > 0.05 and (g < -1).mean() > 0.05
+    assert np.array_equal(S.linspace_f32(WW), O.linspace_f32(WW)) and np.array_equal(S.linspace_f32(HH), O.linspace_f32(HH))
+
+
+@pytest.mark.parametrize("kind", ["uniform", "huge", "integer", "edge"])
+def test_stage2_oracle_in_fp32_is_within_the_bound(sd, kind):
+    """The room the bound leaves: the same restatement run in fp32 stays inside |d| <= 1e-4 |ref| + 1e-6 of the
+    fp64 run on every input kind (the grids differ by an fp32 rounding, the bilinear gathers are continuous)."""
+    import stage2_inputs as S
+    feat, inp, hrf, flow, t = _stage2_case(kind)
+    ref = O.decode_stage2(feat, inp, hrf, flow, t, sd, 37, 45)
+    r32 = O.decode_stage2(feat, inp, hrf, flow, t, sd, 37, 45, dtype=np.float32)
+    ratio = float(S.bound_ratio(r32, ref).max())
+    print(kind, "fp32 oracle / bound:", ratio)
+    assert ratio <= 1.0
