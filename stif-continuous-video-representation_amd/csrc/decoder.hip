@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdio>
+#include <type_traits>
 
 namespace {
 
@@ -136,6 +137,22 @@ STIF_DEV Bilin bilin(float gx, float gy, int Wd, int Hd) {
   return b;
 }
 
+// The corners of the HR pixel centre (row py, column px of the virtual grid) in a map `pitch` pixels wide, from the
+// host's per-row / per-column tables (stif_dec_tables or stif_dec_image: by0 .. wx1)
+template <class TAB>
+STIF_DEV Bilin bilin_tab(const TAB& tb, int py, int px, int pitch) {
+  Bilin b;
+  // the table pointers as locals first: indexing tb.by0[py] .. directly compiles to the same code but for one
+  // commuted v_add_u32 in 12 of the k_dec1 kernels, and this form keeps them instruction for instruction
+  const int *by0 = tb.by0, *by1 = tb.by1, *bx0 = tb.bx0, *bx1 = tb.bx1;
+  const float *wy0_ = tb.wy0, *wy1_ = tb.wy1, *wx0_ = tb.wx0, *wx1_ = tb.wx1;
+  const int y0 = by0[py], y1 = by1[py], x0 = bx0[px], x1 = bx1[px];
+  const float wy0 = wy0_[py], wy1 = wy1_[py], wx0 = wx0_[px], wx1 = wx1_[px];
+  b.o00 = y0 * pitch + x0; b.o01 = y0 * pitch + x1; b.o10 = y1 * pitch + x0; b.o11 = y1 * pitch + x1;
+  b.w00 = wx0 * wy0; b.w01 = wx1 * wy0; b.w10 = wx0 * wy1; b.w11 = wx1 * wy1;
+  return b;
+}
+
 // Stage 2's two warped grids of one HR pixel: warpgrid (warplayer.py:25-39) = linspace base + flow / ((n - 1) / 2)
 // over the virtual WW x HH grid, then the decoder's clamp to (-1 + 1e-6, 1 - 1e-6) (Sakuya_arch_test.py:428,441).
 // The HRfeat corners stage 2 reads are bilin_corners(g, WW, HH) of these; k_dec_bounds reduces the box of the same
@@ -182,92 +199,38 @@ STIF_DEV Bilin bilin_hr(float gx, float gy, int WW, int HH, const stif_dec_windo
   }
 }
 
-// bilinear sample of channel block [c0, c0+64) of an NHWC map with `stride` channels,
-// into two register tiles (features F(r, hf) of each 32-block)
+// bilinear sample of channel block [c0, c0+64) of an NHWC map with `stride` channels, into two register tiles
+// (features F(r, hf) of each 32-block).  The 8 channel groups (4 corner loads, 16 VGPRs each) are loaded GPB at a
+// time, all of a batch before its first blend: 8 / GPB memory latencies at 16 GPB VGPRs of loads in flight.
+template <int GPB>
 STIF_DEV void gather64(f32x16* dst, const float* __restrict__ base, int stride, int c0, const Bilin& b, int hf) {
-  // all 32 corner loads (8 channel groups x 4 corners, 128 VGPRs) are issued before the first blend,
-  // so a gather waits for one memory latency, not one per channel group
-  const int c = c0 + 4 * hf;
-  const float* p00 = base + (size_t)b.o00 * stride + c;
-  const float* p01 = base + (size_t)b.o01 * stride + c;
-  const float* p10 = base + (size_t)b.o10 * stride + c;
-  const float* p11 = base + (size_t)b.o11 * stride + c;
-  f32x4 cr[8][4];
-#pragma unroll
-  for (int g = 0; g < 8; ++g) {   // group g = (ot, v) = (g >> 2, g & 3): channels 8 g + 4 hf ..
-    cr[g][0] = ld4(p00 + 8 * g);
-    cr[g][1] = ld4(p01 + 8 * g);
-    cr[g][2] = ld4(p10 + 8 * g);
-    cr[g][3] = ld4(p11 + 8 * g);
-  }
-#pragma unroll
-  for (int g = 0; g < 8; ++g) {
-    f32x4 s = b.w00 * cr[g][0] + b.w01 * cr[g][1] + b.w10 * cr[g][2] + b.w11 * cr[g][3];
-    // combine the corners here, in load order: otherwise the blend is sunk to the first use (past a
-    // barrier) and all four corners of every channel stay live
-    asm volatile("" : "+v"(s));
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dst[g >> 2][4 * (g & 3) + e] = s[e];
-  }
-}
-
-// gather64 with at most 8 corner loads (32 VGPRs) in flight: four memory latencies
-STIF_DEV void gather64_q(f32x16* dst, const float* __restrict__ base, int stride, int c0, const Bilin& b, int hf) {
   const int c = c0 + 4 * hf;
   const float* p00 = base + (size_t)b.o00 * stride + c;
   const float* p01 = base + (size_t)b.o01 * stride + c;
   const float* p10 = base + (size_t)b.o10 * stride + c;
   const float* p11 = base + (size_t)b.o11 * stride + c;
 #pragma unroll
-  for (int qr = 0; qr < 4; ++qr) {
-    f32x4 cr[2][4];
+  for (int g0 = 0; g0 < 8; g0 += GPB) {
+    f32x4 cr[GPB][4];
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const int o = 8 * (2 * qr + g);
+    for (int g = 0; g < GPB; ++g) {   // group g0 + g = (ot, v) = (>> 2, & 3): channels 8 (g0 + g) + 4 hf ..
+      const int o = 8 * (g0 + g);
       cr[g][0] = ld4(p00 + o);
       cr[g][1] = ld4(p01 + o);
       cr[g][2] = ld4(p10 + o);
       cr[g][3] = ld4(p11 + o);
     }
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
+    for (int g = 0; g < GPB; ++g) {
       f32x4 s = b.w00 * cr[g][0] + b.w01 * cr[g][1] + b.w10 * cr[g][2] + b.w11 * cr[g][3];
+      // combine the corners here, in load order: otherwise the blend is sunk to the first use (past a
+      // barrier) and all four corners of every channel stay live
       asm volatile("" : "+v"(s));
-      const int gg = 2 * qr + g;
+      const int gg = g0 + g;
 #pragma unroll
       for (int e = 0; e < 4; ++e) dst[gg >> 2][4 * (gg & 3) + e] = s[e];
     }
-    asm volatile("" ::: "memory");
-  }
-}
-
-// gather64 with at most 16 corner loads (64 VGPRs) in flight: two memory latencies instead of one, for
-// kernels budgeted below the 128 VGPRs of the one-shot form
-STIF_DEV void gather64_h(f32x16* dst, const float* __restrict__ base, int stride, int c0, const Bilin& b, int hf) {
-  const int c = c0 + 4 * hf;
-  const float* p00 = base + (size_t)b.o00 * stride + c;
-  const float* p01 = base + (size_t)b.o01 * stride + c;
-  const float* p10 = base + (size_t)b.o10 * stride + c;
-  const float* p11 = base + (size_t)b.o11 * stride + c;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    f32x4 cr[4][4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int o = 8 * (4 * half + g);
-      cr[g][0] = ld4(p00 + o);
-      cr[g][1] = ld4(p01 + o);
-      cr[g][2] = ld4(p10 + o);
-      cr[g][3] = ld4(p11 + o);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 s = b.w00 * cr[g][0] + b.w01 * cr[g][1] + b.w10 * cr[g][2] + b.w11 * cr[g][3];
-      asm volatile("" : "+v"(s));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[half][4 * g + e] = s[e];
-    }
-    asm volatile("" ::: "memory");
+    if constexpr (GPB < 8) asm volatile("" ::: "memory");   // the next batch's loads stay behind this one's blends
   }
 }
 
@@ -289,12 +252,53 @@ STIF_DEV f32x4 img_sample(const float* __restrict__ I, const Bilin& b, int hf) {
          b.w11 * ld4(c + b.o11 * IMG_C);
 }
 
+// The HR pixel a lane works on, in workgroups of NW waves at PPW pixels per wave (lane & (PPW - 1): the other lanes
+// hold the same pixels).  The pixels are counted over the whole HH x WW grid or, WIN, over win's query rectangle
+// (row-major per item); lanes past the end redo the last pixel and store nothing (valid).
+struct Pixel {
+  bool valid;
+  long long pc;     // index among all n * rows * columns pixels
+  int item, ly, lx; // item, row and column in the grid / rectangle
+};
+template <int NW, int PPW, bool WIN>
+STIF_DEV Pixel pixel_of(int wv, int lane, int n, int HH, int WW, const stif_dec_window& win) {
+  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
+  const long long total = (long long)n * GH * GW;
+  const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW + wv) * PPW + (lane & (PPW - 1));
+  Pixel o;
+  o.valid = p < total;
+  o.pc = o.valid ? p : total - 1;
+  o.item = (int)(o.pc / ((long long)GH * GW));
+  const int rem = (int)(o.pc - (long long)o.item * GH * GW);
+  o.ly = rem / GW, o.lx = rem - o.ly * GW;
+  return o;
+}
+
+// Stage 2's epilogue: the pixel's RGB (o4 + bias) into the NCHW output -- WIN: through win's output addressing --
+// and, REPORT, the range report.  Stage 1's flow counts too: the warpgrid clamp maps a NaN flow to a finite grid,
+// so an out-of-range flow_imnet operand would otherwise leave a finite but wrong pixel.
+template <bool WIN, bool REPORT>
+STIF_DEV void store_rgb(float* __restrict__ out, const float* __restrict__ mlp, const float* o4, const f32x4 fv,
+                        int item, int py, int px, int HH, int WW, const stif_dec_window& win, int* status) {
+  const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
+  float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
+                 : out + (size_t)item * 3 * plane + (size_t)py * WW + px;
+  bool bad = not_finite((fv[0] + fv[1]) + (fv[2] + fv[3]));
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v = o4[c] + mlp[E_B4 + c];
+    bad |= not_finite(v);
+    o[c * plane] = v;
+  }
+  if constexpr (REPORT) report_range_w<WIN>(status, bad);
+}
+
 // ---- weight streaming: a workgroup consumes its MLP weight tiles segment by segment; each segment
 // (a few 4-KB tiles: one layer, or one output tile's K-tiles) is LDS-DMA'd while the previous one
 // is being consumed (double-buffered, one barrier per segment), and every wave reads its A
 // operands from LDS -- one tile feeds 16 MFMAs in each wave of the workgroup.
-// waves per workgroup of k_dec1: 4-wave workgroups, DEC1_OCC per CU -- by default 4 (36 KB LDS, <= 128 VGPRs
-// each; the HRIMG variants stay at 3: 52 KB, <= 168, and MODE 2 at 2: 69 KB): the waves sharing a SIMD come from different
+// waves per workgroup of k_dec1: 4-wave workgroups, OCC1 (below) of them per CU -- 4 (36 KB LDS, <= 128 VGPRs
+// each; the HRIMG variants 3: 52 KB, <= 168, and MODE 2 2: 69 KB): the waves sharing a SIMD come from different
 // workgroups, so one's segment barrier, gather or sin stretch overlaps the others' MFMAs
 constexpr int NW1 = 4;       // k_dec1 (8-wave workgroups at four waves per SIMD: +8 %, profiles/r06_dec_ab.log)
 constexpr int DEC2_NW = 4;   // k_dec2: 8 layer-3 accumulator tiles (128 VGPRs) live
@@ -371,13 +375,15 @@ STIF_DEV void narrow_dot(float* o, const float* W, int kt, const f32x16& x, int 
 // MODE 0: feat_imnet + flow_imnet fused (the flow stage reads the pixel's own HRfeat);
 // MODE 1: feat_imnet only; MODE 2: flow_imnet only, reading HRfeat at (hr_y, hr_x) of the query
 // (local ensemble).  HRIMG: the flow stage's image input comes from the high-resolution image.
-// DEC1_OCC = 3 (MODE 0 / 1): 6-tile segments (52 KB of LDS) and a 168-register budget, so three workgroups
-// (three waves per SIMD) share a CU; flow layer 1's second output tile then arrives after the last feat step
-// DEC1_OCC = 4: 4-tile segments (36 KB) and 128 registers; flow layer 1 then arrives after the last feat
-// step and flow segment 0 after flow layer 0
-// (the HRIMG variants, decoding_test's, stay at 3: at 128 registers their image gather spills)
+// OCC1, the workgroups per CU a k_dec1 instantiation is laid out for:
+// 4 (MODE 0 / 1): 4-tile segments (36 KB of LDS) and 128 registers; flow layer 1 arrives after the last feat step
+//   and flow segment 0 after flow layer 0.  C0 dec1 869 -> 758 us (2 -> 3, profiles/r04_dec1_occ_ab.log) -> 720 us
+//   (3 -> 4; C2 11.6 -> 11.1 ms, profiles/r04_dec1_occ4_ab.log), all bit-identical
+// 3 (the HRIMG variants, decoding_test's: at 128 registers their image gather spills): 6-tile segments (52 KB) and
+//   a 168-register budget; flow layer 1's second output tile arrives after the last feat step
+// 2 (MODE 2): 8-tile segments (69 KB), 256 registers
 template <int MODE, bool HRIMG>
-constexpr int OCC1 = MODE == 2 ? 2 : (HRIMG && DEC1_OCC > 3) ? 3 : DEC1_OCC;
+constexpr int OCC1 = MODE == 2 ? 2 : HRIMG ? 3 : 4;
 template <int MODE, bool HRIMG>
 constexpr int S1 = OCC1<MODE, HRIMG> == 4 ? 4 : OCC1<MODE, HRIMG> == 3 ? 6 : SEG1;
 // WIN: the pixels are those of win's query rectangle (row-major, hh x ww per item); the tables are read at the
@@ -407,15 +413,12 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
     dma_tiles<NW1>(B1, rm, L_W0, 4, wv, lane);
     dma_tiles<NW1>(B1 + 4 * T, rm, L_W1, 4, wv, lane);
   }
-  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
-  const long long total = (long long)n * GH * GW;
-  const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW1 + wv) * 32 + (lane & 31);
-  const bool valid = p < total;
-  const long long pc = valid ? p : total - 1;
-  const int item = (int)(pc / ((long long)GH * GW));
-  const int rem = (int)(pc - (long long)item * GH * GW);
-  const int ly = rem / GW, lx = rem - ly * GW;
-  const int py = WIN ? win.y0 + ly : ly, px = WIN ? win.x0 + lx : lx;   // row / column of the virtual grid
+  const Pixel pix = pixel_of<NW1, 32, WIN>(wv, lane, n, HH, WW, win);
+  const bool valid = pix.valid;
+  const long long pc = pix.pc;
+  const int item = pix.item;
+  // row / column of the virtual grid
+  const int py = WIN ? win.y0 + pix.ly : pix.ly, px = WIN ? win.x0 + pix.lx : pix.lx;
   const float t = tq[item];
   const float* P = proj + (size_t)item * h * w * PROJ_C;
 
@@ -511,20 +514,18 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
     b.o00 = b.o01 = b.o10 = b.o11 = tb.hr_y[py] * WW + tb.hr_x[px];
     b.w00 = 1.f;
     b.w01 = b.w10 = b.w11 = 0.f;
-    gather64(hr, hrfeat + (size_t)item * HH * WW * 64, 64, 0, b, hf);
+    gather64<8>(hr, hrfeat + (size_t)item * HH * WW * 64, 64, 0, b, hf);
   }
 
   // ---- flow_imnet layer 0: W[:, :64] . HRfeat + bilinear(P2 at the HR centre) + w_t * t + b
   f32x16 z[2];
   {
-    Bilin b;
-    const int y0 = tb.by0[py], y1 = tb.by1[py], x0_ = tb.bx0[px], x1_ = tb.bx1[px];
-    const float wy0 = tb.wy0[py], wy1 = tb.wy1[py], wx0 = tb.wx0[px], wx1 = tb.wx1[px];
-    b.o00 = y0 * w + x0_; b.o01 = y0 * w + x1_; b.o10 = y1 * w + x0_; b.o11 = y1 * w + x1_;
-    b.w00 = wx0 * wy0; b.w01 = wx1 * wy0; b.w10 = wx0 * wy1; b.w11 = wx1 * wy1;
-    if (OCC4) gather64_q(z, P, PROJ_C, 64, b, hf);
-    else if (OCC3) gather64_h(z, P, PROJ_C, 64, b, hf);
-    else gather64(z, P, PROJ_C, 64, b, hf);
+    const Bilin b = bilin_tab(tb, py, px, w);
+    // loads in flight sized to the register budget: 8 corner loads (32 VGPRs, four memory latencies) at 128
+    // registers, 16 (64 VGPRs, two latencies) at 168, all 32 (128 VGPRs, one latency) at 256
+    if (OCC4) gather64<2>(z, P, PROJ_C, 64, b, hf);
+    else if (OCC3) gather64<4>(z, P, PROJ_C, 64, b, hf);
+    else gather64<8>(z, P, PROJ_C, 64, b, hf);
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
@@ -535,11 +536,7 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
         for (int e = 0; e < 4; ++e) z[ot][4 * v + e] = (z[ot][4 * v + e] + (wt[e] * t + bb[e])) * ACC_IN<F16>;
       }
     if constexpr (HRIMG) {   // q_inp from the high-resolution image (decoding_test :515-518)
-      Bilin bi;
-      const int y0 = im.by0[py], y1 = im.by1[py], x0_ = im.bx0[px], x1_ = im.bx1[px];
-      const float wy0 = im.wy0[py], wy1 = im.wy1[py], wx0 = im.wx0[px], wx1 = im.wx1[px];
-      bi.o00 = y0 * im.iw + x0_; bi.o01 = y0 * im.iw + x1_; bi.o10 = y1 * im.iw + x0_; bi.o11 = y1 * im.iw + x1_;
-      bi.w00 = wx0 * wy0; bi.w01 = wx1 * wy0; bi.w10 = wx0 * wy1; bi.w11 = wx1 * wy1;
+      const Bilin bi = bilin_tab(im, py, px, im.iw);
       img_mma(z, mlp + I_L, img_sample(im.img + (size_t)item * im.ih * im.iw * IMG_C, bi, hf), lane);
     }
   }
@@ -628,14 +625,9 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   // segments: [L0: 8 tiles] [L1: 4] then per layer-2 tile kt: [W2 rows kt (2) + W3 column kt (8)],
   // then [W4: 8]
   dma_tiles<DEC2_NW>(B0, rm, E_W0, 8, wv, lane);
-  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
-  const long long total = (long long)n * GH * GW;
-  const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * DEC2_NW + wv) * 32 + (lane & 31);
-  const bool valid = p < total;
-  const long long pc = valid ? p : total - 1;
-  const int item = (int)(pc / ((long long)GH * GW));
-  const int rem = (int)(pc - (long long)item * GH * GW);
-  const int py = rem / GW, px = rem - py * GW;
+  const Pixel pix = pixel_of<DEC2_NW, 32, WIN>(wv, lane, n, HH, WW, win);
+  const long long pc = pix.pc;
+  const int item = pix.item, py = pix.ly, px = pix.lx;   // row / column in the rectangle
   const float t = tq[item];
   const float* P = proj + (size_t)item * h * w * PROJ_C;
   const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
@@ -644,7 +636,6 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   const f32x4 fv = ld4(flow + (size_t)pc * 4);
   const float bx = tb.lin_x[WIN ? win.x0 + px : px], by = tb.lin_y[WIN ? win.y0 + py : py];
   const WarpGrids wg = warp_grids(fv, bx, by, WW, HH);
-  const float g1x = wg.g1x, g1y = wg.g1y, g2x = wg.g2x, g2y = wg.g2y;
 
   // ---- encode_imnet layer 0: W[:, :128] . [q_feat1 | q_feat2] + P3(grid1) + P4(grid2) + w_t t + b
   f32x16 x0[2];
@@ -653,9 +644,9 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
     // at most two 64-wide register tiles are live (2 waves/SIMD fit in 256 VGPRs); the compiler
     // barriers keep it from hoisting the next gather's loads over the current one
     f32x16 z[2], q[2];
-    gather64(z, P, PROJ_C, 128, bilin(g1x, g1y, w, h), hf);
+    gather64<8>(z, P, PROJ_C, 128, bilin(wg.g1x, wg.g1y, w, h), hf);
     asm volatile("" ::: "memory");
-    gather64(q, P, PROJ_C, 192, bilin(g2x, g2y, w, h), hf);
+    gather64<8>(q, P, PROJ_C, 192, bilin(wg.g2x, wg.g2y, w, h), hf);
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
@@ -667,11 +658,11 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
       }
     if constexpr (HRIMG) {   // q_img1 / q_img2 from the high-resolution image (decoding_test :558-583)
       const float* I = im.img + (size_t)item * im.ih * im.iw * IMG_C;
-      img_mma(z, mlp + I_E1, img_sample(I, bilin(g1x, g1y, im.iw, im.ih), hf), lane);
-      img_mma(z, mlp + I_E2, img_sample(I, bilin(g2x, g2y, im.iw, im.ih), hf), lane);
+      img_mma(z, mlp + I_E1, img_sample(I, bilin(wg.g1x, wg.g1y, im.iw, im.ih), hf), lane);
+      img_mma(z, mlp + I_E2, img_sample(I, bilin(wg.g2x, wg.g2y, im.iw, im.ih), hf), lane);
     }
     asm volatile("" ::: "memory");
-    gather64(q, HRF, 64, 0, bilin_hr<WIN>(g1x, g1y, WW, HH, win, status), hf);   // q_feat1 -> W0 columns 0..63
+    gather64<8>(q, HRF, 64, 0, bilin_hr<WIN>(wg.g1x, wg.g1y, WW, HH, win, status), hf);   // q_feat1 -> W0 columns 0..63
     lds_dma_barrier();
     dma_tiles<DEC2_NW>(B1, rm, E_W1, 4, wv, lane);
     {
@@ -682,7 +673,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
         for (int kt = 0; kt < 2; ++kt) tile_mma<F16>(z[ot], B0 + (ot * 4 + kt) * T, qs[kt], lane);
     }
     asm volatile("" ::: "memory");
-    gather64(q, HRF, 64, 0, bilin_hr<WIN>(g2x, g2y, WW, HH, win, status), hf);   // q_feat2 -> W0 columns 64..127
+    gather64<8>(q, HRF, 64, 0, bilin_hr<WIN>(wg.g2x, wg.g2y, WW, HH, win, status), hf);   // q_feat2 -> W0 columns 64..127
     const XT<F16> qs[2] = {xop<F16>(q[0]), xop<F16>(q[1])};
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot) {
@@ -695,12 +686,14 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   lds_dma_barrier();
   const Bias32 eb1[2] = {bias_ld(mlp + E_B1, hf), bias_ld(mlp + E_B1 + 32, hf)};   // before the DMA
   __builtin_amdgcn_sched_barrier(0);
-  auto seg_l23_first = [&](float* dst) {
-    dma_tiles<DEC2_NW>(dst, rm, E_W2, 2, wv, lane);
+  // layer 2 (64 -> 256, sine) is streamed tile by tile into the 8 accumulators of layer 3 (256 -> 256):
+  // segment kt = W2 rows of tile kt (2 tiles) + column kt of W3 (8 tiles)
+  auto seg_l23 = [&](float* dst, int kt) {
+    dma_tiles<DEC2_NW>(dst, rm, E_W2 + kt * 2 * T, 2, wv, lane);
 #pragma unroll
-    for (int ot = 0; ot < 8; ++ot) dma_tiles<DEC2_NW>(dst + (2 + ot) * T, rm, E_W3 + ot * 8 * T, 1, wv, lane);
+    for (int ot = 0; ot < 8; ++ot) dma_tiles<DEC2_NW>(dst + (2 + ot) * T, rm, E_W3 + (ot * 8 + kt) * T, 1, wv, lane);
   };
-  seg_l23_first(B0);
+  seg_l23(B0, 0);
   f32x16 x1[2];
   {
     const XT<F16> xs[2] = {xop<F16>(x0[0]), xop<F16>(x0[1])};
@@ -713,14 +706,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
     }
   }
   const XT<F16> x1s[2] = {xop<F16>(x1[0]), xop<F16>(x1[1])};
-  // layer 2 (64 -> 256, sine) streamed tile by tile into the 8 accumulators of layer 3 (256 -> 256):
-  // segment kt = W2 rows of tile kt (2 tiles) + column kt of W3 (8 tiles)
-  auto seg_l23 = [&](float* dst, int kt) {
-    dma_tiles<DEC2_NW>(dst, rm, E_W2 + kt * 2 * T, 2, wv, lane);
-#pragma unroll
-    for (int ot = 0; ot < 8; ++ot) dma_tiles<DEC2_NW>(dst + (2 + ot) * T, rm, E_W3 + (ot * 8 + kt) * T, 1, wv, lane);
-  };
-  f32x16 a3[8];
+  f32x16 a3[8];   // layer 3's accumulators, fed by the streamed layer-2 tiles (seg_l23)
 #pragma unroll
   for (int ot = 0; ot < 8; ++ot) a3[ot] = f32x16{0};
   auto l23_step = [&](int kt, bool last) {   // kt = 7 peeled (see k_dec1's feat_step)
@@ -752,21 +738,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) o4[c] += __shfl_xor(o4[c], 32);   // the other lane half's 128 features
-  if (valid && hf == 0) {
-    const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
-    float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
-                   : out + (size_t)item * 3 * plane + (size_t)py * WW + px;
-    // stage 1's flow counts too: the warpgrid clamp above maps a NaN flow to a finite grid, so an
-    // out-of-range flow_imnet operand would otherwise leave a finite but wrong pixel
-    bool bad = not_finite((fv[0] + fv[1]) + (fv[2] + fv[3]));
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = o4[c] + mlp[E_B4 + c];
-      bad |= not_finite(v);
-      o[c * plane] = v;
-    }
-    if (F16) report_range_w<WIN>(status, bad);
-  }
+  if (pix.valid && hf == 0) store_rgb<WIN, F16 != 0>(out, mlp, o4, fv, item, py, px, HH, WW, win, status);
 }
 
 
@@ -779,18 +751,15 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
 // four waves per SIMD.
 // Weight streaming (round 6): every workgroup streams the whole 372-KB weight set through its LDS, so the
 // stream is paid once per workgroup; its memory traffic costs ~10 % of the kernel (profiles/r06_dec_probe3.log).
-// Workgroups are DEC2Q_NW waves (8: 128 pixels, two per CU; 16: 256 pixels, one per CU, 27 % slower) and a segment
-// is the layer-2 / -3 weights of DEC2Q_KTS whole layer-2 tiles kt (W2 rows kt + W3 column kt: 10 tiles each),
-// double-buffered in 2 x 40 KB (KTS 1) or 2 x 80 KB (KTS 2): one barrier per kt (or per two).  Every wave issues
-// the same number of LDS-DMA pieces per segment (5), so the compiler's vmcnt bookkeeping stays exact.
+// Workgroups are 8 waves (128 pixels, two per CU; one 16-wave workgroup per CU streaming two layer-2 tiles per
+// segment measured 27 % slower, profiles/r06_dec_ab.log) and a segment is the layer-2 / -3 weights of one layer-2
+// tile kt (W2 rows kt + W3 column kt: 10 tiles), double-buffered in 2 x 40 KB: one barrier per kt.  Every wave
+// issues the same number of LDS-DMA pieces per segment (5), so the compiler's vmcnt bookkeeping stays exact.
 // Gathers: each lane fetches its own quarter of a 64-channel block (16 corner loads in flight).
-constexpr int DEC2Q_NWV = DEC2Q_NW;
-constexpr int KTS = DEC2Q_KTS;            // layer-2 tiles per segment
-constexpr int SEGQ = 10 * KTS;            // tiles per segment
-static_assert(40 * KTS % DEC2Q_NWV == 0 && 32 % DEC2Q_NWV == 0 && 16 % DEC2Q_NWV == 0 && 8 % KTS == 0,
-              "k_dec2q: every wave issues the same number of LDS-DMA pieces");
-static_assert((DEC2Q_NWV == 8 || DEC2Q_NWV == 16) && 2 * SEGQ * T * 4 * (16 / DEC2Q_NWV) <= 160 * 1024,
-              "k_dec2q: 16 waves per CU (four per SIMD) in 8- or 16-wave workgroups, their LDS within 160 KB");
+constexpr int DEC2Q_NW = 8;   // waves per workgroup
+constexpr int SEGQ = 10;      // tiles per segment
+static_assert(SEGQ * 4 % DEC2Q_NW == 0, "k_dec2q: every wave issues the same number of LDS-DMA pieces");
+static_assert(2 * SEGQ * T * 4 * 2 <= 160 * 1024, "k_dec2q: two workgroups per CU, their LDS within 160 KB");
 struct R32 {
   f32x4 s[2];
 };
@@ -854,37 +823,32 @@ STIF_DEV void gather_q(R32* dst, const float* __restrict__ base, int stride, int
 }
 
 template <bool WIN>   // WIN: as k_dec2's
-__global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec2q(
+__global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec2q(
     const float* __restrict__ proj, const float* __restrict__ mlp, const float* __restrict__ hrfeat,
     const float* __restrict__ flow, stif_dec_tables tb, const float* __restrict__ tq, float* __restrict__ out, int n,
     int h, int w, int HH, int WW, int* status, stif_dec_window win) {
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEGQ * T];
   const int lane = threadIdx.x & 63, q = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  constexpr int NW = DEC2Q_NWV;
+  constexpr int NW = DEC2Q_NW;
   float* const B0 = wbuf;
   float* const B1 = wbuf + SEGQ * T;
   const __amdgpu_buffer_rsrc_t rm = mlp_rsrc(mlp);
-  // segments: [L0: 8 tiles] in B0, [L1: 4 tiles] in B1, then per segment s the tiles of kt = KTS s .. KTS s + KTS - 1
-  // ([W2 rows kt (2) | W3 column kt, ot 0-7 (8)] each) alternating B0 / B1, then [W4 rows + B3]
+  // segments: [L0: 8 tiles] in B0, [L1: 4 tiles] in B1, then per layer-2 tile kt [W2 rows kt (2) | W3 column kt,
+  // ot 0-7 (8)] alternating B0 / B1, then [W4 rows + B3]
   dma_tiles<NW>(B0, rm, Q_W0, 8, wv, lane);   // tile index 4 ot + kt
-  auto seg_l23 = [&](float* dst, int sg) {
+  auto seg_l23 = [&](float* dst, int kt) {
 #pragma unroll
-    for (int r = 0; r < 40 * KTS / NW; ++r) {
+    for (int r = 0; r < SEGQ * 4 / NW; ++r) {
       const int i = wv + r * NW;                // piece i: tile j = i / 4 of the segment, quarter i % 4
-      const int j = i >> 2, k = j / 10, jj = j - 10 * k, kt = sg * KTS + k;
-      const int src = (jj < 2 ? Q_W2 + (kt * 2 + jj) * T : Q_W3 + ((jj - 2) * 8 + kt) * T) + (i & 3) * 256;
+      const int j = i >> 2;
+      const int src = (j < 2 ? Q_W2 + (kt * 2 + j) * T : Q_W3 + ((j - 2) * 8 + kt) * T) + (i & 3) * 256;
       dec_dma(rm, dst + j * T + (i & 3) * 256, lane, src * 4);
     }
   };
-  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
-  const long long total = (long long)n * GH * GW;
-  const long long pix = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW + wv) * 16 + (lane & 15);
-  const bool valid = pix < total;
-  const long long pc = valid ? pix : total - 1;
-  const int item = (int)(pc / ((long long)GH * GW));
-  const int rem = (int)(pc - (long long)item * GH * GW);
-  const int py = rem / GW, px = rem - py * GW;
+  const Pixel pix = pixel_of<NW, 16, WIN>(wv, lane, n, HH, WW, win);
+  const long long pc = pix.pc;
+  const int item = pix.item, py = pix.ly, px = pix.lx;   // row / column in the rectangle
   const float t = tq[item];
   const float* P = proj + (size_t)item * h * w * PROJ_C;
   const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
@@ -893,15 +857,14 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
   const f32x4 fv = ld4(flow + (size_t)pc * 4);
   const float bx = tb.lin_x[WIN ? win.x0 + px : px], by = tb.lin_y[WIN ? win.y0 + py : py];
   const WarpGrids wg = warp_grids(fv, bx, by, WW, HH);
-  const float g1x = wg.g1x, g1y = wg.g1y, g2x = wg.g2x, g2y = wg.g2y;
 
   // ---- encode_imnet layer 0: W[:, :128] . [q_feat1 | q_feat2] + P3(grid1) + P4(grid2) + w_t t + b
   R32 x0[2];
   {
     R32 z[2], g[2];
-    gather_q(z, P, PROJ_C, 128, bilin(g1x, g1y, w, h), q);
+    gather_q(z, P, PROJ_C, 128, bilin(wg.g1x, wg.g1y, w, h), q);
     asm volatile("" ::: "memory");
-    gather_q(g, P, PROJ_C, 192, bilin(g2x, g2y, w, h), q);
+    gather_q(g, P, PROJ_C, 192, bilin(wg.g2x, wg.g2y, w, h), q);
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
@@ -913,7 +876,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
           z[ot].s[s][e] = (z[ot].s[s][e] + (g[ot].s[s][e] + wt[e] * t + bb[e])) * ACC_IN<1>;
       }
     asm volatile("" ::: "memory");
-    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(g1x, g1y, WW, HH, win, status), q);   // q_feat1 -> W0 columns 0..63
+    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(wg.g1x, wg.g1y, WW, HH, win, status), q);   // q_feat1 -> W0 columns 0..63
     lds_dma_barrier();                                      // layer 0 landed in B0
     dma_tiles<NW>(B1, rm, Q_W1, 4, wv, lane);
     {
@@ -924,7 +887,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
         for (int kt = 0; kt < 2; ++kt) tile_q(z[ot], B0 + (ot * 4 + kt) * T, qs[kt], lane);
     }
     asm volatile("" ::: "memory");
-    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(g2x, g2y, WW, HH, win, status), q);   // q_feat2 -> W0 columns 64..127
+    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(wg.g2x, wg.g2y, WW, HH, win, status), q);   // q_feat2 -> W0 columns 64..127
     const XQ qs[2] = {xq(g[0]), xq(g[1])};
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot) {
@@ -959,48 +922,37 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
   R32 a3[8];
 #pragma unroll
   for (int ot = 0; ot < 8; ++ot) a3[ot].s[0] = a3[ot].s[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int NSEG = 8 / KTS;
-  auto l23_step = [&](int sg, bool last) {
-    lds_dma_barrier();   // segment sg landed; every wave is done with the other buffer
-    R32 b2[KTS];
-#pragma unroll
-    for (int k = 0; k < KTS; ++k) b2[k] = bias_q(mlp + E_B2 + (sg * KTS + k) * 32, q);   // before the DMA
+  auto l23_step = [&](int kt, bool last) {   // kt = 7 peeled (see k_dec1's feat_step)
+    lds_dma_barrier();   // segment kt landed; every wave is done with the other buffer
+    const R32 b2 = bias_q(mlp + E_B2 + kt * 32, q);   // before the DMA
     __builtin_amdgcn_sched_barrier(0);
-    float* cur = (sg & 1) ? B1 : B0;
-    float* nxt = (sg & 1) ? B0 : B1;
-    auto dma_next = [&]() {
-      if (!last) seg_l23(nxt, sg + 1);
-      else dma_tiles<NW>(nxt, rm, E_W4V, 1, wv, lane);
-    };
-    dma_next();
+    float* cur = (kt & 1) ? B1 : B0;
+    float* nxt = (kt & 1) ? B0 : B1;
+    if (!last) seg_l23(nxt, kt + 1);
+    else dma_tiles<NW>(nxt, rm, E_W4V, 1, wv, lane);
+    R32 acc;
+    acc.s[0] = acc.s[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    tile_q(acc, cur, x1s[0], lane);
+    tile_q(acc, cur + T, x1s[1], lane);
+    const XQ h2 = xq(bias_sin_q(acc, b2));
 #pragma unroll
-    for (int k = 0; k < KTS; ++k) {
-      const float* sk = cur + k * 10 * T;
-      R32 acc;
-      acc.s[0] = acc.s[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      tile_q(acc, sk, x1s[0], lane);
-      tile_q(acc, sk + T, x1s[1], lane);
-      const XQ h2 = xq(bias_sin_q(acc, b2[k]));
-#pragma unroll
-      for (int ot = 0; ot < 8; ++ot) tile_q(a3[ot], sk + (2 + ot) * T, h2, lane);
-    }
+    for (int ot = 0; ot < 8; ++ot) tile_q(a3[ot], cur + (2 + ot) * T, h2, lane);
   };
 #pragma unroll 1
-  for (int sg = 0; sg < NSEG - 1; ++sg) l23_step(sg, false);
-  l23_step(NSEG - 1, true);
+  for (int kt = 0; kt < 7; ++kt) l23_step(kt, false);
+  l23_step(7, true);
   // layer 3 sine streamed into layer 4 (256 -> 3, VALU dot products over this lane's 64 features); W4 rows
-  // and the layer-3 biases in the buffer the last segment did not use (k_dec2's tile)
+  // and the layer-3 biases in B0, the buffer the last segment did not use (k_dec2's tile)
   lds_dma_barrier();
-  float* const B4 = ((NSEG - 1) & 1) ? B0 : B1;
   float o4[3] = {0.f, 0.f, 0.f};
 #pragma unroll
   for (int kt = 0; kt < 8; ++kt) {
-    const R32 h3 = bias_sin_q(a3[kt], B4 + (E_W4V_B3 - E_W4V) + kt * 32, q);
+    const R32 h3 = bias_sin_q(a3[kt], B0 + (E_W4V_B3 - E_W4V) + kt * 32, q);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const f32x4 wr = ld4(B4 + c * 256 + kt * 32 + 16 * s + 4 * q);
+        const f32x4 wr = ld4(B0 + c * 256 + kt * 32 + 16 * s + 4 * q);
 #pragma unroll
         for (int e = 0; e < 4; ++e) o4[c] = fmaf(wr[e], h3.s[s][e], o4[c]);
       }
@@ -1010,19 +962,7 @@ __global__ __launch_bounds__(DEC2Q_NWV * 64) __attribute__((amdgpu_waves_per_eu(
     o4[c] += __shfl_xor(o4[c], 16);
     o4[c] += __shfl_xor(o4[c], 32);
   }
-  if (valid && q == 0) {
-    const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
-    float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
-                   : out + (size_t)item * 3 * plane + (size_t)py * WW + px;
-    bool bad = not_finite((fv[0] + fv[1]) + (fv[2] + fv[3]));
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = o4[c] + mlp[E_B4 + c];
-      bad |= not_finite(v);
-      o[c * plane] = v;
-    }
-    report_range_w<WIN>(status, bad);
-  }
+  if (pix.valid && q == 0) store_rgb<WIN, true>(out, mlp, o4, fv, item, py, px, HH, WW, win, status);
 }
 
 // k_dec_bounds: the box (rows ymin..ymax, columns xmin..xmax of the virtual grid, inclusive) of every HRfeat corner
@@ -1126,84 +1066,7 @@ bool image_ok(const stif_dec_image* im) {
                  im->bx1 && im->wx0 && im->wx1);
 }
 
-template <int MODE, bool HRIMG>
-void launch_dec1(bool f16, long long total, hipStream_t st, const float* proj, const float* mlp,
-                 const stif_dec_tables& tb, const stif_dec_image& im, const float* t, float* hrfeat, float* flow, int n,
-                 int h, int w, int HH, int WW) {
-  const long long blocks = (total + NW1 * 32 - 1) / (NW1 * 32);
-  if (f16)
-    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1, false>), dim3((unsigned)blocks), dim3(NW1 * 64), 0, st, proj, mlp, tb, im,
-                       t, hrfeat, flow, n, h, w, HH, WW, stif_dec_window{});
-  else
-    hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0, false>), dim3((unsigned)blocks), dim3(NW1 * 64), 0, st, proj, mlp, tb, im,
-                       t, hrfeat, flow, n, h, w, HH, WW, stif_dec_window{});
-}
-
-}  // namespace
-
-extern "C" int stif_dec_stage1_ex(const float* proj, const float* mlp, const stif_dec_tables* tab,
-                                  const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
-                                  int w, int HH, int WW, int flags, int* status, void* stream) {
-  (void)status;   // stage 2 checks both stage-1 outputs it reads (flow, and HRfeat through the RGB; stif.h)
-  const bool f16 = flags & STIF_CONV_F16X3;
-  if (!proj || !mlp || !tables_ok(tab) || !image_ok(img) || !t || !hrfeat || !flow || n < 1 || h < 1 || w < 1 ||
-      HH < 2 || WW < 2 || (!tab->hr_y) != (!tab->hr_x))
-    return stif_fail(STIF_E_INVALID, "stif_dec_stage1: bad arguments");
-  const long long total = (long long)n * HH * WW;
-  hipStream_t st = (hipStream_t)stream;
-  const stif_dec_image im = img ? *img : stif_dec_image{};
-  if (tab->hr_y) {   // remapped HRfeat operand: the whole HRfeat map first, then the flow stage
-    launch_dec1<1, false>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
-    if (img) launch_dec1<2, true>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
-    else launch_dec1<2, false>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
-  } else if (img) {
-    launch_dec1<0, true>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
-  } else {
-    launch_dec1<0, false>(f16, total, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW);
-  }
-  return stif_check_launch("stif_dec_stage1");
-}
-
-extern "C" int stif_dec_stage1(const float* proj, const float* mlp, const stif_dec_tables* tab,
-                               const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
-                               int w, int HH, int WW, void* stream) {
-  return stif_dec_stage1_ex(proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, 0, nullptr, stream);
-}
-
-extern "C" int stif_dec_stage2_ex(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                                  const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
-                                  int n, int h, int w, int HH, int WW, int flags, int* status, void* stream) {
-  const bool f16 = flags & STIF_CONV_F16X3;
-  if (!proj || !mlp || !hrfeat || !flow || !tables_ok(tab) || !image_ok(img) || !t || !out || n < 1 || h < 1 ||
-      w < 1 || HH < 2 || WW < 2)
-    return stif_fail(STIF_E_INVALID, "stif_dec_stage2: bad arguments");
-  const long long total = (long long)n * HH * WW;
-  const long long blocks = (total + DEC2_NW * 32 - 1) / (DEC2_NW * 32);
-  const stif_dec_image im = img ? *img : stif_dec_image{};
-  hipStream_t st = (hipStream_t)stream;
-  if (DEC2_Q16 && f16 && !img) {
-    const long long qblocks = (total + DEC2Q_NWV * 16 - 1) / (DEC2Q_NWV * 16);
-    hipLaunchKernelGGL(k_dec2q<false>, dim3((unsigned)qblocks), dim3(DEC2Q_NWV * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
-                       out, n, h, w, HH, WW, status, stif_dec_window{});
-    return stif_check_launch("stif_dec_stage2");
-  }
-  const dim3 g((unsigned)blocks), b(DEC2_NW * 64);
-  if (img && f16) hipLaunchKernelGGL((k_dec2<true, 1, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
-  else if (img) hipLaunchKernelGGL((k_dec2<true, 0, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
-  else if (f16) hipLaunchKernelGGL((k_dec2<false, 1, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
-  else hipLaunchKernelGGL((k_dec2<false, 0, false>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, stif_dec_window{});
-  return stif_check_launch("stif_dec_stage2");
-}
-
-extern "C" int stif_dec_stage2(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                               const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n,
-                               int h, int w, int HH, int WW, void* stream) {
-  return stif_dec_stage2_ex(proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, 0, nullptr, stream);
-}
-
 // ---- windowed decoding
-namespace {
-
 bool rect_in(int y0, int x0, int hh, int ww, int HH, int WW) {
   return y0 >= 0 && x0 >= 0 && hh >= 1 && ww >= 1 && hh <= HH - y0 && ww <= WW - x0;
 }
@@ -1238,43 +1101,138 @@ int window_fail(const char* entry, const char* why) {
   return stif_fail(STIF_E_INVALID, msg);
 }
 
-template <int MODE, bool HRIMG>
-void launch_dec1w(bool f16, hipStream_t st, const float* proj, const float* mlp, const stif_dec_tables& tb,
-                  const stif_dec_image& im, const float* t, float* hrfeat, float* flow, int n, int h, int w, int HH,
-                  int WW, const stif_dec_window& wn) {
-  const long long total = (long long)n * wn.hh * wn.ww;
-  const dim3 g((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32))), b(NW1 * 64);
-  if (f16) hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 1, true>), g, b, 0, st, proj, mlp, tb, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
-  else hipLaunchKernelGGL((k_dec1<MODE, HRIMG, 0, true>), g, b, 0, st, proj, mlp, tb, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
+// A runtime bool as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <int M>
+using Mode = std::integral_constant<int, M>;
+
+// Stage 1 behind its three entry points.  WIN: `win` is resolved here and the pixels are its query rectangle's;
+// the whole-grid form never looks at `win` and launches the WIN = false kernels, which never read the window.
+template <bool WIN>
+int dec_stage1(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
+               const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h, int w, int HH,
+               int WW, int flags, void* stream, const stif_dec_window* win) {
+  const bool args_ok = proj && mlp && tables_ok(tab) && image_ok(img) && t && hrfeat && n >= 1 && h >= 1 && w >= 1;
+  stif_dec_window wn{};
+  if constexpr (WIN) {   // a null flow is the feat-only pass
+    if (!args_ok) return window_fail(me, "bad arguments (null pointer or empty shape)");
+    if (tab->hr_y || tab->hr_x) return window_fail(me, "tables with hr_y / hr_x (local ensemble) have no windowed form");
+    if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
+    // every pixel of the query rectangle stores its HRfeat row into the F layout
+    if (!f_holds_query(wn)) return window_fail(me, "the F rectangle does not contain the query rectangle");
+  } else if (!args_ok || !flow || HH < 2 || WW < 2 || (!tab->hr_y) != (!tab->hr_x)) {
+    return stif_fail(STIF_E_INVALID, "stif_dec_stage1: bad arguments");
+  }
+  const bool f16 = flags & STIF_CONV_F16X3;
+  const long long total = (long long)n * (WIN ? wn.hh : HH) * (WIN ? wn.ww : WW);
+  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
+  const stif_dec_image im = img ? *img : stif_dec_image{};
+  auto launch = [&](auto mode, auto hrimg) {
+    with_bool(f16, [&](auto f16x3) {
+      hipLaunchKernelGGL((k_dec1<decltype(mode)::value, decltype(hrimg)::value, decltype(f16x3)::value, WIN>), grid,
+                         dim3(NW1 * 64), 0, (hipStream_t)stream, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH,
+                         WW, wn);
+    });
+  };
+  if constexpr (WIN) {
+    with_bool(img != nullptr, [&](auto hrimg) {
+      if (!flow) launch(Mode<1>{}, hrimg);
+      else launch(Mode<0>{}, hrimg);
+    });
+  } else if (tab->hr_y) {   // remapped HRfeat operand: the whole HRfeat map first, then the flow stage
+    launch(Mode<1>{}, std::false_type{});
+    with_bool(img != nullptr, [&](auto hrimg) { launch(Mode<2>{}, hrimg); });
+  } else {
+    with_bool(img != nullptr, [&](auto hrimg) { launch(Mode<0>{}, hrimg); });
+  }
+  return stif_check_launch(me);
+}
+
+// Stage 2 behind its three entry points (WIN as dec_stage1's).  f16x3 operands without an HR image go to k_dec2q
+// (16 pixels per wave, four waves per SIMD: C2 stage 2 17.55-17.79 -> 17.32-17.34 ms, profiles/r04_dec2q4_ab.log);
+// the fp32 and the HR-image stages to k_dec2.
+template <bool WIN>
+int dec_stage2(const char* me, const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+               const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n, int h, int w,
+               int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win) {
+  const bool args_ok = proj && mlp && hrfeat && flow && tables_ok(tab) && image_ok(img) && t && out && n >= 1 &&
+                       h >= 1 && w >= 1;
+  stif_dec_window wn{};
+  if constexpr (WIN) {
+    if (!args_ok) return window_fail(me, "bad arguments (null pointer or empty shape)");
+    if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
+  } else if (!args_ok || HH < 2 || WW < 2) {
+    return stif_fail(STIF_E_INVALID, "stif_dec_stage2: bad arguments");
+  }
+  const bool f16 = flags & STIF_CONV_F16X3;
+  const long long total = (long long)n * (WIN ? wn.hh : HH) * (WIN ? wn.ww : WW);
+  auto grid = [&](int wg_pixels) { return dim3((unsigned)((total + wg_pixels - 1) / wg_pixels)); };
+  hipStream_t st = (hipStream_t)stream;
+  if (f16 && !img) {
+    hipLaunchKernelGGL(k_dec2q<WIN>, grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
+                       out, n, h, w, HH, WW, status, wn);
+  } else {
+    const stif_dec_image im = img ? *img : stif_dec_image{};
+    with_bool(img != nullptr, [&](auto hrimg) {
+      with_bool(f16, [&](auto f16x3) {
+        if constexpr (decltype(hrimg)::value || !decltype(f16x3)::value)   // the other pair is k_dec2q's, above
+          hipLaunchKernelGGL((k_dec2<decltype(hrimg)::value, decltype(f16x3)::value, WIN>), grid(DEC2_NW * 32),
+                             dim3(DEC2_NW * 64), 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW,
+                             status, wn);
+      });
+    });
+  }
+  return stif_check_launch(me);
 }
 
 }  // namespace
 
+// status: stage 2 checks both stage-1 outputs it reads (flow, and HRfeat through the RGB; stif.h), so stage 1 has
+// nothing to report
+extern "C" int stif_dec_stage1_ex(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                  const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
+                                  int w, int HH, int WW, int flags, int* /*status*/, void* stream) {
+  return dec_stage1<false>("stif_dec_stage1", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, stream,
+                           nullptr);
+}
+
+extern "C" int stif_dec_stage1(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                               const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
+                               int w, int HH, int WW, void* stream) {
+  return stif_dec_stage1_ex(proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, 0, nullptr, stream);
+}
+
 extern "C" int stif_dec_stage1_win(const float* proj, const float* mlp, const stif_dec_tables* tab,
                                    const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
-                                   int w, int HH, int WW, int flags, int* status, void* stream,
+                                   int w, int HH, int WW, int flags, int* /*status*/, void* stream,
                                    const stif_dec_window* win) {
-  (void)status;   // as stif_dec_stage1_ex: stage 2 checks what it reads
-  static const char* const me = "stif_dec_stage1_win";
-  if (!proj || !mlp || !tables_ok(tab) || !image_ok(img) || !t || !hrfeat || n < 1 || h < 1 || w < 1)
-    return window_fail(me, "bad arguments (null pointer or empty shape)");
-  if (tab->hr_y || tab->hr_x) return window_fail(me, "tables with hr_y / hr_x (local ensemble) have no windowed form");
-  stif_dec_window wn;
-  if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
-  // every pixel of the query rectangle stores its HRfeat row into the F layout
-  if (!f_holds_query(wn)) return window_fail(me, "the F rectangle does not contain the query rectangle");
-  const bool f16 = flags & STIF_CONV_F16X3;
-  hipStream_t st = (hipStream_t)stream;
-  const stif_dec_image im = img ? *img : stif_dec_image{};
-  if (!flow) {
-    if (img) launch_dec1w<1, true>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
-    else launch_dec1w<1, false>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
-  } else if (img) {
-    launch_dec1w<0, true>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
-  } else {
-    launch_dec1w<0, false>(f16, st, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH, WW, wn);
-  }
-  return stif_check_launch(me);
+  return dec_stage1<true>("stif_dec_stage1_win", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, stream,
+                          win);
+}
+
+extern "C" int stif_dec_stage2_ex(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                  const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
+                                  int n, int h, int w, int HH, int WW, int flags, int* status, void* stream) {
+  return dec_stage2<false>("stif_dec_stage2", proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, flags,
+                           status, stream, nullptr);
+}
+
+extern "C" int stif_dec_stage2(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                               const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n,
+                               int h, int w, int HH, int WW, void* stream) {
+  return stif_dec_stage2_ex(proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, 0, nullptr, stream);
+}
+
+extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                   const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
+                                   int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                   const stif_dec_window* win) {
+  return dec_stage2<true>("stif_dec_stage2_win", proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, flags,
+                          status, stream, win);
 }
 
 extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int n, int HH, int WW,
@@ -1288,33 +1246,6 @@ extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, in
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_dec_bounds_init, dim3(1), dim3(64), 0, st, box);
   hipLaunchKernelGGL(k_dec_bounds, dim3(blocks), dim3(256), 0, st, flow, *tab, box, total, HH, WW, wn);
-  return stif_check_launch(me);
-}
-
-extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                                   const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
-                                   int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
-                                   const stif_dec_window* win) {
-  static const char* const me = "stif_dec_stage2_win";
-  if (!proj || !mlp || !hrfeat || !flow || !tables_ok(tab) || !image_ok(img) || !t || !out || n < 1 || h < 1 || w < 1)
-    return window_fail(me, "bad arguments (null pointer or empty shape)");
-  stif_dec_window wn;
-  if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
-  const bool f16 = flags & STIF_CONV_F16X3;
-  const long long total = (long long)n * wn.hh * wn.ww;
-  const stif_dec_image im = img ? *img : stif_dec_image{};
-  hipStream_t st = (hipStream_t)stream;
-  if (DEC2_Q16 && f16 && !img) {
-    const long long qblocks = (total + DEC2Q_NWV * 16 - 1) / (DEC2Q_NWV * 16);
-    hipLaunchKernelGGL(k_dec2q<true>, dim3((unsigned)qblocks), dim3(DEC2Q_NWV * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
-                       out, n, h, w, HH, WW, status, wn);
-    return stif_check_launch(me);
-  }
-  const dim3 g((unsigned)((total + DEC2_NW * 32 - 1) / (DEC2_NW * 32))), b(DEC2_NW * 64);
-  if (img && f16) hipLaunchKernelGGL((k_dec2<true, 1, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
-  else if (img) hipLaunchKernelGGL((k_dec2<true, 0, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
-  else if (f16) hipLaunchKernelGGL((k_dec2<false, 1, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
-  else hipLaunchKernelGGL((k_dec2<false, 0, true>), g, b, 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW, status, wn);
   return stif_check_launch(me);
 }
 

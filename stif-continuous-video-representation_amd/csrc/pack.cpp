@@ -86,8 +86,8 @@ void column(float* dst, const float* W, int ld, int rows, int col) {
 // SineLayer: sin(omega_0 * (W x + b)) with omega_0 = 30 (SIREN.py:44-51): the packed copies of every
 // sine layer's weights and bias carry the factor (computed in double, rounded once), so the kernels
 // evaluate sin(W' x + b') without the multiply.  `rev`: the factor is omega_0 / (2 pi), i.e. the
-// pre-activations come out in revolutions, the unit of the hardware sine (v_sin_f32), and the kernel's
-// range reduction is x - rint(x) (the f16x3 decoder: stif_sin_rev)
+// pre-activations come out in revolutions, the unit of the hardware sine (v_sin_f32), which reduces its
+// argument itself (the f16x3 decoder: siren_sin<1>)
 constexpr double OMEGA0 = 30.0;
 constexpr double TWO_PI = 6.283185307179586476925286766559;
 std::vector<float> omega(const float* src, size_t n, bool rev) {

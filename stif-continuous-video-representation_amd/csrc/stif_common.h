@@ -39,18 +39,6 @@ STIF_DEV void split_f16x3(f32x4 x0, f32x4 x1, f16x8& h, f16x8& l) {
   // is exact in fp32, so l equals fp16(x * 2^4 - float(h)) bit for bit, at 4 VALU ops per pair
   // instead of ~7 (the compiler's lowering of the plain expression scales, converts h back to fp32
   // and subtracts separately)
-#if STIF_SPLIT_C
-  // plain-expression form (diagnostic): the compiler sees the VALU ops, so its hazard recognizer covers them
-  const f32x4 s0 = x0 * F16X3_SCALE_A, s1 = x1 * F16X3_SCALE_A;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float v = e < 4 ? s0[e] : s1[e - 4];
-    const _Float16 hh = (_Float16)v;
-    h[e] = hh;
-    l[e] = (_Float16)(v - (float)hh);
-  }
-  return;
-#endif
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   u32x4 hv, lv;
 #pragma unroll
@@ -58,17 +46,10 @@ STIF_DEV void split_f16x3(f32x4 x0, f32x4 x1, f16x8& h, f16x8& l) {
     const float x = e < 2 ? x0[2 * e] : x1[2 * e - 4];
     const float y = e < 2 ? x0[2 * e + 1] : x1[2 * e - 3];
     unsigned hp, lp;
-    asm(
-#if STIF_SPLIT_NOP_PRE
-        "s_nop 7\n\ts_nop 7\n\t"
-#endif
-        "v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
+    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
         "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
         "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
         "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-#if STIF_SPLIT_NOP
-        "\n\ts_nop 4"
-#endif
         : "=&v"(hp), "=&v"(lp)
         : "v"(x), "v"(y), "s"(F16X3_SCALE_A));
     hv[e] = hp;
@@ -102,20 +83,16 @@ STIF_DEV float sigmoid_fast(float x) {
 enum { STIF_ACT_NONE = 0, STIF_ACT_LRELU = 1, STIF_ACT_RELU = 2, STIF_ACT_RES = 3,
        STIF_ACT_OFFMASK = 4, STIF_ACT_LSTM = 5 };
 
-// sin(2 pi x) for pre-activations in revolutions (the f16x3 decoder: omega_0 / (2 pi) is folded into
-// the packed sine-layer weights, stif_pack_dec_mlp_ex): x - rint(x) is exact, so the one rounding of
-// the reduction is the fp32 accumulation of x itself, as for a pre-activation in radians; then the
-// hardware v_sin_f32 on [-1/2, 1/2] revolutions (~4e-7 absolute, tools/experiments/sin_acc.hip).
-// 2 VALU + one transcendental (8 issue cycles): the SIREN decoder is VALU-issue-bound and evaluates one
-// sine per hidden unit.  Used instead of ocml sinf, whose Payne-Hanek path costs ~200 VGPRs in the MLP
-// kernels.
+// sin(2 pi x) for an argument in revolutions, reduced explicitly: x - rint(x) is exact, then the hardware
+// v_sin_f32 on [-1/2, 1/2] revolutions (~4e-7 absolute).  The accuracy baseline of tools/experiments/sin_acc.hip;
+// no kernel uses it -- the f16x3 decoder leaves the reduction to the hardware (siren_sin<1> below).
 STIF_DEV float stif_sin_rev(float x) { return __builtin_amdgcn_sinf(x - __builtin_rintf(x)); }
 
 // sin(x) for the fp32-operand decoder (F16 = 0, the fp32 re-run the range guard promises): quadrant
 // reduction by pi/2 (q = rint(x 2/pi), 3-part Cody-Waite constant, exact products for |q| < 2^12,
 // i.e. |x| < 6400) and minimax-free Taylor polynomials on [-pi/4, pi/4] through r^9 (sin) / r^8 (cos):
 // ~1e-7 absolute, the accuracy of the reference's torch.sin within a few ulp; ~20 VALU, no
-// transcendental.  The f16x3 decoder uses the faster stif_sin_rev above.
+// transcendental.  The f16x3 decoder uses the hardware sine (siren_sin<1> below).
 __host__ __device__ __forceinline__ float stif_sin_poly(float x) {
   const float qm = fmaf(x, 0.636619772367581343076f, 12582912.0f);   // round(x * 2/pi) by the magic add
   const float q = qm - 12582912.0f;
@@ -129,17 +106,16 @@ __host__ __device__ __forceinline__ float stif_sin_poly(float x) {
   const float v = (qi & 1) ? pc : ps;
   return (qi & 2) ? -v : v;
 }
-// The hardware sine reduces its argument itself, exactly: v_sin_f32 of x and of x - rint(x) have the same
-// maximum error against sin(2 pi x) -- 1.1-1.3e-7 in every band from |x| <= 0.5 to |x| <= 1e7 revolutions, 6-34 %
-// of results one ulp apart (tools/r5/vsin_reduce.hip, profiles/r05_sin_raw.log) -- so the f16x3 decoder skips the
-// two-instruction reduction (DEC_SIN_RAW = 1).
-#ifndef DEC_SIN_RAW
-#define DEC_SIN_RAW 1
-#endif
+// The SIREN sine.  F16 (the f16x3 decoder): sin(2 pi x) of a pre-activation in revolutions -- omega_0 / (2 pi) is
+// folded into the packed sine-layer weights (stif_pack_dec_mlp_ex) -- by the hardware v_sin_f32 alone, one
+// transcendental: the decoder is VALU-issue-bound and evaluates one sine per hidden unit, and ocml sinf's
+// Payne-Hanek path costs ~200 VGPRs in the MLP kernels.  The hardware sine reduces its argument itself, exactly:
+// v_sin_f32 of x and of x - rint(x) have the same maximum error against sin(2 pi x) -- 1.1-1.3e-7 in every band
+// from |x| <= 0.5 to |x| <= 1e7 revolutions, 6-34 % of results one ulp apart (tools/r5/vsin_reduce.hip,
+// profiles/r05_sin_raw.log) -- so no reduction is spent.  Otherwise (fp32 operands): stif_sin_poly.
 template <int F16>
 STIF_DEV float siren_sin(float x) {
-  if constexpr (F16 && DEC_SIN_RAW) return __builtin_amdgcn_sinf(x);
-  else if constexpr (F16) return stif_sin_rev(x);
+  if constexpr (F16) return __builtin_amdgcn_sinf(x);
   else return stif_sin_poly(x);
 }
 

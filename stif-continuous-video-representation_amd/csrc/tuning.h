@@ -23,26 +23,7 @@
 #define DCN_MR2_MIN 1024   // two-row kernel from this many workgroups (512 measured no faster)
 #endif
 
-// ---- k_dec1 / k_dec2 / k_dec2q (decoder.hip)
-#ifndef DEC1_OCC
-// k_dec1 (MODE 0 / 1) workgroups per CU: 4 (36 KB LDS, 128 registers, the flow projection gathered in four
-// 8-load quarters), 3 (52 KB, 168, halves) or 2 (69 KB, 256).  C0 dec1 869 -> 758 us (2 -> 3,
-// r04_dec1_occ_ab.log) -> 720 us (3 -> 4; C2 11.6 -> 11.1 ms, r04_dec1_occ4_ab.log); all bit-identical
-#define DEC1_OCC 4
-#endif
-#ifndef DEC2_Q16
-// stage 2 (f16x3, LR-projection inputs) by k_dec2q: 16 pixels per wave, four waves per SIMD (128 VGPRs);
-// C2 stage 2 17.55-17.79 -> 17.32-17.34 ms (r04_dec2q4_ab.log).  0 = k_dec2 (also the fp32 and
-// high-resolution-image stages)
-#define DEC2_Q16 1
-#endif
-#ifndef DEC2Q_NW
-// k_dec2q waves per workgroup: 8 (two 80-KB workgroups per CU, one layer-2 tile per streamed weight segment) or
-// 16 (one 160-KB workgroup, two tiles per segment: +27 %, r06_dec_ab.log)
-#define DEC2Q_NW 8
-#endif
-#ifndef DEC2Q_KTS
-#define DEC2Q_KTS (DEC2Q_NW == 16 ? 2 : 1)   // layer-2 tiles per streamed weight segment
-#endif
-static_assert(DEC1_OCC >= 2 && DEC1_OCC <= 4, "DEC1_OCC: k_dec1 is laid out for 2, 3 or 4 workgroups per CU");
-static_assert(DEC2_Q16 == 0 || DEC2_Q16 == 1, "DEC2_Q16: 0 (k_dec2) or 1 (k_dec2q)");
+// ---- k_dec1 / k_dec2 / k_dec2q (decoder.hip): no knobs.  What earlier A/Bs settled is fixed in the source, with its
+// numbers at the line that fixes it: k_dec1's workgroups per CU (OCC1: 4, HR-image variants 3, MODE 2 2;
+// r04_dec1_occ_ab.log, r04_dec1_occ4_ab.log), f16x3 stage 2 without an HR image by k_dec2q (r04_dec2q4_ab.log) in
+// 8-wave workgroups with one layer-2 tile per weight segment (r06_dec_ab.log), the raw hardware sine (r05_sin_raw.log)

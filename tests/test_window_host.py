@@ -108,3 +108,70 @@ def test_window_entry_points_validate_before_launching(stif):
     assert s1(W(9, 11, 13, 17), hrf=None) == L.E_INVALID
     assert s2(W(9, 11, 13, 17), out=None) == L.E_INVALID
     assert bd(W(9, 11, 13, 17), box=None) == L.E_INVALID
+
+
+def test_whole_grid_entry_points_validate_before_launching(stif):
+    """The whole-grid stage entry points (_ex and plain) reject every bad argument with STIF_E_INVALID and their one
+    text before any launch; the (fake) pointers are never touched."""
+    L = stif._lib
+    lib = L.lib()
+    A = 4096                                 # a fake address: validation comes first
+    tab = L.DecTables(*[A] * 14)             # hr_y / hr_x stay NULL
+    shape = dict(n=1, h=16, w=20, HH=37, WW=45)
+
+    def s1(ex, tab=tab, img=None, **kw):
+        a = dict(proj=A, mlp=A, t=A, hrfeat=A, flow=A, **shape)
+        a.update(kw)
+        head = (a["proj"], a["mlp"], C.byref(tab) if tab is not None else None,
+                C.byref(img) if img is not None else None, a["t"], a["hrfeat"], a["flow"],
+                a["n"], a["h"], a["w"], a["HH"], a["WW"])
+        return lib.stif_dec_stage1_ex(*head, 0, None, None) if ex else lib.stif_dec_stage1(*head, None)
+
+    def s2(ex, tab=tab, img=None, **kw):
+        a = dict(proj=A, mlp=A, hrfeat=A, flow=A, t=A, out=A, **shape)
+        a.update(kw)
+        head = (a["proj"], a["mlp"], a["hrfeat"], a["flow"], C.byref(tab) if tab is not None else None,
+                C.byref(img) if img is not None else None, a["t"], a["out"], a["n"], a["h"], a["w"], a["HH"], a["WW"])
+        return lib.stif_dec_stage2_ex(*head, 0, None, None) if ex else lib.stif_dec_stage2(*head, None)
+
+    def rejected(fn, text, ex, **kw):
+        lib.stif_dec_blend4(None, None, None, 0, 0, 0, None)      # another text in the error slot first
+        assert fn(ex, **kw) == L.E_INVALID, (text, ex, kw)
+        assert lib.stif_last_error() == text, (lib.stif_last_error(), ex, kw)
+
+    img_bad = L.DecImage(A, 64, 80, *[A] * 8)
+    img_bad.wx0 = None                       # one null table
+    img_noimg = L.DecImage(None, 64, 80, *[A] * 8)
+    tab_hr_y = L.DecTables(*[A] * 15)        # hr_y without hr_x
+    tab_hr_x = L.DecTables(*[A] * 14)
+    tab_hr_x.hr_x = A                        # hr_x without hr_y
+    tab_hole = L.DecTables(*[A] * 14)
+    tab_hole.lin_x = None                    # one null table
+    for fn, text, ptrs in ((s1, b"stif_dec_stage1: bad arguments", ("proj", "mlp", "t", "hrfeat", "flow")),
+                           (s2, b"stif_dec_stage2: bad arguments", ("proj", "mlp", "hrfeat", "flow", "t", "out"))):
+        for ex in (True, False):
+            for name in ptrs:                # each null pointer in turn (a null flow included)
+                rejected(fn, text, ex, **{name: None})
+            rejected(fn, text, ex, tab=None)
+            rejected(fn, text, ex, tab=tab_hole)
+            for kw in (dict(n=0), dict(h=0), dict(w=0), dict(HH=1), dict(WW=1)):
+                rejected(fn, text, ex, **kw)
+            rejected(fn, text, ex, img=img_bad)
+            rejected(fn, text, ex, img=img_noimg)
+    for ex in (True, False):
+        rejected(s1, b"stif_dec_stage1: bad arguments", ex, tab=tab_hr_y)
+        rejected(s1, b"stif_dec_stage1: bad arguments", ex, tab=tab_hr_x)
+    # the windowed stage 1 takes a null flow (the feat-only pass): its argument check passes and the window is
+    # looked at next; a null hrfeat is still its own rejection
+    W = L.DecWindow
+
+    def s1w(win, flow, hrf=A):
+        return lib.stif_dec_stage1_win(A, A, C.byref(tab), None, A, hrf, flow, 1, 16, 20, 37, 45, 0, None, None,
+                                       C.byref(win) if win is not None else None)
+
+    assert s1w(None, None) == L.E_INVALID
+    assert lib.stif_last_error() == b"stif_dec_stage1_win: null window"
+    assert s1w(W(30, 0, 13, 17), None) == L.E_INVALID
+    assert lib.stif_last_error() == b"stif_dec_stage1_win: the query rectangle is not inside the HH x WW grid"
+    assert s1w(W(9, 11, 13, 17), None, hrf=None) == L.E_INVALID
+    assert lib.stif_last_error() == b"stif_dec_stage1_win: bad arguments (null pointer or empty shape)"

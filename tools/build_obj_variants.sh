@@ -2,7 +2,8 @@
 # Kernel-experiment libraries that differ from the in-tree build in ONE object: SRC (a csrc/*.hip
 # basename) compiled with -D switches (VAR = 'A+B=2' -> -DA -DB=2) and linked with the other in-tree
 # objects (make first), so every other kernel keeps the Makefile's exact flags.  -> tools/exp_<VAR>.so
-# For the knobs of csrc/tuning.h, e.g. `tools/build_obj_variants.sh decoder DEC1_OCC=3`; bench.py and the
+# For the knobs of csrc/tuning.h, e.g. `tools/build_obj_variants.sh wino WINO_OM_RING=4` (the decoder has none
+# left: what its A/Bs settled is fixed in decoder.hip, tuning.h lists the logs); bench.py and the
 # tools/bench_*.py microbenchmarks run against a variant with STIF_HIP_LIB=$PWD/tools/exp_<VAR>.so.
 set -e
 cd "$(dirname "$0")/.."
