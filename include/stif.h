@@ -423,6 +423,26 @@ int stif_metric_psnr_ssim(const stif_metric_args* args, double* out, void* works
 /* The normalised 1-D window (cv2.getGaussianKernel(11, 1.5)) as the host computes it for the kernel. */
 int stif_metric_window(double k[11]);
 
+/* The float protocol, myutils.eval_metrics (:234-241): calc_psnr beside an SSIM of the frames clamped to [0, 1],
+ * data range 1 (C1 = 1e-4, C2 = 9e-4), fp64 after the clamp, replicate padding of 5, so that every one of the
+ * 3 H W positions is a centre.  STIF_FSSIM_VOLUME is myutils.ssim_matlab (:105-158): the RGB frame as a 3 x H x W
+ * volume under an 11 x 11 x 11 window, padded on all three axes (over three channels the depth pass is a fixed
+ * 3 x 3 channel mix).  STIF_FSSIM_PLANAR is myutils.ssim (:47-102): the 11 x 11 window per channel.  The window is
+ * stif_metric_window's fp64 one; the reference builds its own in fp32 (gap: DESIGN.md section 3f). */
+enum { STIF_FSSIM_VOLUME = 0, STIF_FSSIM_PLANAR = 1 };
+/* Bytes of workspace stif_metric_float needs (four doubles per 32 x 32 tile of every channel); 0 for n < 1, H or
+ * W < 11 (the reference's smaller window for smaller images is not reproduced) or an unknown mode.  Pure host. */
+size_t stif_metric_float_workspace_size(int n, int H, int W, int mode);
+/* args: pred / pred_* against gt_f32 / gtf_* (both fp32 RGB planes, unclamped), n, H, W; gt_u8 is ignored; flags
+ * must be 0 or STIF_METRIC_FLOAT.  out: device array [n][4] = { sum of squared errors of the unclamped floats,
+ * 3 H W, sum of the SSIM map, 3 H W } per item: PSNR = -10 log10(sse / npix + 1e-8), SSIM = ssim_sum / nwin
+ * (stif_amd.metrics.finish with float_mode).  Two launches on `stream`, no host read-back (graph-capturable), no
+ * floating-point atomics: repeated calls give identical bits.  Every argument is validated before the first
+ * launch: STIF_E_INVALID for null pointers, n < 1, H or W < 11, an unknown mode, bad flags, a pitch below W,
+ * overlapping planes or items, a misaligned out or workspace; STIF_E_WORKSPACE for a missing or short workspace. */
+int stif_metric_float(const stif_metric_args* args, int mode, double* out, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 /* ---- video I/O: planar Y'CbCr (the frame payload of a YUV4MPEG2 stream) <-> the model's fp32 RGB planes ---- */
 
 enum { STIF_YUV_BT601 = 0, STIF_YUV_BT709 = 1 };   /* stif_yuv_format.matrix: (Kr, Kb) = (0.299, 0.114) / (0.2126, 0.0722) */

@@ -72,6 +72,7 @@ class DecWindow(C.Structure):
 
 
 METRIC_Y, METRIC_SSIM, METRIC_FLOAT = 1, 2, 4   # stif_metric_args.flags (stif.h STIF_METRIC_*)
+FSSIM_VOLUME, FSSIM_PLANAR = 0, 1               # stif_metric_float's mode (stif.h STIF_FSSIM_*)
 
 
 class MetricArgs(C.Structure):
@@ -100,6 +101,8 @@ EXPORTS = {
     "stif_metric_workspace_size": (C.c_size_t, [C.c_int] * 4),
     "stif_metric_psnr_ssim": (C.c_int, [C.POINTER(MetricArgs), _P, _P, C.c_size_t, _P]),
     "stif_metric_window": (C.c_int, [C.POINTER(C.c_double)]),
+    "stif_metric_float_workspace_size": (C.c_size_t, [C.c_int] * 4),
+    "stif_metric_float": (C.c_int, [C.POINTER(MetricArgs), C.c_int, _P, _P, C.c_size_t, _P]),
     "stif_conv2d_nhwc": (C.c_int, [C.POINTER(ConvArgs), _P]),
     "stif_conv3x3_wino": (C.c_int, [C.POINTER(ConvArgs), _P]),
     "stif_upsample2x_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,

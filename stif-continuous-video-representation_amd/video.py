@@ -13,7 +13,8 @@ The harness's data formats either side of the model run on the GPU too:
 
 ``evaluate_sequence`` / ``evaluate_folder`` add the reference's evaluation loop (myutils.py:1151-1174):
 run_sequence, then PSNR / SSIM of every output frame that has a ground truth, scored on the device
-(stif_amd.metrics), and the "AVG PSNR / AVG SSIM" means.
+(stif_amd.metrics), and the "AVG PSNR / AVG SSIM" means; ``metric="float"`` scores with the float protocol of
+myutils.eval_metrics (:234-241: calc_psnr beside ssim_matlab) instead of the quantised one.
 
 ``frame_schedule`` / ``render_stream`` / ``render_y4m`` render whole videos: any length in bounded memory (frames
 are taken a chunk at a time, each encoded once), any rational output frame rate (every pair gets its own query
@@ -166,14 +167,34 @@ def run_folder(model, in_dir: str, out_dir: str, times=None):
 
 
 # ----------------------------------------------------------------------------- evaluation
-def evaluate_sequence(model, frames: torch.Tensor, gt, times=None, scale=None, channels: str = "y"):
+def _gt_float_planes(g: torch.Tensor, device) -> torch.Tensor:
+    """The float protocol's ground truth [3, H, W] on the device: a float tensor is taken as RGB planes; uint8 BGR
+    [H, W, 3] becomes RGB planes / 255 in fp32 (a 256-entry table of the correctly rounded quotients, gathered on
+    the device)."""
+    if g.is_floating_point():
+        if g.dim() != 3 or g.shape[0] != 3:
+            raise ValueError(f"a float ground truth must be RGB planes [3, H, W]; got {tuple(g.shape)}")
+        return g.to(device)
+    if g.dtype != torch.uint8 or g.dim() != 3 or g.shape[2] != 3:
+        raise ValueError(f"gt must be uint8 BGR [H, W, 3] or float RGB [3, H, W]; got {g.dtype} {tuple(g.shape)}")
+    lut = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(device)
+    return lut[g.to(device).flip(2).permute(2, 0, 1).contiguous().long()]
+
+
+def evaluate_sequence(model, frames: torch.Tensor, gt, times=None, scale=None, channels: str = "y",
+                      metric: str = "quantised"):
     """run_sequence + the reference's scoring loop (myutils.py:1155-1174) on the device.  gt[pair][time] is the
     ground truth of that output frame, uint8 BGR [H, W, 3] (numpy or torch, as cv2.imread), or None to skip it.
     When pad_to_4 padded the input the outputs are larger than the ground truth: the top-left H x W crop of the
-    output is scored in place, through the metric's stride arguments.  Returns {"psnr", "ssim": lists over pairs
-    of lists over times (None where skipped), "avg_psnr", "avg_ssim": means over the scored frames (the
-    reference's "AVG PSNR / AVG SSIM"), "count"}."""
+    output is scored in place, through the metric's stride arguments.  metric="float" scores with
+    myutils.eval_metrics instead (metrics.eval_metrics: calc_psnr and ssim_matlab on the unquantised floats;
+    `channels` does not apply); there a ground truth may also be a float RGB [3, H, W] tensor, and must be at
+    least 11 x 11.  Returns {"psnr", "ssim": lists over pairs of lists over times (None where skipped),
+    "avg_psnr", "avg_ssim": means over the scored frames (the reference's "AVG PSNR / AVG SSIM"), "count"}."""
     from . import metrics as M
+    if metric not in ("quantised", "float"):
+        raise ValueError('metric must be "quantised" or "float"')
+    fl = metric == "float"
     outs = run_sequence(model, frames, times, scale)
     flags = M.mode_flags(channels, True)
     where, sums = [], []
@@ -183,15 +204,18 @@ def evaluate_sequence(model, frames: torch.Tensor, gt, times=None, scale=None, c
             if g is None:
                 continue
             g = torch.as_tensor(np.ascontiguousarray(g) if isinstance(g, np.ndarray) else g)
-            H, W = g.shape[:2]
+            if fl:
+                g = _gt_float_planes(g, o.device)
+            H, W = g.shape[1:] if fl else g.shape[:2]
             if H > o.shape[1] or W > o.shape[2]:
                 raise ValueError(f"gt[{i}][{k}] is {H}x{W}, larger than the {o.shape[1]}x{o.shape[2]} output")
-            sums.append(M.sums(o[None, :, :H, :W], g[None], flags))
+            crop = o[None, :, :H, :W]
+            sums.append(M.sums_float(crop, g[None]) if fl else M.sums(crop, g[None], flags))
             where.append((i, k))
     psnr = [[None] * len(row) for row in outs]
     ssim = [[None] * len(row) for row in outs]
     if sums:
-        p, s = M.finish(torch.cat(sums, 0).cpu().numpy())     # one read-back for the whole sequence
+        p, s = M.finish(torch.cat(sums, 0).cpu().numpy(), float_mode=fl)     # one read-back for the whole sequence
         for (i, k), pv, sv in zip(where, p, s):
             psnr[i][k], ssim[i][k] = float(pv), float(sv)
     n = len(where)
@@ -205,11 +229,13 @@ def _frame_key(name: str):
     return (0, int(stem), name) if stem.isdigit() else (1, 0, name)
 
 
-def evaluate_folder(model, lr_dir: str, gt_dir: str, times=None, scale=None, channels: str = "y"):
+def evaluate_folder(model, lr_dir: str, gt_dir: str, times=None, scale=None, channels: str = "y",
+                    metric: str = "quantised"):
     """evaluate_sequence for frames on disk: lr_dir holds the low-resolution input frames, gt_dir the ground
     truth of the output frames in output order (pair-major, then time: the numbering run_folder writes under
     HR/); output frames beyond the last file in gt_dir are not scored.  Files are read with PIL and flipped to
-    BGR as run_folder does; numeric names sort by value.  Prints the two averages in the reference's format."""
+    BGR as run_folder does; numeric names sort by value.  `metric` as in evaluate_sequence.  Prints the two
+    averages in the reference's format."""
     from PIL import Image
 
     def read(d, name):
@@ -221,7 +247,7 @@ def evaluate_folder(model, lr_dir: str, gt_dir: str, times=None, scale=None, cha
     nt = len(HARNESS_TIMES if times is None else times)
     gts = [read(gt_dir, nm) for nm in sorted(os.listdir(gt_dir), key=_frame_key)]
     gt = [[gts[i * nt + k] if i * nt + k < len(gts) else None for k in range(nt)] for i in range(len(lr) - 1)]
-    res = evaluate_sequence(model, frames.contiguous(), gt, times, scale, channels)
+    res = evaluate_sequence(model, frames.contiguous(), gt, times, scale, channels, metric)
     print("AVG PSNR: {:.4f}, AVG SSIM: {:.4f}".format(res["avg_psnr"], res["avg_ssim"]))
     return res
 
