@@ -2,7 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 int stif_fail(int code, const char* msg);
 int stif_check_launch(const char* where);
 // compute units of the current device (cached; 256 if the query fails) -- persistent-grid sizing
 int stif_num_cus();
+
+// A runtime bool as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}

@@ -31,7 +31,7 @@
 // 9 K steps per pair instead of 10 for two single groups (tap pairs); epilogue through LDS as k_dcn.
 #include "abi_util.h"
 #include "stif.h"
-#include "stif_common.h"
+#include "dcn_bilinear.h"
 
 #include <algorithm>
 
@@ -68,19 +68,15 @@ constexpr int OFF_XT = 0, OFF_XW = T_INST * 256;
 constexpr int LDS_F = OFF_W + RING * 4096;
 static_assert(WK_F <= 4096 && NW * 1024 <= D_F && LDS_F * 4 <= 80 * 1024 && OFF_XW + PW_PAD_F <= LDS_F, "LDS map");
 
-// vmcnt waits with an immediate operand (the counts are wave-uniform)
+// vmcnt waits with an immediate operand (the counts are wave-uniform): phase 1 waits for everything, for
+// all but the next step's weights, or for all but those and the side stage of the next data chunk
+constexpr int WQ = WK_INS / NW;   // weight DMA instructions per wave and step
+constexpr int DQ = D_INS / NW;    // data DMA instructions per wave and chunk
 STIF_DEV void wait_vm(int n) {
+  static_assert(WQ == 4 && WQ + DQ == 8, "wait_vm's immediates are WQ and WQ + DQ");
   switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
+    case WQ: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case WQ + DQ: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
 }
@@ -114,7 +110,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
   // data chunk c (channels 16c..16c+15) of the 10 x 34 halo: slot s = pixel * 5 + sub (sub 4 = pad)
   auto stage_data = [&](int c, float* dst) {
 #pragma unroll
-    for (int j = 0; j < D_INS / NW; ++j) {
+    for (int j = 0; j < DQ; ++j) {
       const int i = wv + j * NW;
       const int s = i * 64 + lane;
       const int px = s / 5, sub = s - 5 * px;
@@ -130,7 +126,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
   auto stage_w = [&](int k, int slot) {
     float* dst = smem + OFF_W + slot * 4096;
 #pragma unroll
-    for (int j = 0; j < WK_INS / NW; ++j) {
+    for (int j = 0; j < WQ; ++j) {
       const int i = wv + j * NW;
       const unsigned voff = i < MT * 2 ? (unsigned)((k * WK_F + i * 256) * 4 + lane * 16) : 0x80000000u;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rwom, dst + i * 256, 16, voff, 0, 0, 0);
@@ -187,8 +183,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
       const int k = 9 * c + t;
       // this step's weights (and, at a chunk start, its data) landed in every wave; the DMA issued in the
       // last two steps (weights of k + 1, the side stage of tap 1) may stay in flight
-      constexpr int WQ = WK_INS / NW;   // weight DMA instructions per wave and step
-      if (t == 2 || t == 3) wait_vm(c < 3 ? WQ + D_INS / NW : WQ);
+      if (t == 2 || t == 3) wait_vm(c < 3 ? WQ + DQ : WQ);
       else if (t == 8 && c == 3) wait_vm(0);
       else wait_vm(WQ);
       // a bare s_barrier: __syncthreads()'s workgroup fence would wait for vmcnt(0), i.e. for the DMA of
@@ -255,42 +250,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
   report_range(a.status, bad);
 
   // ---------------------------------------------------------------- phase 2: deformable conv
-  // bilinear sample of this lane half's group (channels 16 pa + 8 h .. + 7: a0 = quad 2h, a1 = quad 2h + 1)
-  // at tap `tap` with offset (dy, dx) and modulation m folded into the corner weights; `> -1` / `< H`
-  // gate; global fallback outside the tile
+  // dcn_tile_sample of this lane half's group (channels 16 pa + 8 h .. + 7: a0 = quad 2h, a1 = quad 2h + 1)
+  // at tap `tap` with offset (dy, dx) and modulation mk
   auto sample = [&](const float* st, int pa, int tap, float dy, float dx, float mk, f32x4& a0, f32x4& a1) {
     const int ky = tap / 3, kx = tap - 3 * ky;
     const float h_im = (float)(oy - 1 + ky) + dy;
     const float w_im = (float)(ox - 1 + kx) + dx;
-    const bool valid = pix_ok & (h_im > -1.f) & (w_im > -1.f) & (h_im < (float)H) & (w_im < (float)W);
-    const float fh = floorf(h_im), fw = floorf(w_im);
-    const float lh = h_im - fh, lw = w_im - fw, hh = 1.f - lh, hw = 1.f - lw;
-    const int h_low = (int)fh, w_low = (int)fw;
-    const int r0 = h_low - ty0, c0 = w_low - tx0;
-    const bool in_tile = ((unsigned)r0 < (unsigned)(TR - 1)) & ((unsigned)c0 < (unsigned)(TC - 1));
-    const float m = valid ? mk : 0.f;
-    const float hm = hh * m, lm = lh * m;
-    const float w1 = hm * hw, w2 = hm * lw, w3 = lm * hw, w4 = lm * lw;
-    const float* p0 = st + (((in_tile ? r0 : 0) * 4 + 2 * hf) * TP + (in_tile ? c0 : 0)) * 4;
-    const float* p1 = p0 + 4 * TP * 4;   // next row
-    a0 = w1 * ld4(p0) + w2 * ld4(p0 + 4) + w3 * ld4(p1) + w4 * ld4(p1 + 4);
-    a1 = w1 * ld4(p0 + TP * 4) + w2 * ld4(p0 + TP * 4 + 4) + w3 * ld4(p1 + TP * 4) + w4 * ld4(p1 + TP * 4 + 4);
-    const bool fb = valid & !in_tile;
-    if (__builtin_amdgcn_ballot_w64(fb)) {
-      if (fb) {
-        const int h_high = h_low + 1, w_high = w_low + 1, co = pa * 16 + hf * 8;
-        const bool b1 = h_low >= 0 && w_low >= 0, b2 = h_low >= 0 && w_high <= W - 1;
-        const bool b3 = h_high <= H - 1 && w_low >= 0, b4 = h_high <= H - 1 && w_high <= W - 1;
-        const float* q1 = in + ((size_t)h_low * W + w_low) * 64 + co;
-        const float* q2 = in + ((size_t)h_low * W + w_high) * 64 + co;
-        const float* q3 = in + ((size_t)h_high * W + w_low) * 64 + co;
-        const float* q4 = in + ((size_t)h_high * W + w_high) * 64 + co;
-        const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-        a0 = w1 * (b1 ? ld4(q1) : z) + w2 * (b2 ? ld4(q2) : z) + w3 * (b3 ? ld4(q3) : z) + w4 * (b4 ? ld4(q4) : z);
-        a1 = w1 * (b1 ? ld4(q1 + 4) : z) + w2 * (b2 ? ld4(q2 + 4) : z) + w3 * (b3 ? ld4(q3 + 4) : z) +
-             w4 * (b4 ? ld4(q4 + 4) : z);
-      }
-    }
+    const bool valid = pix_ok & dcn_gate(h_im, w_im, H, W);
+    dcn_tile_sample<4, 1>(st, TR, TC, TP, ty0, tx0, 2 * hf, in, pa * 16 + hf * 8, H, W, h_im, w_im, mk, valid, a0,
+                          a1);
   };
 
   // accumulators start at the DCN bias x 2^14 (lane = output channel)
@@ -323,14 +291,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
       sample(st, pa, t, om[s / 16][s % 16], om[(s + 1) / 16][(s + 1) % 16], om[(s + 2) / 16][(s + 2) % 16], a0, a1);
       f16x8 ah, al;
       split_f16x3(a0, a1, ah, al);
-      const float* wp = sw + t * 1024 + lane * 4;   // [tap][nt][plane][lane][8 halves]
-      const f16x8 bh0 = ldh8(wp), bl0 = ldh8(wp + 256), bh1 = ldh8(wp + 512), bl1 = ldh8(wp + 768);
-      acc0 = mfma16h(ah, bh0, acc0);
-      acc1 = mfma16h(ah, bh1, acc1);
-      acc0 = mfma16h(ah, bl0, acc0);
-      acc1 = mfma16h(ah, bl1, acc1);
-      acc0 = mfma16h(al, bh0, acc0);
-      acc1 = mfma16h(al, bh1, acc1);
+      mfma_f16x3_2nt(ah, al, sw + t * 1024 + lane * 4, acc0, acc1);   // [tap][nt][plane][lane][8 halves]
       __builtin_amdgcn_sched_barrier(0);   // one tap's operands live at a time (VGPR budget)
     }
   }
@@ -338,7 +299,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
   // epilogue through a per-wave LDS block -> coalesced 16-B stores (k_dcn's)
   float* out = a.out[g] + (size_t)n * a.out_item;
   float* blk = smem + OFF_D0 + wv * 1024;
-  const int rpx = lane >> 3, c4 = lane & 7;
   float chk2 = 0.f;
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
@@ -350,13 +310,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
       if (EPI == STIF_EPI_LRELU) t = lrelu01(t);
       v[r] = t;
     }
-    tile_to_lds(blk, v, lane);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int px = i * 8 + rpx, x = ox0 + px;
-      const f32x4 o = lds_row4(blk, px, c4);
-      if (oy < H && x < W) st4(out + ((size_t)oy * W + x) * 64 + nt * 32 + c4 * 4, o);
-    }
+    store_tile_rows(blk, lane, v, out, oy, ox0, H, W, 64, nt * 32);
   }
   report_range(a.status, not_finite(chk2));
 }

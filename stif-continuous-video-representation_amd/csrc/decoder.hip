@@ -1101,12 +1101,6 @@ int window_fail(const char* entry, const char* why) {
   return stif_fail(STIF_E_INVALID, msg);
 }
 
-// A runtime bool as a template argument: f(std::true_type{}) or f(std::false_type{})
-template <class F>
-void with_bool(bool v, F&& f) {
-  if (v) f(std::true_type{});
-  else f(std::false_type{});
-}
 template <int M>
 using Mode = std::integral_constant<int, M>;
 

@@ -59,6 +59,26 @@ STIF_DEV void split_f16x3(f32x4 x0, f32x4 x1, f16x8& h, f16x8& l) {
   l = __builtin_bit_cast(f16x8, lv);
 }
 
+// One split-fp16 K step (16 K values) into two 32-column N-tiles: the B fragments of N-tile nt as packed
+// [nt][plane hi, lo][lane][8 halves] (256 floats per plane) at wp = base + lane * 4, and the three products
+// ah*bh + ah*bl + al*bh per N-tile, interleaved over the two accumulators.  A kernel whose M-tiles share the
+// fragments loads them once and applies them per M-tile.
+struct F16x3Frag2 {
+  f16x8 bh0, bl0, bh1, bl1;
+};
+STIF_DEV F16x3Frag2 ldh8_2nt(const float* wp) { return {ldh8(wp), ldh8(wp + 256), ldh8(wp + 512), ldh8(wp + 768)}; }
+STIF_DEV void mfma_f16x3_2nt(f16x8 ah, f16x8 al, const F16x3Frag2& b, f32x16& acc0, f32x16& acc1) {
+  acc0 = mfma16h(ah, b.bh0, acc0);
+  acc1 = mfma16h(ah, b.bh1, acc1);
+  acc0 = mfma16h(ah, b.bl0, acc0);
+  acc1 = mfma16h(ah, b.bl1, acc1);
+  acc0 = mfma16h(al, b.bh0, acc0);
+  acc1 = mfma16h(al, b.bh1, acc1);
+}
+STIF_DEV void mfma_f16x3_2nt(f16x8 ah, f16x8 al, const float* wp, f32x16& acc0, f32x16& acc1) {
+  mfma_f16x3_2nt(ah, al, ldh8_2nt(wp), acc0, acc1);
+}
+
 // f16x3 operand-range report.  An operand outside the split range (|A * 2^4| > 65504) becomes an fp16
 // infinity, and every product it enters turns into inf or NaN (h = inf, l = -inf: inf - inf), so the
 // outputs it feeds are not finite.  The kernels test their pre-activation outputs with this and set
@@ -142,6 +162,20 @@ STIF_DEV void tile_to_lds(float* blk, const f32x16& v, int lane) {
   }
 }
 STIF_DEV f32x4 lds_row4(const float* blk, int px, int c4) { return ld4(blk + px * 32 + ((c4 ^ (px & 3)) << 2)); }
+// The whole epilogue tail: the tile through the wave's block, then row y of a [H][W][pixel_stride] map, pixels
+// ox0 .. ox0 + 31 clipped to the map, channels ch0 .. ch0 + 31 (8 pixels x 128 B per store instruction).
+// conv.hip's epilogues still spell this out (their RES / LSTM forms interleave other work): the next user.
+STIF_DEV void store_tile_rows(float* blk, int lane, const f32x16& v, float* dst, int y, int ox0, int H, int W,
+                              int pixel_stride, int ch0) {
+  const int rpx = lane >> 3, c4 = lane & 7;
+  tile_to_lds(blk, v, lane);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int px = i * 8 + rpx, x = ox0 + px;
+    const f32x4 o = lds_row4(blk, px, c4);
+    if (y < H && x < W) st4(dst + ((size_t)y * W + x) * pixel_stride + ch0 + c4 * 4, o);
+  }
+}
 
 // Barrier for LDS filled by LDS-DMA (buffer_load/global_load ... lds): the DMA completes
 // asynchronously on each wave's vmcnt and gfx950's back-off barrier does not drain it, so every

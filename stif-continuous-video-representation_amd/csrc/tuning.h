@@ -8,7 +8,7 @@
 #define WINO_OM_RING 2     // k_wino_om B-operand blocks in flight (4: 158 -> 170-177 us, r02_wino_om_ring_ab.log)
 #endif
 
-// ---- k_dcn (dcn.hip): the DCN core of the two-kernel path and the _ext drop-in at the STIF shape
+// ---- k_dcn (dcn.hip): the DCN core of the two-kernel path and of the _ext drop-in (dcn_v2.hip) at the STIF shape
 #ifndef DCN_TH
 // waves per workgroup: 4 (8-row two-row tiles, two workgroups per CU whose barriers and memory waits
 // overlap): C0 L1 DCN 240 -> 223 us against 8 (r02_dcn_th_ab.log)

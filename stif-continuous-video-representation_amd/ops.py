@@ -280,29 +280,39 @@ def dcn_sep(groups, *, epi=L.EPI_NONE, status=None):
     _launch("stif_dcn_sep_nhwc", trace, L.lib().stif_dcn_sep_nhwc, C.byref(a), _stream())
 
 
-def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
-                   dilation_h, dilation_w, deformable_group):
-    """Drop-in for ``_ext.dcn_v2_forward`` (DCNv2/src/dcn_v2.h:9-23): NCHW in, new NCHW tensor out."""
-    for t in (input, weight, bias, offset, mask):
+def _dcn_v2_args(name, tensors, kernel_h, kernel_w, *geom):
+    """The checks both drop-in entry points share (tensors = input, weight, ...): the tensors made contiguous
+    and the 14 shape arguments of the C ABI.  geom: stride, pad, dilation (h, w each) and deformable_group."""
+    for t in tensors:
         if not (t.is_cuda and t.dtype == torch.float32):
-            raise RuntimeError("dcn_v2_forward: tensors must be float32 on the GPU")
-    input, weight, bias, offset, mask = (t.contiguous() for t in (input, weight, bias, offset, mask))
-    b, c, h, w = input.shape
-    co, ci, kh, kw = weight.shape
+            raise RuntimeError(f"{name}: tensors must be float32 on the GPU")
+    tensors = tuple(t.contiguous() for t in tensors)
+    b, c, h, w = tensors[0].shape
+    co, ci, kh, kw = tensors[1].shape
     if (kh, kw) != (kernel_h, kernel_w):
         raise RuntimeError(f"Input shape and kernel shape wont match: ({kernel_h} x {kernel_w} vs {kh} x {kw}).")
     if ci != c:
         raise RuntimeError(f"Input shape and kernel channels wont match: ({c} vs {ci}).")
+    return tensors, (b, c, h, w, co, kernel_h, kernel_w, *geom)
+
+
+def _dcn_v2_workspace(size_fn, dims, device):
+    nbytes = size_fn(*dims)
+    return torch.empty(max(nbytes // 4, 1), device=device, dtype=torch.float32), nbytes
+
+
+def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                   dilation_h, dilation_w, deformable_group):
+    """Drop-in for ``_ext.dcn_v2_forward`` (DCNv2/src/dcn_v2.h:9-23): NCHW in, new NCHW tensor out."""
+    ts, dims = _dcn_v2_args("dcn_v2_forward", (input, weight, bias, offset, mask), kernel_h, kernel_w, stride_h,
+                            stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
+    b, _, h, w, co = dims[:5]
     ho = (h + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
     wo = (w + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
     out = torch.empty(b, co, ho, wo, device=input.device, dtype=torch.float32)
-    lib = L.lib()
-    dims = (b, c, h, w, co, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
-            deformable_group)
-    nbytes = lib.stif_dcn_v2_workspace_size(*dims)
-    ws = torch.empty(max(nbytes // 4, 1), device=input.device, dtype=torch.float32)
-    L.check(lib.stif_dcn_v2_forward(_vp(input), _vp(weight), _vp(bias), _vp(offset), _vp(mask), _vp(out), *dims,
-                                    _vp(ws), nbytes, _stream()), "dcn_v2_forward")
+    ws, nbytes = _dcn_v2_workspace(L.lib().stif_dcn_v2_workspace_size, dims, out.device)
+    L.check(L.lib().stif_dcn_v2_forward(*[_vp(t) for t in ts], _vp(out), *dims, _vp(ws), nbytes, _stream()),
+            "dcn_v2_forward")
     return out
 
 
@@ -311,25 +321,13 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, ke
     """Drop-in for ``_ext.dcn_v2_backward`` (DCNv2/src/dcn_v2.h:39-52): returns new tensors
     (grad_input, grad_offset, grad_mask, grad_weight, grad_bias) in that order, as
     ``_DCNv2.backward`` (DCNv2/dcn_v2.py:31-45) unpacks them."""
-    ts = (input, weight, bias, offset, mask, grad_output)
-    for t in ts:
-        if not (t.is_cuda and t.dtype == torch.float32):
-            raise RuntimeError("dcn_v2_backward: tensors must be float32 on the GPU")
-    input, weight, bias, offset, mask, grad_output = (t.contiguous() for t in ts)
-    b, c, h, w = input.shape
-    co, ci, kh, kw = weight.shape
-    if (kh, kw) != (kernel_h, kernel_w):
-        raise RuntimeError(f"Input shape and kernel shape wont match: ({kernel_h} x {kernel_w} vs {kh} x {kw}).")
-    if ci != c:
-        raise RuntimeError(f"Input shape and kernel channels wont match: ({c} vs {ci}).")
+    ts, dims = _dcn_v2_args("dcn_v2_backward", (input, weight, bias, offset, mask, grad_output), kernel_h, kernel_w,
+                            stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
+    input, weight, bias, offset, mask, _ = ts
     grads = [torch.empty_like(t) for t in (input, offset, mask, weight, bias)]
-    lib = L.lib()
-    dims = (b, c, h, w, co, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
-            deformable_group)
-    nbytes = lib.stif_dcn_v2_backward_workspace_size(*dims)
-    ws = torch.empty(max(nbytes // 4, 1), device=input.device, dtype=torch.float32)
-    L.check(lib.stif_dcn_v2_backward(*[_vp(t) for t in (input, weight, bias, offset, mask, grad_output)],
-                                     *[_vp(g) for g in grads], *dims, _vp(ws), nbytes, _stream()), "dcn_v2_backward")
+    ws, nbytes = _dcn_v2_workspace(L.lib().stif_dcn_v2_backward_workspace_size, dims, input.device)
+    L.check(L.lib().stif_dcn_v2_backward(*[_vp(t) for t in ts], *[_vp(g) for g in grads], *dims, _vp(ws), nbytes,
+                                         _stream()), "dcn_v2_backward")
     return tuple(grads)
 
 
