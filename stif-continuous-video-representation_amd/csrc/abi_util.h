@@ -15,3 +15,9 @@ void with_bool(bool v, F&& f) {
   if (v) f(std::true_type{});
   else f(std::false_type{});
 }
+// A runtime int as a template argument, over the values it may take: f(std::integral_constant<int, V>{}) for
+// the V that equals v; false (f not called) if none does
+template <int... Vs, class F>
+bool with_int(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}

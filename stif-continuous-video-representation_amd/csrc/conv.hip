@@ -106,7 +106,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv(stif_conv_args a) {
   };
   f32x4 ur[EPT][4];
   float uw[EPT][4];
-  auto up_issue = [&](int c) {   // F.interpolate(x2, bilinear, align_corners=False) corner loads
+  auto up_issue = [&](int c) {   // F.interpolate(x2, bilinear, align_corners=False) corner loads (up2_src)
     const int co = (c - NC0) * 8;
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
@@ -114,11 +114,9 @@ __global__ __launch_bounds__(NW * 64) void k_conv(stif_conv_args a) {
       const int col = e % HC, rh = e / HC, h = rh & 1, row = rh >> 1;
       const int y = iy0 + row, x = ix0 + col;
       const bool ok = e < IN_EL && y >= 0 && y < H && x >= 0 && x < W;
-      const float sy = fmaxf(0.5f * ((float)y + 0.5f) - 0.5f, 0.f);
-      const float sx = fmaxf(0.5f * ((float)x + 0.5f) - 0.5f, 0.f);
-      const int y0 = min((int)sy, H1 - 1), x0 = min((int)sx, W1 - 1);
-      const int y1 = y0 + (y0 < H1 - 1 ? 1 : 0), x1 = x0 + (x0 < W1 - 1 ? 1 : 0);
-      const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
+      const Up2Src sy = up2_src(y, H1), sx = up2_src(x, W1);
+      const int y0 = sy.i0, y1 = sy.i1, x0 = sx.i0, x1 = sx.i1;
+      const float ly1 = sy.frac, lx1 = sx.frac;
       uw[k][0] = ok ? 1.f - ly1 : 0.f;
       uw[k][1] = ok ? ly1 : 0.f;
       uw[k][2] = 1.f - lx1;
@@ -503,18 +501,13 @@ extern "C" int stif_conv2d_nhwc(const stif_conv_args* pa, void* stream) {
     return stif_fail(STIF_E_INVALID, "1x1 conv: unsupported in1 mode");
   }
   // 3x3 stride 1
-#define STIF_CONV_CASE(IN1)                                                   \
-  switch (a.epi) {                                                            \
-    case STIF_EPI_NONE: return launch<3, 1, 2, 2, 4, IN1, STIF_EPI_NONE>(a, st); \
-    case STIF_EPI_LRELU: return launch<3, 1, 2, 2, 4, IN1, STIF_EPI_LRELU>(a, st); \
-    case STIF_EPI_RELU: return launch<3, 1, 2, 2, 4, IN1, STIF_EPI_RELU>(a, st); \
-    case STIF_EPI_RES: return launch<3, 1, 2, 2, 4, IN1, STIF_EPI_RES>(a, st);   \
-    default: break;                                                           \
-  }
-  if (a.in1_mode == 0) { STIF_CONV_CASE(0) }
-  else if (a.in1_mode == 1) { STIF_CONV_CASE(1) }
-  else if (a.in1_mode == 2) { STIF_CONV_CASE(2) }
-#undef STIF_CONV_CASE
+  int rc = STIF_OK;
+  bool ok = false;
+  with_int<0, 1, 2>(a.in1_mode, [&](auto in1) {
+    ok = with_int<STIF_EPI_NONE, STIF_EPI_LRELU, STIF_EPI_RELU, STIF_EPI_RES>(
+        a.epi, [&](auto epi) { rc = launch<3, 1, 2, 2, 4, decltype(in1)::value, decltype(epi)::value>(a, st); });
+  });
+  if (ok) return rc;
   return stif_fail(STIF_E_INVALID, "stif_conv2d_nhwc: unsupported combination");
 }
 

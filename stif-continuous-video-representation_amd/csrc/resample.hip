@@ -23,13 +23,9 @@ __global__ __launch_bounds__(256) void k_up2(const float* __restrict__ in, float
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= W * c4n) return;
   const int x = t / c4n, q = t - x * c4n;
-  // align_corners=False source coordinates (clamped at 0 like ATen's area_pixel_compute_source_index)
-  const float sy = fmaxf(0.5f * ((float)y + 0.5f) - 0.5f, 0.f);
-  const float sx = fmaxf(0.5f * ((float)x + 0.5f) - 0.5f, 0.f);
-  const int y0 = min((int)sy, h1 - 1), x0 = min((int)sx, w1 - 1);
-  const int y1 = y0 + (y0 < h1 - 1 ? 1 : 0), x1 = x0 + (x0 < w1 - 1 ? 1 : 0);
-  const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
-  const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+  const Up2Src sy = up2_src(y, h1), sx = up2_src(x, w1);
+  const int y0 = sy.i0, y1 = sy.i1, x0 = sx.i0, x1 = sx.i1;
+  const float ly1 = sy.frac, lx1 = sx.frac, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
   const float* src = in + (size_t)item * in_item + q * 4;
   const f32x4 v00 = ld4(src + ((size_t)y0 * w1 + x0) * c), v01 = ld4(src + ((size_t)y0 * w1 + x1) * c);
   const f32x4 v10 = ld4(src + ((size_t)y1 * w1 + x0) * c), v11 = ld4(src + ((size_t)y1 * w1 + x1) * c);
@@ -40,7 +36,7 @@ __global__ __launch_bounds__(256) void k_up2(const float* __restrict__ in, float
 // one thread = 4 channels of the 2x2 output quad of input pixel (i, j): rows 2i, 2i+1, columns 2j,
 // 2j+1.  Every corner of those four outputs lies in the 3x3 input neighbourhood of (i, j), so the
 // thread loads 9 float4s for 4 outputs (16 with k_up2) and evaluates each output with k_up2's
-// coordinates, weights and expression (same rounding).  grid (x blocks over w1 * c/4, input row i, item)
+// coordinates (up2_src), weights and expression (same rounding).  grid (x blocks over w1 * c/4, input row i, item)
 STIF_DEV f32x4 sel3(int s, f32x4 a, f32x4 b, f32x4 c) { return s == 0 ? a : (s == 1 ? b : c); }
 
 __global__ __launch_bounds__(256) void k_up2q(const float* __restrict__ in, float* __restrict__ out, int n, int h1,
@@ -66,19 +62,15 @@ __global__ __launch_bounds__(256) void k_up2q(const float* __restrict__ in, floa
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
     const int y = 2 * i + a;
-    const float sy = fmaxf(0.5f * ((float)y + 0.5f) - 0.5f, 0.f);
-    const int y0 = min((int)sy, h1 - 1);
-    const int y1 = y0 + (y0 < h1 - 1 ? 1 : 0);
-    const float ly1 = sy - (float)y0, ly0 = 1.f - ly1;
-    const int sy0 = y0 - i + 1, sy1 = y1 - i + 1;
+    const Up2Src sy = up2_src(y, h1);
+    const float ly1 = sy.frac, ly0 = 1.f - ly1;
+    const int sy0 = sy.i0 - i + 1, sy1 = sy.i1 - i + 1;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       const int x = 2 * j + b;
-      const float sx = fmaxf(0.5f * ((float)x + 0.5f) - 0.5f, 0.f);
-      const int x0 = min((int)sx, w1 - 1);
-      const int x1 = x0 + (x0 < w1 - 1 ? 1 : 0);
-      const float lx1 = sx - (float)x0, lx0 = 1.f - lx1;
-      const int sx0 = x0 - j + 1, sx1 = x1 - j + 1;
+      const Up2Src sx = up2_src(x, w1);
+      const float lx1 = sx.frac, lx0 = 1.f - lx1;
+      const int sx0 = sx.i0 - j + 1, sx1 = sx.i1 - j + 1;
       const f32x4 u0 = sel3(sy0, R[0][0], R[1][0], R[2][0]), u1 = sel3(sy0, R[0][1], R[1][1], R[2][1]),
                   u2 = sel3(sy0, R[0][2], R[1][2], R[2][2]);
       const f32x4 d0 = sel3(sy1, R[0][0], R[1][0], R[2][0]), d1 = sel3(sy1, R[0][1], R[1][1], R[2][1]),
@@ -131,6 +123,7 @@ __global__ __launch_bounds__(256) void k_up_img(const float* __restrict__ x, flo
     const int Y = (int)(r % H);
     const int item = (int)(r / H);
     // ATen upsample_bilinear2d, align_corners=False, scale_factor given: src = (d + 0.5) / s - 0.5, >= 0
+    // (the general form: 1 / s and its product round where up2_src's 0.5 * (d + 0.5) is exact, so it stays as written)
     const float sy = fmaxf(((float)Y + 0.5f) * inv - 0.5f, 0.f);
     const float sx = fmaxf(((float)X + 0.5f) * inv - 0.5f, 0.f);
     const int y0 = min((int)sy, h - 1), x0 = min((int)sx, w - 1);

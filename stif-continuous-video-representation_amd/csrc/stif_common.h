@@ -100,6 +100,21 @@ STIF_DEV float sigmoid_fast(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
 }
 
+// One axis of F.interpolate(scale_factor=2, mode='bilinear', align_corners=False): output index d of a map
+// upsampled from n1 samples blends source samples i0 and i1 with weights (1 - frac, frac).  The source
+// coordinate is clamped at 0 like ATen's area_pixel_compute_source_index.  Every x2 site takes its
+// coordinates from here and keeps its own expression of the blend (k_up_img's general 1 / s form rounds
+// differently and stays as written).
+struct Up2Src {
+  int i0, i1;
+  float frac;
+};
+STIF_DEV Up2Src up2_src(int d, int n1) {
+  const float s = fmaxf(0.5f * ((float)d + 0.5f) - 0.5f, 0.f);
+  const int i0 = min((int)s, n1 - 1);
+  return {i0, i0 + (i0 < n1 - 1 ? 1 : 0), s - (float)i0};
+}
+
 enum { STIF_ACT_NONE = 0, STIF_ACT_LRELU = 1, STIF_ACT_RELU = 2, STIF_ACT_RES = 3,
        STIF_ACT_OFFMASK = 4, STIF_ACT_LSTM = 5 };
 

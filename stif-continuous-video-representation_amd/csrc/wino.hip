@@ -22,6 +22,10 @@
 // Input halo tiles (6 rows x 34 columns x 32 channels per phase) are LDS-DMA'd, double-buffered,
 // even and odd columns in separate runs, a pixel's channel chunks consecutive (coalesced loads) at an
 // odd pitch (conflict-free transform reads).
+//
+// Two kernels, k_wino (one 64-cout slice per tile) and k_wino_om (the 64 -> 216 offset/mask conv, all couts
+// per tile), share at file scope the staging image (stage_image), the tile walk (xcd_tile_range, tile_of), the
+// input transform row (XRow) and the output-transform exchange (ex_col_sums / ex_write / ex_read).
 #include "abi_util.h"
 #include "stif.h"
 #include "stif_common.h"
@@ -85,16 +89,110 @@ STIF_DEV void stage_image(__amdgpu_buffer_rsrc_t rs, float* dst, int iy0, int ix
 // phases stage the 4 x 18 coarse pixels under a tile's 6 x 34 halo (coarse rows oy0/2 - 1 .. +2,
 // columns ox0/2 - 1 .. +16) into a scratch area by LDS-DMA, and between phases the workgroup expands
 // them into the phase image with F.interpolate(scale_factor=2, bilinear, align_corners=False)
-// arithmetic (k_up2's expression) times s -- the upsampled map is never written to HBM.
+// arithmetic (up2_src and k_up2's blend) times s -- the upsampled map is never written to HBM.
 constexpr int UP_R = 4, UP_C = 18;                    // coarse rows / columns per tile
 constexpr int SCR_F = UP_R * UP_C * 2 * PSUB * 4;      // scratch floats: [row][col][chunk][4]
 constexpr int SCR_INS = (UP_R * UP_C * 2 * PSUB + 63) / 64;
 
+// ---- the tile walk.  XCD-aware persistent schedule: workgroup b is dispatched to XCD b % 8, and XCD x
+// owns the contiguous tile range [x * per, (x + 1) * per) -- tiles that share input (cout slices, halo
+// rows) run at the same time under the same L2 -- which its workgroups stride through.
+struct TileRange {
+  int lo, T, end, stride;   // the XCD's first tile; this workgroup's first tile, the range's end, the stride
+};
+STIF_DEV TileRange xcd_tile_range(int ntiles) {
+  const int xcd = blockIdx.x & 7, per = (ntiles + 7) >> 3;   // host: grid is a multiple of 8
+  const int end = min((xcd + 1) * per, ntiles);
+  return {xcd * per, (int)(xcd * per + (blockIdx.x >> 3)), end, (int)(gridDim.x >> 3)};
+}
 struct Tile {
   int oy0, ox0, slice, g, n;
-  const float* src0;   // the item's input maps (k_wino: in0 and in1 of group g, item n), loaded from the
-  const float* src1;   // kernel arguments once per tile, not per staging phase
 };
+// tile order: cout slice fastest (the slices of one spatial tile share its input), then x, y, item
+// (k_wino_om: one slice, a workgroup computes all couts)
+STIF_DEV Tile tile_of(int T, int slices, int tiles_x, int tiles_y, int nitems) {
+  Tile t;
+  t.slice = T % slices;
+  int r = T / slices;
+  const int x = r % tiles_x;
+  r /= tiles_x;
+  const int y = r % tiles_y;
+  r /= tiles_y;
+  t.g = r / nitems;
+  t.n = r - t.g * nitems;
+  t.oy0 = y * WR;
+  t.ox0 = x * 32;
+  return t;
+}
+
+// ---- the input transform.  Row i (= wave i) of B^T d B for lane's Winograd tile (lane & 31) and channels
+// 4h..4h+3 (h = lane >> 5) of an 8-channel chunk: the wave's MFMA A operands for xi = 4i + j.  Split in
+// the LDS reads (issued one chunk ahead where registers allow, so their latency hides under the current
+// chunk's MFMAs) and the add/subtract part.
+struct XRow {
+  int rA, rB;           // rows of the 4x4 patch feeding transform row i: (B^T d)_i = d[rA] + sB * d[rB]
+  float sB;
+  int s0, s1, s2, s3;   // column slots of the patch's four columns
+  int tyl, hf;
+  STIF_DEV XRow(int wi, int lane)
+      : rA((wi == 0) ? 0 : (wi == 2 ? 2 : 1)), rB((wi == 3) ? 3 : (wi == 2 ? 1 : 2)), sB((wi == 1) ? 1.f : -1.f),
+        s0(col_slot(0) + (lane & 15)), s1(col_slot(1) + (lane & 15)), s2(col_slot(2) + (lane & 15)),
+        s3(col_slot(3) + (lane & 15)), tyl((lane & 31) >> 4), hf(lane >> 5) {}
+  // chunk s of the phase image `buf`; s enters as a pointer offset so that it becomes the ds_read's immediate
+  // (inside the index the compiler ORs it into one address VGPR per chunk: 6 VGPRs the F16 kernels do not have)
+  STIF_DEV void read(const float* buf, int s, f32x4* rd) const {
+    const float* ra = buf + ((2 * tyl + rA) * OM_RP + hf) * 4 + s * 8;
+    const float* rb = buf + ((2 * tyl + rB) * OM_RP + hf) * 4 + s * 8;
+    rd[0] = ld4(ra + s0 * PITCH * 4); rd[1] = ld4(rb + s0 * PITCH * 4);
+    rd[2] = ld4(ra + s1 * PITCH * 4); rd[3] = ld4(rb + s1 * PITCH * 4);
+    rd[4] = ld4(ra + s2 * PITCH * 4); rd[5] = ld4(rb + s2 * PITCH * 4);
+    rd[6] = ld4(ra + s3 * PITCH * 4); rd[7] = ld4(rb + s3 * PITCH * 4);
+  }
+  STIF_DEV void form(const f32x4* rd, f32x4* v) const {
+    const f32x4 t0 = rd[0] + sB * rd[1];
+    const f32x4 t1 = rd[2] + sB * rd[3];
+    const f32x4 t2 = rd[4] + sB * rd[5];
+    const f32x4 t3 = rd[6] + sB * rd[7];
+    v[0] = t0 - t2;
+    v[1] = t1 + t2;
+    v[2] = t2 - t1;
+    v[3] = t1 - t3;
+  }
+};
+
+// ---- the output transform, balanced over all waves.  Wave i holds P_i[b] = sum_j M[i][j] A[j][b]
+// (registers, ex_col_sums); Y[0] = P_0 + P_1 + P_2, Y[1] = P_1 - P_2 - P_3.  Per 32-cout half the waves
+// write their P_i into the exchange image transposed to [i][b][tile][co] (ex_write), then every thread
+// combines (ex_read) and stores (pixel, 4-cout) vectors as coalesced 16-B accesses (8 lanes = one pixel's
+// 128 B).  Row swizzle R ^ (bit2(tile) ^ b) keeps both the b32 writes (lane halves 4 tiles apart) and the
+// b128 reads (16-lane groups = b 0/1 of one tile) conflict-free.
+// Exchange addresses as a per-lane base plus compile-time offsets (no hoisted address VGPRs):
+//   writer (m = mfma_row(r, lane), bit2(m) = hf): row bit 0 is flipped iff hf ^ b, i.e.
+//   +32 floats for even r, -32 for odd r;  reader (m = 16(k >> 1) + txo): bit2(m) = bit2(txo).
+STIF_DEV void ex_col_sums(const f32x16& m0, const f32x16& m1, const f32x16& m2, const f32x16& m3, f32x16* yv) {
+  yv[0] = m0 + m1 + m2;
+  yv[1] = m1 - m2 - m3;
+}
+STIF_DEV void ex_write(float* ex, int wi, int lane, const f32x16* yv) {
+  const int hf = lane >> 5, tl = lane & 31;
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const int fl = (hf ^ b) * 32;
+    float* wb = ex + ((wi * 2 + b) * 32 + 4 * hf) * 32 + tl;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) wb[((r & 3) + 8 * (r >> 2)) * 32 + ((r & 1) ? -fl : fl)] = yv[b][r];
+  }
+}
+// thread tid's outputs: cout quad c4 = tid & 7 of the half, column oxl = (tid >> 3) & 31 of the tile, rows
+// k = 0..3; returns y of row k before scale and bias
+STIF_DEV f32x4 ex_read(const float* ex, int tid, int k) {
+  const int c4 = tid & 7, oxl = (tid >> 3) & 31;
+  const int bb = oxl & 1, txo = oxl >> 1;
+  const float* rbase = ex + (bb * 32 + (txo ^ (((txo >> 2) ^ bb) & 1))) * 32 + c4 * 4 + (k >> 1) * 512;
+  const f32x4 p1 = ld4(rbase + 1 * 2048), p2 = ld4(rbase + 2 * 2048);
+  const f32x4 pe = ld4(rbase + ((k & 1) ? 3 : 0) * 2048);
+  return (k & 1) ? (p1 - p2 - pe) : (pe + p1 + p2);
+}
 
 // Persistent: WG_PER_CU workgroups per CU walk the tiles (tile = 4 output rows x 32 columns x one
 // 64-cout slice of one item), and the last staging phase of a tile already LDS-DMAs the first
@@ -115,9 +213,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wi = __builtin_amdgcn_readfirstlane(tid >> 6);   // transform row i of this wave
-  const int hf = lane >> 5;
-  const int tl = lane & 31;                                  // Winograd tile of this lane
-  const int tyl = tl >> 4, txl = tl & 15;
 
   const int tiles_x = (a.Wo + 31) >> 5;
   const int tiles_y = (a.Ho + WR - 1) / WR;
@@ -128,22 +223,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const int NP = NC / PSUB;   // host guarantees NC % PSUB == 0
   const int NQ = NC >> 1;     // F16: 16-channel chunk pairs
 
-  // tile order: cout slice fastest (the slices of one spatial tile share its input), then x, y, item
-  auto tile_of = [&](int T) {
-    Tile t;
-    t.slice = T % slices;
-    int r = T / slices;
-    const int x = r % tiles_x;
-    r /= tiles_x;
-    const int y = r % tiles_y;
-    r /= tiles_y;
-    t.g = r / a.nitems;
-    t.n = r - t.g * a.nitems;
-    t.oy0 = y * WR;
-    t.ox0 = x * 32;
-    t.src0 = a.in0[t.g] + (size_t)t.n * a.in0_item;
-    t.src1 = IN1 ? a.in1[t.g] + (size_t)t.n * a.in1_item : t.src0;
-    return t;
+  // a tile and its item's input maps (in0 and in1 of group g, item n), loaded from the kernel arguments
+  // once per tile, not per staging phase
+  struct WTile : Tile {
+    const float *src0, *src1;
+  };
+  auto wtile_of = [&](int T) {
+    const Tile t = tile_of(T, slices, tiles_x, tiles_y, a.nitems);
+    const float* src0 = a.in0[t.g] + (size_t)t.n * a.in0_item;
+    return WTile{t, src0, IN1 ? a.in1[t.g] + (size_t)t.n * a.in1_item : src0};
   };
   // packed U: [slice][chunk][i][j][nt][lane][4]; B fragment (j, local half u) at wsl + (j*2 + u)*256
   // F16 (STIF_PACK_F16X3): [slice][pair][i][j][u][plane h|l][lane][8 halves]; fragment (j, u, plane)
@@ -156,7 +244,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   // staging image (stage_image): DMA instruction (r, m) = wave wi's ins = wi, wi + 4, ... of 30
   const int lpx = lane / 9, lck = lane - 9 * (lane / 9);
   const int h1 = H >> 1, w1 = W >> 1;   // IN1 = 2: the coarse map's size
-  auto stage = [&](const Tile& t, int p, int buf) {
+  auto stage = [&](const WTile& t, int p, int buf) {
     // a phase lies entirely in one input (NC0 % PSUB == 0, host-checked)
     const bool second = IN1 && p * PSUB >= NC0;
     const float* src = second ? t.src1 : t.src0;
@@ -187,22 +275,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   // borders -- and the same for columns.  So a thread takes a 2 x 2 quad of halo pixels for one 16-B
   // channel chunk: 4 coarse reads and 8 lerps for 4 outputs (the per-pixel form needs 16 reads and 12).
   // Quads that touch a map border (clamped source coordinates, or pixels outside the map) take the
-  // per-pixel k_up2 expression.  The scale s (2 or 1 in the model) is folded into the row weights.
-  auto expand_px = [&](const Tile& t, int r, int c, int ch) {   // k_up2's expression for one pixel
+  // per-pixel form (up2_src, k_up2's blend).  The scale s (2 or 1 in the model) is folded into the row weights.
+  auto expand_px = [&](const Tile& t, int r, int c, int ch) {
     const int cy0 = (t.oy0 >> 1) - 1, cx0 = (t.ox0 >> 1) - 1;
     const int Y = t.oy0 - 1 + r, X = t.ox0 - 1 + c;
     f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
     if (((unsigned)Y < (unsigned)H) & ((unsigned)X < (unsigned)W)) {
-      const float sy = fmaxf(0.5f * ((float)Y + 0.5f) - 0.5f, 0.f);
-      const float sx = fmaxf(0.5f * ((float)X + 0.5f) - 0.5f, 0.f);
-      const int y0 = min((int)sy, h1 - 1), x0 = min((int)sx, w1 - 1);
-      const int y1 = y0 + (y0 < h1 - 1 ? 1 : 0), x1 = x0 + (x0 < w1 - 1 ? 1 : 0);
-      const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
-      const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-      const float* s0 = scr + ((y0 - cy0) * UP_C) * 32 + ch * 4;
-      const float* s1 = scr + ((y1 - cy0) * UP_C) * 32 + ch * 4;
-      const f32x4 v00 = ld4(s0 + (x0 - cx0) * 32), v01 = ld4(s0 + (x1 - cx0) * 32);
-      const f32x4 v10 = ld4(s1 + (x0 - cx0) * 32), v11 = ld4(s1 + (x1 - cx0) * 32);
+      const Up2Src sy = up2_src(Y, h1), sx = up2_src(X, w1);
+      const float ly1 = sy.frac, lx1 = sx.frac, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+      const float* s0 = scr + ((sy.i0 - cy0) * UP_C) * 32 + ch * 4;
+      const float* s1 = scr + ((sy.i1 - cy0) * UP_C) * 32 + ch * 4;
+      const f32x4 v00 = ld4(s0 + (sx.i0 - cx0) * 32), v01 = ld4(s0 + (sx.i1 - cx0) * 32);
+      const f32x4 v10 = ld4(s1 + (sx.i0 - cx0) * 32), v11 = ld4(s1 + (sx.i1 - cx0) * 32);
       v = (ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11)) * a.in1_scale;
     }
     return v;
@@ -237,55 +321,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   };
   auto up_phase = [&](int p) { return IN1 == 2 && p * PSUB >= NC0; };
 
-  // rows of the 4x4 patch feeding transform row i: (B^T d)_i = d[rA] + sB * d[rB]
-  const int rA = (wi == 0) ? 0 : (wi == 2 ? 2 : 1);
-  const int rB = (wi == 3) ? 3 : (wi == 2 ? 1 : 2);
-  const float sB = (wi == 1) ? 1.f : -1.f;
-  const int s0 = col_slot(0) + txl, s1 = col_slot(1) + txl, s2 = col_slot(2) + txl, s3 = col_slot(3) + txl;
+  const XRow xr(wi, lane);
 
-  // input transform row i of 8-channel chunk s of the phase in `buf`, for this lane's tile and
-  // channels 4h..4h+3: the wave's MFMA A operands for xi = 4i + j.  Split in the LDS reads (issued
-  // one chunk ahead where registers allow, so their latency hides under the current chunk's MFMAs)
-  // and the add/subtract part.
-  auto xread = [&](const float* buf, int s, f32x4* rd) {
-    const float* ra = buf + ((2 * tyl + rA) * OM_RP + 2 * s + hf) * 4;
-    const float* rb = buf + ((2 * tyl + rB) * OM_RP + 2 * s + hf) * 4;
-    rd[0] = ld4(ra + s0 * PITCH * 4); rd[1] = ld4(rb + s0 * PITCH * 4);
-    rd[2] = ld4(ra + s1 * PITCH * 4); rd[3] = ld4(rb + s1 * PITCH * 4);
-    rd[4] = ld4(ra + s2 * PITCH * 4); rd[5] = ld4(rb + s2 * PITCH * 4);
-    rd[6] = ld4(ra + s3 * PITCH * 4); rd[7] = ld4(rb + s3 * PITCH * 4);
-  };
-  auto xform = [&](const f32x4* rd, f32x4* v) {
-    const f32x4 t0 = rd[0] + sB * rd[1];
-    const f32x4 t1 = rd[2] + sB * rd[3];
-    const f32x4 t2 = rd[4] + sB * rd[5];
-    const f32x4 t3 = rd[6] + sB * rd[7];
-    v[0] = t0 - t2;
-    v[1] = t1 + t2;
-    v[2] = t2 - t1;
-    v[3] = t1 - t3;
-  };
-
-  // XCD-aware persistent schedule: workgroup b is dispatched to XCD b % 8, and XCD x owns the
-  // contiguous tile range [x * per, (x + 1) * per) -- tiles that share input (cout slices, halo rows)
-  // run at the same time under the same L2.  Static (a.sched == nullptr): the XCD's workgroups stride
-  // through it.  Dynamic (a.sched: this stream's 8 counters): the first two tiles are static, the rest
+  // The tile walk (xcd_tile_range).  Static (a.sched == nullptr): the XCD's workgroups stride through its
+  // range.  Dynamic (a.sched: this stream's 8 counters): the first two tiles are static, the rest
   // are taken from the XCD's counter (relative to its value before the launch, sb), one workgroup-wide
   // atomic fetched a tile ahead -- a workgroup that started late (another stream's kernel held the CU)
   // takes fewer tiles instead of finishing late.  Outputs do not depend on it.
-  const int xcd = blockIdx.x & 7, nl = gridDim.x >> 3;   // host: grid is a multiple of 8
-  const int per = (ntiles + 7) >> 3;
-  const int tend = min((xcd + 1) * per, ntiles);
+  const TileRange tr = xcd_tile_range(ntiles);
+  const int xcd = blockIdx.x & 7, nl = tr.stride, tend = tr.end;
   // (the fp32-operand variants -- the range re-run -- keep the static schedule: no registers to spare)
   int* const sched = a.sched;
   const bool dyn = F16 && sched != nullptr;
   __shared__ int tslot[2];                                // fetched tile indices, by tile parity
-  int T = xcd * per + (blockIdx.x >> 3);
+  int T = tr.T;
   int Tn = T + nl;                                        // the next tile (static for the first two)
-  const int dbase = xcd * per + 2 * nl;                   // dynamic tile d = dbase + counter value
+  const int dbase = tr.lo + 2 * nl;                       // dynamic tile d = dbase + counter value
   int par = 0;
   if (T < tend) {
-  Tile cur = tile_of(T);
+  WTile cur = wtile_of(T);
   const float* wsl = wbase(cur);
   f32x4 bw[4][2];
   // F16: B operand ring over the (pair, j) blocks, two blocks deep: slot j & 1 holds block j's
@@ -311,7 +365,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 
   for (;;) {
     const bool has_next = Tn < tend;
-    const Tile nxt = tile_of(has_next ? Tn : T);
+    const WTile nxt = wtile_of(has_next ? Tn : T);
     const float* wnx = wbase(nxt);
     // dynamic: the tile after next, consumed at the next tile's top (written to tslot after phase 0's
     // barrier, when every wave has read the previous value)
@@ -330,6 +384,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
       Tn = dyn ? dbase + tslot[par] : Tn + nl;
       par ^= 1;
     };
+    // the LDS-DMA a phase issues: the tile's next phase, or after its last one the next tile's phase 0
+    auto stage_next = [&](int p) {
+      if (p + 1 < NP) stage(cur, p + 1, (gp + 1) & 1);
+      else if (has_next) stage(nxt, 0, (gp + 1) & 1);
+    };
+    // A phase's end.  Every load older than the last 8 B-operand loads (F16: the last two blocks' refills;
+    // fp32: the last chunk's prefetches) -- the phase's LDS-DMA among them -- has landed; those 8 stay in
+    // flight across the barrier.  (The IN1 = 2 expand of the coarse patch just landed follows in both bodies,
+    // spelled out: inside this lambda it costs k_wino<2, *, 0> a spilled VGPR.)
+    auto end_phase = [&](int p) {
+      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      __syncthreads();
+      publish(p);
+    };
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -343,18 +411,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
         f32x4 rd[8];
         // the phase's first LDS reads go out before the next phase's LDS-DMA is issued, so the DMA
         // issue (~1K cycles per wave) overlaps their latency instead of preceding it
-        xread(buf, 0, rd);
-        if (p + 1 < NP) stage(cur, p + 1, (gp + 1) & 1);
-        else if (has_next) stage(nxt, 0, (gp + 1) & 1);
+        xr.read(buf, 0, rd);
+        stage_next(p);
 #pragma unroll
         for (int sp = 0; sp < PSUB / 2; ++sp) {
           // chunk pair (2 sp, 2 sp + 1): lane half h holds channels 4h..4h+3 of both, i.e. the 8
           // K values of a 32x32x16 f16 MFMA; transform both, split all four j, then fetch the next
           // pair's first chunk so its LDS reads hide under this pair's MFMAs
           f32x4 va[4], vb[4];
-          xform(rd, va);
-          xread(buf, 2 * sp + 1, rd);
-          xform(rd, vb);
+          xr.form(rd, va);
+          xr.read(buf, 2 * sp + 1, rd);
+          xr.form(rd, vb);
           const int q = p * (PSUB / 2) + sp;
           const float* wq = wsl + (size_t)q * 16384;
           const float* wq1 = q + 1 < NQ ? wq + 16384 : wnx;
@@ -362,7 +429,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
           for (int j = 0; j < 4; ++j) {
             f16x8 ah, al;
             split_f16x3(va[j], vb[j], ah, al);
-            if (j == XREAD_J && 2 * sp + 2 < PSUB) xread(buf, 2 * sp + 2, rd);
+            if (j == XREAD_J && 2 * sp + 2 < PSUB) xr.read(buf, 2 * sp + 2, rd);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
               acc[j][u] = mfma16h(ah, bh[j & 1][u], acc[j][u]);
@@ -379,11 +446,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-        // every load older than the last two blocks' B refills (8) -- the phase's LDS-DMA among
-        // them -- has landed
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        __syncthreads();
-        publish(p);
+        end_phase(p);
         if (IN1 == 2 && p + 1 < NP && up_phase(p + 1)) {
           expand(cur, (gp + 1) & 1);
           __syncthreads();
@@ -391,16 +454,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
       }
     } else
     for (int p = 0; p < NP; ++p, ++gp) {
-      if (p + 1 < NP) stage(cur, p + 1, (gp + 1) & 1);
-      else if (has_next) stage(nxt, 0, (gp + 1) & 1);
+      stage_next(p);
       const float* buf = smem + (gp & 1) * BUF_F;
       f32x4 rd[8];
-      xread(buf, 0, rd);
+      xr.read(buf, 0, rd);
 #pragma unroll
       for (int s = 0; s < PSUB; ++s) {
         f32x4 v[4];
-        xform(rd, v);
-        if (s + 1 < PSUB) xread(buf, s + 1, rd);
+        xr.form(rd, v);
+        if (s + 1 < PSUB) xr.read(buf, s + 1, rd);
         // B operands of the next chunk (the next tile's first chunk after the last one).  bw[j] is
         // reloaded right after its MFMAs, 3/4 of a chunk before its next use; the scheduling
         // barriers keep the compiler from sinking those loads next to their use, which would
@@ -418,38 +480,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      // every load older than the last chunk's B-operand prefetches -- the phase's LDS-DMA among
-      // them -- has landed; those 8 stay in flight across the barrier
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      __syncthreads();
-      publish(p);
+      end_phase(p);
       if (IN1 == 2 && p + 1 < NP && up_phase(p + 1)) {
         expand(cur, (gp + 1) & 1);
         __syncthreads();
       }
     }
 
-    // ---- output transform, balanced over all waves.  Wave i holds P_i[b] = sum_j M[i][j] A[j][b]
-    // (registers); Y[0] = P_0 + P_1 + P_2, Y[1] = P_1 - P_2 - P_3.  Two rounds (32-cout halves nt):
-    // the waves write their P_i[nt] into the buffer of the phase just finished (free after the
-    // barrier; the other one is receiving the next tile) transposed to [i][b][tile][co], then every
-    // thread combines and stores (pixel, 4-cout) vectors as coalesced 16-B accesses (8 lanes = one
-    // pixel's 128 B).  Row swizzle R ^ (bit2(tile) ^ b) keeps both the b32 writes (lane halves 4
-    // tiles apart) and the b128 reads (16-lane groups = b 0/1 of one tile) conflict-free.
+    // ---- output transform (ex_col_sums / ex_write / ex_read), two rounds (32-cout halves nt).  The
+    // exchange image is the buffer of the phase just finished (free after the barrier; the other one is
+    // receiving the next tile).
     float* ex = smem + ((gp - 1) & 1) * BUF_F;
     f32x16 yv[2][2];   // [local half][b]
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      yv[u][0] = acc[0][u] + acc[1][u] + acc[2][u];
-      yv[u][1] = acc[1][u] - acc[2][u] - acc[3][u];
-    }
-    // Exchange addresses as a per-lane base plus compile-time offsets (no hoisted address VGPRs):
-    //   writer (m = mfma_row(r, lane), bit2(m) = hf): row bit 0 is flipped iff hf ^ b, i.e.
-    //   +32 floats for even r, -32 for odd r;  reader (m = 16(k >> 1) + txo): bit2(m) = bit2(txo).
-    // this thread's outputs: cout quad c4, column ox of the tile, rows k = 0..3
-    const int c4 = tid & 7, oxl = (tid >> 3) & 31;
-    const int ox = cur.ox0 + oxl;
-    const int bb = oxl & 1, txo = oxl >> 1;
+    for (int u = 0; u < 2; ++u) ex_col_sums(acc[0][u], acc[1][u], acc[2][u], acc[3][u], yv[u]);
+    // this thread's outputs (ex_read): cout quad c4, column ox of the tile, rows k = 0..3
+    const int c4 = tid & 7;
+    const int ox = cur.ox0 + ((tid >> 3) & 31);
     // LSTM: the quad is (i, f, o, g) of hidden channel cout/4; out / out2 / res are 64-ch maps
     constexpr bool LSTM = EPI == STIF_EPI_LSTM;
     const int ostride = LSTM ? 64 : a.cout;
@@ -488,24 +535,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       if (nt) __syncthreads();   // round-0 readers are done with the exchange image
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int fl = (hf ^ b) * 32;
-        float* wb = ex + ((wi * 2 + b) * 32 + 4 * hf) * 32 + tl;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          wb[((r & 3) + 8 * (r >> 2)) * 32 + ((r & 1) ? -fl : fl)] = yv[nt][b][r];
-      }
+      ex_write(ex, wi, lane, yv[nt]);
       __syncthreads();
       const int cob = cur.slice * 64 + nt * 32 + c4 * 4;
       const f32x4 bv = cob < a.cout ? ld4(a.bias[cur.g] + cob) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float* rbase = ex + (bb * 32 + (txo ^ (((txo >> 2) ^ bb) & 1))) * 32 + c4 * 4 + (k >> 1) * 512;
-        const f32x4 p1 = ld4(rbase + 1 * 2048), p2 = ld4(rbase + 2 * 2048);
-        const f32x4 pe = ld4(rbase + ((k & 1) ? 3 : 0) * 2048);
-        f32x4 y = (k & 1) ? (p1 - p2 - pe) : (pe + p1 + p2);
-        y = y * (F16 ? F16X3_UNSCALE : 1.f) + bv;   // exact power of two
+        f32x4 y = ex_read(ex, tid, k) * (F16 ? F16X3_UNSCALE : 1.f) + bv;   // exact power of two
         if (F16) chk += (cob < a.cout) ? (y[0] + y[1]) + (y[2] + y[3]) : 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -555,28 +591,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wi = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hf = lane >> 5;
-  const int tl = lane & 31;
-  const int tyl = tl >> 4, txl = tl & 15;
   const int tiles_x = (a.Wo + 31) >> 5;
   const int tiles_y = (a.Ho + WR - 1) / WR;
   const int H = a.H, W = a.W;                   // C0 = 64, in1_mode 0 (host-checked)
   const int ntn = (a.cout + 31) >> 5;           // 32-cout N-tiles
   const int wbytes = ((a.cout + 63) >> 6) * SLICE_F * 4;
-
-  auto tile_of = [&](int T) {
-    Tile t;
-    t.slice = 0;
-    const int x = T % tiles_x;
-    int r = T / tiles_x;
-    const int y = r % tiles_y;
-    r /= tiles_y;
-    t.g = r / a.nitems;
-    t.n = r - t.g * a.nitems;
-    t.oy0 = y * WR;
-    t.ox0 = x * 32;
-    return t;
-  };
 
   // staging: k_wino's image (stage_image), 32 channels per phase, all four waves issuing
   const int lpx = lane / 9, lck = lane - 9 * (lane / 9);
@@ -587,36 +606,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     stage_image(rs, smem + buf * BUF_F, t.oy0 - 1, t.ox0 - 1, H, W, 64, p * 32, wi, 4, lpx, lck);
   };
 
-  // input transform row i (k_wino's xread / xform) -> split A operands of chunk pair q
-  const int rA = (wi == 0) ? 0 : (wi == 2 ? 2 : 1);
-  const int rB = (wi == 3) ? 3 : (wi == 2 ? 1 : 2);
-  const float sB = (wi == 1) ? 1.f : -1.f;
-  const int s0 = col_slot(0) + txl, s1 = col_slot(1) + txl, s2 = col_slot(2) + txl, s3 = col_slot(3) + txl;
-  auto xread = [&](const float* buf, int s, f32x4* rd) {
-    const float* ra = buf + ((2 * tyl + rA) * OM_RP + 2 * s + hf) * 4;
-    const float* rb = buf + ((2 * tyl + rB) * OM_RP + 2 * s + hf) * 4;
-    rd[0] = ld4(ra + s0 * PITCH * 4); rd[1] = ld4(rb + s0 * PITCH * 4);
-    rd[2] = ld4(ra + s1 * PITCH * 4); rd[3] = ld4(rb + s1 * PITCH * 4);
-    rd[4] = ld4(ra + s2 * PITCH * 4); rd[5] = ld4(rb + s2 * PITCH * 4);
-    rd[6] = ld4(ra + s3 * PITCH * 4); rd[7] = ld4(rb + s3 * PITCH * 4);
-  };
-  auto xform = [&](const f32x4* rd, f32x4* v) {
-    const f32x4 t0 = rd[0] + sB * rd[1];
-    const f32x4 t1 = rd[2] + sB * rd[3];
-    const f32x4 t2 = rd[4] + sB * rd[5];
-    const f32x4 t3 = rd[6] + sB * rd[7];
-    v[0] = t0 - t2;
-    v[1] = t1 + t2;
-    v[2] = t2 - t1;
-    v[3] = t1 - t3;
-  };
+  // input transform row i -> split A operands of chunk pair q
+  const XRow xr(wi, lane);
   f16x8 Ah[4][4], Al[4][4];
   auto make_a = [&](const float* buf, int sp, int q) {
     f32x4 rd[8], va[4], vb[4];
-    xread(buf, 2 * sp, rd);
-    xform(rd, va);
-    xread(buf, 2 * sp + 1, rd);
-    xform(rd, vb);
+    xr.read(buf, 2 * sp, rd);
+    xr.form(rd, va);
+    xr.read(buf, 2 * sp + 1, rd);
+    xr.form(rd, vb);
 #pragma unroll
     for (int j = 0; j < 4; ++j) split_f16x3(va[j], vb[j], Ah[q][j], Al[q][j]);
   };
@@ -636,28 +634,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     bl[slot] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r, bvo, boff(n, b, 1), 0));
   };
 
-  // output transform of N-tile n (k_wino's exchange, one 32-cout round); `last` also waits for the
-  // next tile's first staging phase (buffer 0) before the closing barrier
-  const int c4 = tid & 7, oxl = (tid >> 3) & 31;
-  const int bb = oxl & 1, txo = oxl >> 1;
+  // output transform of N-tile n: the exchange of one 32-cout half
+  const int c4 = tid & 7;
   auto bias_of = [&](const Tile& t, int n) {   // loaded before the N-tile's B prefetches (vmcnt order)
     const int cob = n * 32 + c4 * 4;
     return cob < a.cout ? ld4(a.bias[t.g] + cob) : f32x4{0.f, 0.f, 0.f, 0.f};
   };
   auto write_p = [&](const f32x16* acc) {
     f32x16 yv[2];
-    yv[0] = acc[0] + acc[1] + acc[2];
-    yv[1] = acc[1] - acc[2] - acc[3];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int fl = (hf ^ b) * 32;
-      float* wb = ex + ((wi * 2 + b) * 32 + 4 * hf) * 32 + tl;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) wb[((r & 3) + 8 * (r >> 2)) * 32 + ((r & 1) ? -fl : fl)] = yv[b][r];
-    }
+    ex_col_sums(acc[0], acc[1], acc[2], acc[3], yv);
+    ex_write(ex, wi, lane, yv);
   };
   auto read_store = [&](const Tile& t, int n, f32x4 bv) {
-    const int ox = t.ox0 + oxl;
+    const int ox = t.ox0 + ((tid >> 3) & 31);
     const int cob = n * 32 + c4 * 4;
     const int m3 = cob % 3;
     const bool cok = cob < a.cout;
@@ -667,11 +656,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     float chk = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float* rbase = ex + (bb * 32 + (txo ^ (((txo >> 2) ^ bb) & 1))) * 32 + c4 * 4 + (k >> 1) * 512;
-      const f32x4 p1 = ld4(rbase + 1 * 2048), p2 = ld4(rbase + 2 * 2048);
-      const f32x4 pe = ld4(rbase + ((k & 1) ? 3 : 0) * 2048);
-      f32x4 y = (k & 1) ? (p1 - p2 - pe) : (pe + p1 + p2);
-      y = y * F16X3_UNSCALE + bv;
+      f32x4 y = ex_read(ex, tid, k) * F16X3_UNSCALE + bv;
       chk += (y[0] + y[1]) + (y[2] + y[3]);
       // sigmoid(m) on the mask channels (packed position % 3 == 2), branch-free: v_exp + v_rcp
       // (a few ulp, far inside the parity bar)
@@ -707,13 +692,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     }
   };
 
-  // XCD-aware persistent schedule (as k_wino): XCD x owns a contiguous range of spatial tiles
-  const int xcd = blockIdx.x & 7, nl = gridDim.x >> 3;
-  const int per = (ntiles + 7) >> 3;
-  const int tend = min((xcd + 1) * per, ntiles);
-  int T = xcd * per + (blockIdx.x >> 3);
-  if (T >= tend) return;
-  Tile cur = tile_of(T);
+  // the tile walk (xcd_tile_range) over spatial tiles: one slice
+  const TileRange tr = xcd_tile_range(ntiles);
+  int T = tr.T;
+  if (T >= tr.end) return;
+  Tile cur = tile_of(T, 1, tiles_x, tiles_y, a.nitems);
   __amdgpu_buffer_rsrc_t wr = wres(cur.g);
 #pragma unroll
   for (int s = 0; s < RING; ++s) ldb(wr, 0, s, s);
@@ -721,9 +704,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (;;) {
-    const int Tn = T + nl;
-    const bool has_next = Tn < tend;
-    const Tile nxt = tile_of(has_next ? Tn : T);
+    const int Tn = T + tr.stride;
+    const bool has_next = Tn < tr.end;
+    const Tile nxt = tile_of(has_next ? Tn : T, 1, tiles_x, tiles_y, a.nitems);
     const __amdgpu_buffer_rsrc_t wrn = wres(nxt.g);
     stage(cur, 1, 1);
     make_a(smem, 0, 0);
@@ -835,22 +818,17 @@ extern "C" int stif_conv3x3_wino(const stif_conv_args* pa, void* stream) {
   if (a.C0 % (8 * PSUB) || (a.in1_mode && a.C1 % (8 * PSUB)))
     return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: input channel counts must be multiples of 32");
   if (a.epi == STIF_EPI_RES && !a.res[0]) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: RES needs res");
-#define STIF_WINO_CASE(IN1)                                              \
-  switch (a.epi) {                                                       \
-    case STIF_EPI_NONE: return launch<IN1, STIF_EPI_NONE>(a, st);        \
-    case STIF_EPI_LRELU: return launch<IN1, STIF_EPI_LRELU>(a, st);      \
-    case STIF_EPI_RELU: return launch<IN1, STIF_EPI_RELU>(a, st);        \
-    case STIF_EPI_RES: return launch<IN1, STIF_EPI_RES>(a, st);          \
-    default: break;                                                      \
-  }
-  if (a.in1_mode == 0 && a.epi == STIF_EPI_OFFMASK) return launch<0, STIF_EPI_OFFMASK>(a, st);
-  if (a.in1_mode == 1 && a.epi == STIF_EPI_LSTM) return launch<1, STIF_EPI_LSTM>(a, st);
-  if (a.in1_mode == 0) { STIF_WINO_CASE(0) }
-  else if (a.in1_mode == 1) { STIF_WINO_CASE(1) }
-  else if (a.in1_mode == 2) {   // the cat(., s * up2(.)) convs: NONE / LRELU
-    if (a.epi == STIF_EPI_NONE) return launch<2, STIF_EPI_NONE>(a, st);
-    if (a.epi == STIF_EPI_LRELU) return launch<2, STIF_EPI_LRELU>(a, st);
-  }
-#undef STIF_WINO_CASE
+  // the epilogues each input mode is built for (2 = the cat(., s * up2(.)) convs)
+  int rc = STIF_OK;
+  bool ok = false;
+  if (a.in1_mode == 0)
+    ok = with_int<STIF_EPI_NONE, STIF_EPI_LRELU, STIF_EPI_RELU, STIF_EPI_RES, STIF_EPI_OFFMASK>(
+        a.epi, [&](auto epi) { rc = launch<0, decltype(epi)::value>(a, st); });
+  else if (a.in1_mode == 1)
+    ok = with_int<STIF_EPI_NONE, STIF_EPI_LRELU, STIF_EPI_RELU, STIF_EPI_RES, STIF_EPI_LSTM>(
+        a.epi, [&](auto epi) { rc = launch<1, decltype(epi)::value>(a, st); });
+  else if (a.in1_mode == 2)
+    ok = with_int<STIF_EPI_NONE, STIF_EPI_LRELU>(a.epi, [&](auto epi) { rc = launch<2, decltype(epi)::value>(a, st); });
+  if (ok) return rc;
   return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: unsupported in1 mode / epilogue");
 }

@@ -337,3 +337,66 @@ def test_wino_dynamic_schedule_bit_identical(stif):
         assert int(ops._SCHED[(s3.device.index, s3.cuda_stream)].abs().sum()) == 0
     finally:
         ops.DYNAMIC_TILES = keep
+
+
+_WALK_REF = {}
+
+
+def _walk_case(case):
+    """Inputs and oracle outputs of one tile-walk case, computed once for both operand modes."""
+    if case not in _WALK_REF:
+        G, N, H, W = 3, 5, 64, 96
+        cout = 256 if case == "lstm" else 64
+        x0 = rnd(G, N, 64, H, W, seed=70)
+        x1 = rnd(G, N, 64, H // 2, W // 2, seed=71) if case == "up2" else rnd(G, N, 64, H, W, seed=71)
+        c = rnd(G, N, 64, H, W, seed=72)
+        ws = [rnd(cout, 128, 3, 3, seed=73 + g, scale=0.04) for g in range(G)]
+        bs = [rnd(cout, seed=76 + g) for g in range(G)]
+        refs = []
+        for g in range(G):
+            if case == "lstm":
+                refs.append(O.conv_lstm_cell(x0[g], x1[g], c[g], {"conv.weight": ws[g], "conv.bias": bs[g]}, "",
+                                             np.float64))
+            elif case == "up2":
+                up = O.upsample2x(x1[g].astype(np.float64)) * 2.0
+                refs.append((O.lrelu(O.conv2d(np.concatenate([x0[g], up], 1), ws[g], bs[g])),))
+            else:
+                refs.append((O.conv2d(np.concatenate([x0[g], x1[g]], 1), ws[g], bs[g]),))
+        _WALK_REF[case] = (x0, x1, c, ws, bs, refs)
+    return _WALK_REF[case]
+
+
+@pytest.mark.parametrize("case", ["up2", "cat", "lstm"])
+def test_wino_tile_walk_across_groups(stif, case, pf):
+    """A workgroup's step from one tile to the next -- the next tile's phase 0 staged during the last phase,
+    its first B operands prefetched, the exchange buffer reused -- for the coarse-patch scratch (in1_mode 2,
+    LRELU, scale 2), the two-input NONE conv and the LSTM epilogue, across a change of weight group: three
+    groups x 5 items of 64 x 96 are 48 spatial tiles per item and 720 in all (x 4 cout slices for the LSTM
+    conv), more than the two workgroups per CU of the persistent grid (asserted from the device's CU count: 512
+    workgroups and 90 tiles per XCD range on 256 CUs), so workgroups take a second tile, and the group
+    boundaries (spatial tiles 240 and 480) fall inside XCD ranges: workgroups there go on with other weights,
+    other in0 / in1 / out pointers and another bias.  Outputs start as NaN and must match the oracle."""
+    L, ops = stif._lib, stif.ops
+    G, N, H, W = 3, 5, 64, 96
+    x0, x1, c, ws, bs, refs = _walk_case(case)
+    tiles = G * N * (H // 4) * (W // 32) * (4 if case == "lstm" else 1)
+    assert tiles > 2 * torch.cuda.get_device_properties(0).multi_processor_count, tiles
+    mode = L.PACK_WINO_LSTM if case == "lstm" else L.PACK_WINO
+    groups = []
+    for g in range(G):
+        grp = dict(layer=ops.pack_conv(ws[g], bs[g], mode | pf), in0=nhwc(x0[g]), in1=nhwc(x1[g]),
+                   out=torch.full((N, H, W, 64), float("nan"), device="cuda"))
+        if case == "lstm":
+            grp.update(res=nhwc(c[g]), out2=torch.full((N, H, W, 64), float("nan"), device="cuda"))
+        groups.append(grp)
+    if case == "up2":
+        ops.conv2d(groups, epi=L.EPI_LRELU, in1_mode=2, in1_scale=2.0)
+    elif case == "cat":
+        ops.conv2d(groups, epi=L.EPI_NONE, in1_mode=1)
+    else:
+        ops.conv2d(groups, epi=L.EPI_LSTM, in1_mode=1)
+    for grp, ref in zip(groups, refs):
+        for key, r in zip(("out", "out2"), ref):
+            got = to_nchw(grp[key])
+            assert np.isfinite(got).all()
+            assert relmax(got, r) < RTOL
