@@ -489,6 +489,26 @@ int stif_yuv_to_rgb(const stif_yuv_format* fmt, const void* y, const void* u, co
 int stif_rgb_to_yuv(const stif_yuv_format* fmt, const float* rgb, long long rgb_item, long long rgb_plane,
                     long long rgb_pitch, int n, void* y, void* u, void* v, void* stream);
 
+/* ---- scene cuts: how much the picture changes between adjacent frames of a clip ---- */
+
+/* Bytes of workspace stif_scene_sad needs (one 64-bit partial sum per pair and workgroup; a function of the shape
+ * alone); 0 for n < 2 or H, W < 1.  Pure host. */
+size_t stif_scene_workspace_size(int n, int H, int W);
+/* rgb: n >= 2 frames of fp32 RGB planes, element (i, c, y, x) at rgb[i * item + c * plane + y * pitch + x] (the
+ * addressing of stif_metric_args.pred; all zero = a dense [n][3][H][W]), so the H x W rectangle in the top-left of
+ * a padded [n][3][h_n][w_n] model input is scored in place; nothing outside the rectangle is read.
+ * sad: device array [n - 1]; sad[i] = the sum over the rectangle of |q_i - q_i+1|, q the 8-bit luma of a pixel, in
+ * fp32 without FMA contraction: r, g, b = fminf(fmaxf(v, 0), 1) (a NaN becomes 0); y = (0.299f r + 0.587f g) +
+ * 0.114f b; q = min((int)rintf(y * 255.f), 255).  From q on the arithmetic is integer and the totals 64-bit (an 8K
+ * pair going black to white sums to 8,460,288,000), so the result is exact, the same for every summation order and
+ * every call, and equal to a host restatement to the last bit.  sad / (255 H W) is the mean luma change in [0, 1].
+ * Two launches on `stream`, no atomics, no host read-back, no allocation (graph-capturable); each frame is read
+ * once per 8 pairs.  Every argument is validated before the first launch: STIF_E_INVALID for null pointers, n < 2,
+ * H or W < 1 (or H W > 2^48), a pitch below W, overlapping planes or items, a sad or workspace that is not 8-byte
+ * aligned; STIF_E_WORKSPACE for a missing or short workspace. */
+int stif_scene_sad(const float* rgb, long long item, long long plane, long long pitch, int n, int H, int W,
+                   unsigned long long* sad, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,8 @@ EXPORTS = {
     # name: (restype, argtypes)
     "stif_yuv_to_rgb": (C.c_int, [C.POINTER(YuvFormat), _P, _P, _P, C.c_int, _P] + [C.c_longlong] * 3 + [_P]),
     "stif_rgb_to_yuv": (C.c_int, [C.POINTER(YuvFormat), _P] + [C.c_longlong] * 3 + [C.c_int, _P, _P, _P, _P]),
+    "stif_scene_workspace_size": (C.c_size_t, [C.c_int] * 3),
+    "stif_scene_sad": (C.c_int, [_P] + [C.c_longlong] * 3 + [C.c_int] * 3 + [_P, _P, C.c_size_t, _P]),
     "stif_metric_workspace_size": (C.c_size_t, [C.c_int] * 4),
     "stif_metric_psnr_ssim": (C.c_int, [C.POINTER(MetricArgs), _P, _P, C.c_size_t, _P]),
     "stif_metric_window": (C.c_int, [C.POINTER(C.c_double)]),

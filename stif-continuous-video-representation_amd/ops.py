@@ -537,3 +537,24 @@ def rgb_to_yuv(rgb, fmt, out=None):
     _launch("stif_rgb_to_yuv", None, L.lib().stif_rgb_to_yuv, C.byref(f), _vp(rgb), item, plane, pitch, n, y, u, v,
             _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- scene cuts
+def scene_sad(frames, h=None, w=None):
+    """Sum of absolute differences of the 8-bit luma of every adjacent pair of ``frames`` (stif_scene_sad): a
+    float32 CUDA tensor [n >= 2, 3, H, W] with contiguous rows (any view ``_rgb_strides`` accepts) -> an int64 device
+    tensor [n - 1].  ``h``, ``w`` select the top-left h x w rectangle (default: all of H x W), so a padded model
+    input is scored without its padding.  Exact integers; nothing is read back here."""
+    if frames.dim() != 4 or frames.shape[0] < 2:
+        raise ValueError(f"scene_sad: frames must be [n >= 2, 3, H, W], got {tuple(frames.shape)}")
+    n = frames.shape[0]
+    h = frames.shape[2] if h is None else int(h)
+    w = frames.shape[3] if w is None else int(w)
+    if not (1 <= h <= frames.shape[2] and 1 <= w <= frames.shape[3]):
+        raise ValueError(f"scene_sad: the rectangle {h} x {w} does not lie in {tuple(frames.shape)}")
+    item, plane, pitch = _rgb_strides(frames, n, h, w, "scene_sad: frames")
+    sad = torch.empty(n - 1, device=frames.device, dtype=torch.int64)
+    ws = torch.empty(max(1, L.lib().stif_scene_workspace_size(n, h, w) // 8), device=frames.device, dtype=torch.int64)
+    _launch("stif_scene_sad", None, L.lib().stif_scene_sad, _vp(frames), item, plane, pitch, n, h, w, _vp(sad),
+            _vp(ws), ws.numel() * 8, _stream())
+    return sad

@@ -20,6 +20,8 @@ myutils.eval_metrics (:234-241: calc_psnr beside ssim_matlab) instead of the qua
 are taken a chunk at a time, each encoded once), any rational output frame rate (every pair gets its own query
 times), raw YUV4MPEG2 in and out (stif_amd.y4m, ops.yuv_to_rgb / rgb_to_yuv).  They compose gen_feat_window and
 decoding; the harness functions above keep the reference's behaviour, truncating quantisation included.
+Optionally they detect scene cuts on the device (ops.scene_sad, ``scene_scores``) or take them from the caller,
+and repeat a real frame across a cut instead of interpolating between two unrelated pictures.
 """
 from __future__ import annotations
 
@@ -284,10 +286,32 @@ def _padded_size(h, w):
     return int(4 * math.ceil(h / 4)), int(4 * math.ceil(w / 4))
 
 
-def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw):
+def scene_scores(sad, h, w, prev=None):
+    """Cut scores of consecutive pairs from their luma SADs (ops.scene_sad over h x w pixels; pure host code).
+    m_p = sad_p / (255 h w) is the mean luma change of pair p in [0, 1], and score_p = min(m_p, |m_p - m_p-1|):
+    a cut is a large change that the pair before it did not show.  The min tells a cut from what only looks like
+    one: steady fast motion has a large m but a small change of m, and a one-frame flash gives two large m in a
+    row, of which the second scores about 0.  ``prev`` is m of the pair before the first one -- the ``last``
+    returned for the preceding chunk, so that scoring a clip in pieces equals scoring it at once; None at the start
+    of a stream, where m_p-1 is taken as m_p itself and the very first pair scores 0.  Two consequences: a cut
+    between frames 0 and 1 of a stream is never detected, and a scene that lasts one frame is detected once (at
+    its first pair, not at the pair that leaves it).  Returns (scores, last): a list of floats and the last m
+    (``prev`` itself for an empty ``sad``)."""
+    area = 255 * int(h) * int(w)
+    scores = []
+    for s in sad:
+        m = int(s) / area
+        scores.append(min(m, abs(m - (m if prev is None else prev))))
+        prev = m
+    return scores, prev
+
+
+def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw, scene_threshold=None, hold_pairs=(), cuts=None):
     """render_stream's core.  ``chunks`` yields device tensors [k, 3, h_n, w_n] of new input frames, already
     zero-padded to a multiple of 4 (k >= 1; the pairs of a chunk are its frames plus the previous chunk's last).
-    Gradients are switched off around the model calls only, never across a yield."""
+    Gradients are switched off around the model calls only, never across a yield.  scene_threshold / hold_pairs /
+    cuts: render_stream's; a cut pair is never fused, breaks the run of pairs on either side, and its outputs
+    repeat the model's rendering of one of its two frames."""
     hn, wn = _padded_size(h, w)
     OH, OW = out_hw
     grid = (int(round(OH * hn / h)), int(round(OW * wn / w)))      # virtual grid of the padded frame
@@ -296,11 +320,23 @@ def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw):
     base = 0                      # index of the first pair of the current chunk
     last, last_feats = None, None
     B = 0                         # pairs of the latent the model holds after a chunk (for the closing t = 1 frame)
+    forced = frozenset(int(p) for p in hold_pairs)
+    prev_m = None                 # mean luma change of the previous chunk's last pair (scene_scores' prev)
+    last_cut = False              # the last pair so far is a cut
+    closing = None                # ... and this is its held frame p + 1, if an output showed it already
 
     def fuse(x, feats, a, b):
         with torch.no_grad():
             model.gen_feat_window(x[a:b + 1], frame_feats=tuple(f[a:b + 1] for f in feats))
         return b - a
+
+    def held(x, feats, i):
+        """The model's rendering of frame i of (x, feats) standing still: the degenerate pair (i, i) at t = 0."""
+        with torch.no_grad():
+            model.gen_feat_window(torch.cat([x[i:i + 1], x[i:i + 1]]),
+                                  frame_feats=tuple(torch.cat([f[i:i + 1], f[i:i + 1]]) for f in feats))
+            o = model.decoding_pairs([0], [torch.zeros(1, dtype=torch.float32)], grid)[0][0]
+        return o[:, :OH, :OW]
 
     for x in chunks:
         with torch.no_grad():
@@ -312,24 +348,47 @@ def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw):
         P = x.shape[0] - 1
         if P == 0:
             continue                                                # a first chunk of one frame: no pair yet
+        cut = [base + i in forced for i in range(P)]
+        if scene_threshold is not None:
+            from . import ops
+            # one launch over the chunk (its P pairs are x's adjacent frames) and one read-back of P integers
+            scores, prev_m = scene_scores(ops.scene_sad(x, h, w).tolist(), h, w, prev_m)
+            cut = [c or s > scene_threshold for c, s in zip(cut, scores)]
+        if cuts is not None:
+            cuts.extend(base + i for i in range(P) if cut[i])
         per = [[] for _ in range(P)]                                # query times of each pair of the chunk
         while pending[0] < base + P:
             per[pending[0] - base].append(pending[1])
             pending = next(sched)
-        # runs of consecutive pairs that have queries share one latent; pairs without an output are not run
+        last_cut, closing = cut[-1], None
+        # runs of consecutive uncut pairs that have queries share one latent; pairs without an output are not run
         a = 0
         while a < P:
             if not per[a]:
                 a += 1
                 continue
+            if cut[a]:
+                # hold instead of blend: outputs before the middle of the pair show frame a, the others frame
+                # a + 1, each rendered once and repeated as tensors of their own
+                for i, ts in ((a, [t for t in per[a] if 2 * t < 1]), (a + 1, [t for t in per[a] if 2 * t >= 1])):
+                    if ts:
+                        o = held(x, feats, i)
+                        if i == P and pending == (base + P, 0):
+                            closing = o.clone()                     # the frame a closing t = 1 output would show
+                        for _ in ts[1:]:
+                            yield o.clone()
+                        yield o
+                        del o
+                a += 1
+                continue
             b = a
-            while b < P and per[b]:
+            while b < P and per[b] and not cut[b]:
                 b += 1
             B = fuse(x, feats, a, b)
             yield from _decode_run(model, per[a:b], grid, OH, OW)
             a = b
         base += P
-        if not per[-1] and pending == (base, 0):
+        if not per[-1] and not last_cut and pending == (base, 0):
             # the next output falls exactly on this chunk's last frame: if the stream ends here it is the last
             # pair at t = 1, so its latent is made now, while both of its frames are held (should the stream
             # go on, this one pair was fused for nothing; only a lower output rate can come here)
@@ -337,7 +396,10 @@ def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw):
         del x, feats
     if base == 0:
         raise ValueError("render_stream needs at least two frames")
-    if pending == (base, 0):
+    if pending == (base, 0) and last_cut:
+        # the stream ended on an output instant and on a cut: the last frame, held (the carried frame and features)
+        yield closing if closing is not None else held(last, last_feats, 0)
+    elif pending == (base, 0):
         # the stream ended on an output instant: the last pair (the last item of the model's latent) at t = 1
         yield from _decode_run(model, [[]] * (B - 1) + [[1]], grid, OH, OW)
 
@@ -373,7 +435,8 @@ def _out_size(h, w, scale, out_size):
     return OH, OW
 
 
-def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_pairs=8):
+def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_pairs=8, scene_threshold=None,
+                  hold_pairs=(), cuts=None):
     """Render a video of any length at any output frame rate in bounded memory.  ``frames``: an iterable of RGB
     float [3, h, w] frames in [0, 1] (host or device) at ``fps_in``; yields device float [3, OH, OW] frames
     (unclamped) at ``fps_out`` in display order, (OH, OW) = ``out_size`` or (h, w) * ``scale``.  The output frames
@@ -385,7 +448,19 @@ def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_
     carried into the next.  The decoder's virtual grid is that of the padded frame, (round(OH h_n / h),
     round(OW w_n / w)), and the yielded frame its top-left OH x OW crop -- for h, w multiples of 4 exactly
     ``decoding(scale=(OH, OW))``.  Alive at a time: at most chunk_pairs + 1 input frames, one chunk's features and
-    latents, and the decoded frames of one chunk that have not been yielded yet."""
+    latents, and the decoded frames of one chunk that have not been yielded yet.
+
+    Scene cuts (off by default).  ``scene_threshold``: a float switches the detector on -- one ``ops.scene_sad`` per
+    chunk over its frames (the carried last frame first) and one read-back of its pair sums; pair p is a cut when
+    ``scene_scores``' score_p > scene_threshold (see there for what is and is not detected).  ``hold_pairs``: pair
+    indices that are cuts whatever the detector says, e.g. from an edit list (no detector, any device).  ``cuts``:
+    a list that receives the index of every cut pair, in order.  The schedule does not change: an output (p, t) of
+    a cut pair shows input frame p if t < 1/2 and frame p + 1 otherwise (the closing t = 1 frame of a stream that
+    ends on a cut included), where "shows frame f" is the model's rendering of the degenerate pair (f, f) at t = 0,
+    bit for bit the crop of ``run_sequence(model, stack([frame_f, frame_f]), times=[0.0])[0][0]`` -- the same size
+    and the same network as its neighbours.  A cut pair is never fused and splits the runs either side of it; a
+    held frame is fused and decoded once per pair and repeated as separate tensors; the memory bound grows by one
+    pair (the two-frame window of a held frame) and at most one output frame."""
     import itertools
     if chunk_pairs < 1:
         raise ValueError("chunk_pairs must be >= 1")
@@ -416,16 +491,19 @@ def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_
                 del f
             yield x
 
-    return _render_chunks(model, chunks(), h, w, fps_in, fps_out, _out_size(h, w, scale, out_size))
+    return _render_chunks(model, chunks(), h, w, fps_in, fps_out, _out_size(h, w, scale, out_size), scene_threshold,
+                          hold_pairs, cuts)
 
 
-def render_y4m(model, src, dst, fps_out=None, multiplier=8, scale=4, chunk_pairs=8, matrix="auto", out_size=None):
+def render_y4m(model, src, dst, fps_out=None, multiplier=8, scale=4, chunk_pairs=8, matrix="auto", out_size=None,
+               scene_threshold=None, hold_pairs=(), cuts=None):
     """Render a YUV4MPEG2 stream to another: reader -> upload -> yuv_to_rgb -> render_stream -> rgb_to_yuv ->
     download -> writer.  src / dst: paths or binary file objects (pipes work: nothing seeks).  The output runs at
     ``fps_out`` (default: ``multiplier`` x the input rate) and (h, w) * ``scale`` (or ``out_size`` = (OH, OW)); it
     keeps the input's chroma layout, depth, range, matrix ("auto": BT.709 for an input luma >= 1280 wide or >= 720
     high, else BT.601) and X tags, so colours survive the round trip.  Uploads and downloads go through pinned host
-    buffers, one chunk of input frames / one chunk's worth of output frames at a time.  Returns (frames read,
+    buffers, one chunk of input frames / one chunk's worth of output frames at a time.  scene_threshold / hold_pairs / cuts:
+    render_stream's scene-cut arguments (the detector scores the converted RGB frames).  Returns (frames read,
     frames written)."""
     from fractions import Fraction
 
@@ -480,7 +558,8 @@ def render_y4m(model, src, dst, fps_out=None, multiplier=8, scale=4, chunk_pairs
                     writer.write(host[j])
 
             k = 0
-            for frame in _render_chunks(model, chunks(), h, w, fps_in, fps_o, (OH, OW)):
+            for frame in _render_chunks(model, chunks(), h, w, fps_in, fps_o, (OH, OW), scene_threshold, hold_pairs,
+                                        cuts):
                 ops.rgb_to_yuv(frame[None], fmt_out, out=ybuf[k:k + 1])   # the crop, converted in place
                 del frame
                 k += 1

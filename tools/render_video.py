@@ -7,6 +7,9 @@
 `-` is stdin / stdout (nothing seeks, so pipes work).  The model comes from a reference-style option file
 (``network_G`` + ``path.pretrain_model_G``, stif_amd.serving) or, with --checkpoint, from a state-dict file on the
 default LIIF architecture; --seed-weights N uses the deterministic test weights instead (no checkpoint needed).
+--scene-threshold X switches the on-device scene-cut detector on (a pair whose cut score exceeds X repeats a real
+frame instead of being interpolated; no value is recommended: none has been validated on footage), --hold-pairs
+12,340 forces cuts from an edit list; with either, the cut pairs are reported on stderr.
 A thin front end of stif_amd.video.render_y4m.
 """
 import argparse
@@ -51,6 +54,9 @@ def main(argv=None):
     ap.add_argument("--size", help="output size WxH instead of --scale")
     ap.add_argument("--chunk-pairs", type=int, default=8, help="frame pairs rendered at a time (bounds the memory)")
     ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto")
+    ap.add_argument("--scene-threshold", type=float, help="detect scene cuts: hold a frame where the cut score of a "
+                    "pair (video.scene_scores, in [0, 1]) exceeds this; off when not given")
+    ap.add_argument("--hold-pairs", default="", help="comma-separated pair indices to treat as cuts, e.g. 12,340")
     opt = ap.parse_args(argv)
     stif = stif_pkg.load()
     model = build_model(stif, opt)
@@ -58,12 +64,17 @@ def main(argv=None):
     if opt.size:
         ow, oh = opt.size.lower().split("x")
         out_size = (int(oh), int(ow))
+    hold = [int(p) for p in opt.hold_pairs.split(",") if p.strip()]
+    cuts = []
     src = sys.stdin.buffer if opt.src == "-" else opt.src
     dst = sys.stdout.buffer if opt.dst == "-" else opt.dst
     nin, nout = stif.video.render_y4m(model, src, dst, fps_out=opt.fps_out, multiplier=opt.multiplier,
                                       scale=opt.scale, chunk_pairs=opt.chunk_pairs, matrix=opt.matrix,
-                                      out_size=out_size)
+                                      out_size=out_size, scene_threshold=opt.scene_threshold, hold_pairs=hold,
+                                      cuts=cuts)
     print(f"{nin} frames in, {nout} frames out", file=sys.stderr)
+    if opt.scene_threshold is not None or hold:
+        print(f"{len(cuts)} cut pairs: {','.join(map(str, cuts))}", file=sys.stderr)
 
 
 if __name__ == "__main__":
