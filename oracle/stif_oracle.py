@@ -497,18 +497,12 @@ def decode_stage2(feat, inp, hrfeat, flow, t, sd, HH, WW, dtype=np.float64, img=
     return np.ascontiguousarray(pred.transpose(0, 2, 1).reshape(B, 3, HH, WW))
 
 
-def _decode(feat, inp, times, sd, HH, WW, dtype, capture=None, img=None, shift=None):
-    """The decoder body shared by decoding / decoding_test / decoding_fasttest /
-    decoding_localensemble (Sakuya_arch_test.py:364-459, 461-598, 863-1085).
-    img: the image the flow / encode stages sample bilinearly (LR inp, or decoding_test's x4
-    upsampled HRinp).  shift: (vx, vy) of the local ensemble -- the query coordinates move by
-    (vx/H + 1e-6, vy/W + 1e-6) for every sampling step except rel_coord and the warpgrid base.
-    Returns (list of [B,3,HH,WW], area [HH*WW] or None)."""
-    B = feat.shape[0]
-    H, W = feat.shape[-2:]
-    featc = np.asarray(feat, dtype).reshape(B, 192, H, W)          # cat(feat[:,0..2]) (:365)
-    inpc = np.asarray(inp, dtype).reshape(B, 6, H, W)
-    img = inpc if img is None else np.asarray(img, dtype)
+def _query_axes(H, W, HH, WW, shift=None):
+    """Everything stage 1 derives from the HR query grid, per HR row / column, in the reference's fp32: the nearest
+    LR indices ``iy`` / ``ix`` (:382-385), ``rel_y`` / ``rel_x`` (:394-396), the coordinates ``gy`` / ``gx`` of the two
+    bilinear gathers (:410-417) and the HR pixel ``hy`` / ``hx`` whose HRfeat row the flow stage reads (:406-409).
+    shift: (vx, vy) of the local ensemble -- the query moves by (vx/H + 1e-6, vy/W + 1e-6) for every sampling step
+    (:994-998), rel_coord keeps the unshifted query (:1000-1002); without a shift ``hy`` / ``hx`` are the identity."""
     lo, hi = F32(-1 + 1e-6), F32(1 - 1e-6)
     cy = np.clip(make_coord_1d(HH), lo, hi)                          # coord_highres (:373), row/col
     cx = np.clip(make_coord_1d(WW), lo, hi)
@@ -521,35 +515,69 @@ def _decode(feat, inp, times, sd, HH, WW, dtype, capture=None, img=None, shift=N
     ix = np.clip(nearest_index(sx, W), 0, W - 1)
     rel_y = ((cy - ly[iy]) * F32(H)).astype(F32)                     # (:394-396)
     rel_x = ((cx - lx[ix]) * F32(W)).astype(F32)
-    Q = HH * WW
-    qy = np.repeat(np.arange(HH), WW)
-    qx = np.tile(np.arange(WW), HH)
-    gy = np.broadcast_to(sy[qy], (B, Q))
-    gx = np.broadcast_to(sx[qx], (B, Q))
-    lin = featc.reshape(B, 192, H * W).transpose(0, 2, 1)
-    q_feat = lin[:, iy[qy] * W + ix[qx]]                              # nearest (:382-385)
-    q_inp = inpc.reshape(B, 6, H * W).transpose(0, 2, 1)[:, iy[qy] * W + ix[qx]]
-    rel = np.stack([np.broadcast_to(rel_y[qy], (B, Q)), np.broadcast_to(rel_x[qx], (B, Q))], -1).astype(dtype)
-    area = None
-    if shift is not None:                                            # :1003
-        area = np.abs((rel_y[qy] * rel_x[qx]).astype(F32)).astype(dtype) + 1e-9
     # nearest HR pixel of the (shifted) query: identity without a shift (:406-409)
     hy = np.clip(nearest_index(sy, HH), 0, HH - 1)
     hx = np.clip(nearest_index(sx, WW), 0, WW - 1)
+    return dict(iy=iy, ix=ix, rel_y=rel_y, rel_x=rel_x, gy=sy, gx=sx, hy=hy, hx=hx)
+
+
+def decode_stage1(feat, inp, t, sd, HH, WW, dtype=np.float64, img=None, shift=None):
+    """Stage 1 of the decoder on its own (Sakuya_arch_test.py:373-422; the local ensemble's :994-1035): from the
+    latent, the frame pair and a time per item ``t`` [B], feat_imnet on the 201 inputs (nearest latent and frames,
+    rel_coord, t) -> HRfeat, then flow_imnet on the 263 inputs (HRfeat at the HR pixel nearest to the query, the
+    bilinear gathers of the latent and the image at the query, t) -> flow in HR pixels (x1, y1, x2, y2).
+    feat [B,3,64,H,W] (or [B,192,H,W]), inp [B,2,3,H,W] (or [B,6,H,W]); ``img``: decoding_test's HRinp [B,6,sH,sW],
+    which the flow stage samples instead of ``inp`` (feat_imnet always reads ``inp``); ``shift``: see ``_query_axes``.
+    Returns (hrfeat [B,HH,WW,64], flow [B,HH,WW,4]).  ``_decode`` begins with it."""
+    B = feat.shape[0]
+    H, W = feat.shape[-2:]
+    featc = np.asarray(feat, dtype).reshape(B, 192, H, W)          # cat(feat[:,0..2]) (:365)
+    inpc = np.asarray(inp, dtype).reshape(B, 6, H, W)
+    img = inpc if img is None else np.asarray(img, dtype)
+    q = _query_axes(H, W, HH, WW, shift)
+    Q = HH * WW
+    qy = np.repeat(np.arange(HH), WW)
+    qx = np.tile(np.arange(WW), HH)
+    gy = np.broadcast_to(q["gy"][qy], (B, Q))
+    gx = np.broadcast_to(q["gx"][qx], (B, Q))
+    near = q["iy"][qy] * W + q["ix"][qx]
+    q_feat = featc.reshape(B, 192, H * W).transpose(0, 2, 1)[:, near]   # nearest (:382-385)
+    q_inp = inpc.reshape(B, 6, H * W).transpose(0, 2, 1)[:, near]
+    rel = np.stack([np.broadcast_to(q["rel_y"][qy], (B, Q)), np.broadcast_to(q["rel_x"][qx], (B, Q))], -1).astype(dtype)
+    pe = np.broadcast_to(np.asarray(t, dtype).reshape(-1, 1, 1), (B, Q, 1))
+    x1 = np.concatenate([q_feat, q_inp, rel, pe], -1)                 # 201 (:399)
+    hrfeat = siren(x1, sd, "feat_imnet.", 3, dtype)                   # [B,Q,64] (:400)
+    q_hr = hrfeat[:, q["hy"][qy] * WW + q["hx"][qx]]
+    q_inp2 = bilinear_sample(img, gx, gy, dtype)                      # (:410-413)
+    q_feat0 = bilinear_sample(featc, gx, gy, dtype)                   # (:414-417)
+    flow = siren(np.concatenate([q_hr, q_feat0, q_inp2, pe], -1), sd, "flow_imnet.", 3, dtype)  # 263
+    return hrfeat.reshape(B, HH, WW, 64), flow.reshape(B, HH, WW, 4)
+
+
+def _decode(feat, inp, times, sd, HH, WW, dtype, capture=None, img=None, shift=None):
+    """The decoder body shared by decoding / decoding_test / decoding_fasttest /
+    decoding_localensemble (Sakuya_arch_test.py:364-459, 461-598, 863-1085): ``decode_stage1`` then
+    ``decode_stage2`` per query time.
+    img: the image the flow / encode stages sample bilinearly (LR inp, or decoding_test's x4
+    upsampled HRinp).  shift: (vx, vy) of the local ensemble -- the query coordinates move by
+    (vx/H + 1e-6, vy/W + 1e-6) for every sampling step except rel_coord and the warpgrid base.
+    Returns (list of [B,3,HH,WW], area [HH*WW] or None)."""
+    B = feat.shape[0]
+    H, W = feat.shape[-2:]
+    Q = HH * WW
+    area = None
+    if shift is not None:                                            # :1003
+        q = _query_axes(H, W, HH, WW, shift)
+        area = np.abs((q["rel_y"][np.repeat(np.arange(HH), WW)] * q["rel_x"][np.tile(np.arange(WW), HH)]).astype(F32))
+        area = area.astype(dtype) + 1e-9
     preds = []
     for t in times:
-        pe = np.full((B, Q, 1), t, dtype)
-        x1 = np.concatenate([q_feat, q_inp, rel, pe], -1)             # 201 (:399)
-        hrfeat = siren(x1, sd, "feat_imnet.", 3, dtype)               # [B,Q,64] (:400)
-        q_hr = hrfeat[:, hy[qy] * WW + hx[qx]]
-        q_inp2 = bilinear_sample(img, gx, gy, dtype)                  # (:410-413)
-        q_feat0 = bilinear_sample(featc, gx, gy, dtype)               # (:414-417)
-        flow = siren(np.concatenate([q_hr, q_feat0, q_inp2, pe], -1), sd, "flow_imnet.", 3, dtype)  # 263
+        tb = np.full(B, t, dtype)
+        hrfeat, flow = decode_stage1(feat, inp, tb, sd, HH, WW, dtype, img=img, shift=shift)
         if capture is not None:
-            capture.setdefault("hrfeat", []).append(hrfeat)
-            capture.setdefault("flow", []).append(flow)
-        preds.append(decode_stage2(featc, inpc, hrfeat.reshape(B, HH, WW, 64), flow.reshape(B, HH, WW, 4),
-                                   np.full(B, t, dtype), sd, HH, WW, dtype, img=img))      # (:424-457)
+            capture.setdefault("hrfeat", []).append(hrfeat.reshape(B, Q, 64))
+            capture.setdefault("flow", []).append(flow.reshape(B, Q, 4))
+        preds.append(decode_stage2(feat, inp, hrfeat, flow, tb, sd, HH, WW, dtype, img=img))      # (:424-457)
     return preds, area
 
 

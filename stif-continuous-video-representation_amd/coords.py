@@ -68,9 +68,12 @@ def axis_table(n_lr: int, n_hr: int, shift: float = 0.0) -> dict:
     )
 
 
-def dec_tables(h: int, w: int, HH: int, WW: int, shift=None) -> dict:
-    """Tables of one decode; shift = (vx, vy) of the local ensemble (rows move by vx/h, cols by vy/w)."""
-    sy, sx = (0.0, 0.0) if shift is None else (shift[0] * (2 / h / 2) + 1e-6, shift[1] * (2 / w / 2) + 1e-6)
+def dec_tables(h: int, w: int, HH: int, WW: int, shift=None, shift_grid=None) -> dict:
+    """Tables of one decode; shift = (vx, vy) of the local ensemble (rows move by vx/h, cols by vy/w).
+    shift_grid = (h0, w0): the grid whose half pixel the shift is (the latent's), where the map sampled is not the
+    latent -- decoding_test's s-times upsampled image, sampled at the same shifted query as the latent."""
+    h0, w0 = (h, w) if shift_grid is None else shift_grid
+    sy, sx = (0.0, 0.0) if shift is None else (shift[0] * (2 / h0 / 2) + 1e-6, shift[1] * (2 / w0 / 2) + 1e-6)
     ty = axis_table(h, HH, sy)
     tx = axis_table(w, WW, sx)
     out = {}

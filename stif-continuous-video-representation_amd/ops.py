@@ -345,13 +345,14 @@ class DecTablesDev:
 
 class DecImageDev:
     """decoding_test's HRinp: the x`s` bilinear upsample of the frame pair ([n, s*h, s*w, 8] NHWC on
-    the device, stif_upsample_image) and its bilinear tables at the HR query grid (HH, WW)."""
+    the device, stif_upsample_image) and its bilinear tables at the HR query grid (HH, WW).  shift: the local
+    ensemble's (vx, vy), as DecTablesDev's -- the image is sampled at the same shifted query as the latent."""
 
-    def __init__(self, x_nchw, s, HH, WW):
+    def __init__(self, x_nchw, s, HH, WW, shift=None):
         n, _, _, h, w = x_nchw.shape
         self.img = torch.empty(n, s * h, s * w, 8, device=x_nchw.device, dtype=torch.float32)
         L.check(L.lib().stif_upsample_image(_vp(x_nchw), _vp(self.img), n, h, w, s, _stream()), "stif_upsample_image")
-        t = dec_tables(s * h, s * w, HH, WW)
+        t = dec_tables(s * h, s * w, HH, WW, shift, (h, w))
         keys = ["b0_y", "b1_y", "w0_y", "w1_y", "b0_x", "b1_x", "w0_x", "w1_x"]
         self._t = {k: torch.from_numpy(np.ascontiguousarray(t[k])).to(x_nchw.device) for k in keys}
         self._keys = keys

@@ -266,6 +266,27 @@ def test_ensemble_tables(stif):
     assert np.allclose(sum(w), 1.0, atol=1e-5)
 
 
+def test_image_tables_follow_the_ensemble_shift(stif):
+    """The HR image of decoding_test is sampled at the same shifted query as the latent: the tables of the 64 x 80
+    image with shift_grid = the latent's (16, 20) address the source coordinate that is 4x the latent's (+1.5), i.e.
+    the shift is half a pixel of the latent, not of the image (ops.DecImageDev builds its tables this way)."""
+    C = stif.coords
+    for HH, WW in ((37, 45), (64, 80)):
+        for shift in ((-1, 1), (1, -1)):
+            lat = C.dec_tables(16, 20, HH, WW, shift)
+            img = C.dec_tables(64, 80, HH, WW, shift, (16, 20))
+            plain = C.dec_tables(64, 80, HH, WW)
+            for ax, n in (("y", HH), ("x", WW)):
+                i = np.arange(4, n - 4)                   # where no shifted query is clamped and both weights are kept
+                src_lat = lat["b0_" + ax][i] + lat["w1_" + ax][i].astype(np.float64)
+                src_img = img["b0_" + ax][i] + img["w1_" + ax][i].astype(np.float64)
+                assert np.abs(src_img - (4 * src_lat + 1.5)).max() < 1e-3
+                moved = src_img - (plain["b0_" + ax][i] + plain["w1_" + ax][i])
+                assert np.allclose(moved, 2.0 * shift[ax == "x"], atol=1e-3)    # half a latent pixel = 2 image pixels
+    assert all(np.array_equal(C.dec_tables(64, 80, 64, 80, None, (16, 20))[k], v)
+               for k, v in C.dec_tables(64, 80, 64, 80).items())
+
+
 def test_resize_tables_match_reference(stif):
     """video.resize_tables = calculate_weights_indices (data/util.py:248-300), fixture from the reference"""
     h = np.load(os.path.join(REPO, "tests", "golden", "harness.npz"))

@@ -345,3 +345,163 @@ def test_stage2_oracle_in_fp32_is_within_the_bound(sd, kind):
     ratio = float(S.bound_ratio(r32, ref).max())
     print(kind, "fp32 oracle / bound:", ratio)
     assert ratio <= 1.0
+
+
+# ----------------------------------------------------------------------------- decoder stage 1 on its own
+def _stage1_case(image):
+    import stage2_inputs as S
+    feat, inp = S.latent(2, 16, 20)
+    img = O.upsample_bilinear(inp.reshape(2, 6, 16, 20), 4) if image else None      # decoding_test's HRinp
+    return feat, inp, np.array([0.3, 0.7], np.float32), img
+
+
+@pytest.mark.parametrize("image", [False, True], ids=["lr", "hrimg"])
+@pytest.mark.parametrize("shift", [None, (-1, 1)], ids=["whole", "shift-1+1"])
+def test_stage1_is_what_decode_records(sd, shift, image):
+    """decode_stage1 is the hrfeat and the flow that _decode(..., capture=) records, bit for bit, and a time per
+    item is the scalar-time decode of that item."""
+    feat, inp, t, img = _stage1_case(image)
+    HH, WW = 37, 45
+    cap = {}
+    O._decode(feat, inp, [0.3, 0.7], sd, HH, WW, np.float64, capture=cap, img=img, shift=shift)
+    for k, tq in enumerate([0.3, 0.7]):
+        hrf, flow = O.decode_stage1(feat, inp, np.full(2, tq), sd, HH, WW, img=img, shift=shift)
+        assert hrf.shape == (2, HH, WW, 64) and flow.shape == (2, HH, WW, 4)
+        assert np.array_equal(hrf.reshape(2, -1, 64), cap["hrfeat"][k])
+        assert np.array_equal(flow.reshape(2, -1, 4), cap["flow"][k])
+    hrf, flow = O.decode_stage1(feat, inp, t, sd, HH, WW, img=img, shift=shift)      # float32(0.3), float32(0.7)
+    for b in range(2):
+        one = O.decode_stage1(feat[b:b + 1], inp[b:b + 1], t[b:b + 1], sd, HH, WW, img=None if img is None else img[b:b + 1],
+                              shift=shift)
+        assert np.array_equal(hrf[b], one[0][0]) and np.array_equal(flow[b], one[1][0])
+
+
+def _nearest_image_sample(img, gx, gy, dtype=np.float64):
+    """O.bilinear_sample, but a 6-channel map (the frame pair) is read at its nearest pixel."""
+    if img.shape[1] != 6:
+        return _BILINEAR(img, gx, gy, dtype)
+    B, C, H, W = img.shape
+    idx = np.clip(O.nearest_index(gy, H), 0, H - 1) * W + np.clip(O.nearest_index(gx, W), 0, W - 1)
+    return np.asarray(img, dtype).reshape(B, C, H * W).transpose(0, 2, 1)[np.arange(B)[:, None], idx]
+
+
+_BILINEAR = O.bilinear_sample
+_SIREN = O.siren
+_AXES = O._query_axes
+
+
+def _flow_time_swapped_siren(x, sd, p, n_sine, dtype):
+    """O.siren, but flow_imnet reads the other item's time (its last input)."""
+    if p == "flow_imnet.":
+        x = x.copy()
+        x[..., -1] = x[::-1, ..., -1]
+    return _SIREN(x, sd, p, n_sine, dtype)
+
+
+def _axes_mutant(name):
+    def axes(H, W, HH, WW, shift=None):
+        q, q0 = _AXES(H, W, HH, WW, shift), _AXES(H, W, HH, WW, None)
+        if name == "remap_dropped":                       # the flow stage reads the pixel's own HRfeat
+            q["hy"], q["hx"] = q0["hy"], q0["hx"]
+        elif name == "nearest_unshifted":
+            q["iy"], q["ix"] = q0["iy"], q0["ix"]
+        elif name == "rel_shifted":
+            q["rel_y"] = ((q["gy"] - O.make_coord_1d(H)[q["iy"]]) * np.float32(H)).astype(np.float32)
+            q["rel_x"] = ((q["gx"] - O.make_coord_1d(W)[q["ix"]]) * np.float32(W)).astype(np.float32)
+        elif name == "gathers_unshifted":
+            q["gy"], q["gx"] = q0["gy"], q0["gx"]
+        else:
+            raise ValueError(name)
+        return q
+    return axes
+
+
+STAGE1_MUTANTS = ["times_swapped", "flow_time_swapped", "rel_swapped", "replicate_padding", "nearest_image", "lr_for_hr"]
+STAGE1_SHIFT_MUTANTS = ["remap_dropped", "nearest_unshifted", "rel_shifted", "gathers_unshifted"]
+# what the attenuation is asserted for: wrong flows that leave HRfeat right, plus rel_swapped seen through its flow
+STAGE1_FLOW_ONLY = ["flow_time_swapped", "replicate_padding", "nearest_image", "lr_for_hr", "remap_dropped",
+                    "gathers_unshifted"]
+
+
+def _stage1_mutant(name, mp, sd, feat, inp, t, HH, WW, img, shift):
+    """(hrfeat, flow) of the wrong restatement ``name``, by patching the oracle's helpers inside ``mp`` or by
+    permuting inputs / weight columns."""
+    if name == "times_swapped":
+        t = t[::-1]
+    elif name == "flow_time_swapped":
+        mp.setattr(O, "siren", _flow_time_swapped_siren)
+    elif name == "rel_swapped":                           # columns 198 / 199 of feat_imnet's first layer: rel_y, rel_x
+        k = "feat_imnet.net.0.linear.weight"
+        w = np.array(sd[k])
+        w[:, [198, 199]] = w[:, [199, 198]]
+        sd = {**sd, k: w}
+    elif name == "replicate_padding":
+        mp.setattr(O, "bilinear_sample", _replicate_sample)
+    elif name == "nearest_image":
+        mp.setattr(O, "bilinear_sample", _nearest_image_sample)
+    elif name == "lr_for_hr":
+        img = None
+    else:
+        mp.setattr(O, "_query_axes", _axes_mutant(name))
+    return O.decode_stage1(feat, inp, t, sd, HH, WW, img=img, shift=shift)
+
+
+@pytest.mark.parametrize("grid", [(37, 45), (64, 80)], ids=["37x45", "64x80"])
+@pytest.mark.parametrize("image,shift", [(False, None), (True, None), (False, (-1, 1)), (True, (1, -1))],
+                         ids=["lr", "hrimg", "lr-shift-1+1", "hrimg-shift+1-1"])
+def test_stage1_inputs_tell_a_wrong_stage1_from_a_right_one(sd, monkeypatch, grid, image, shift):
+    """The inputs of the GPU stage-1 tests discriminate, and the RGB would not: each wrong restatement of stage 1 --
+    the item times swapped (for both nets, for flow_imnet only), rel_y / rel_x swapped, replicate for zero padding
+    (told at the border only: 4 pixels inside it nothing changes), the flow stage's image read at its nearest pixel,
+    the LR image where the HR image was asked for; with a shift: the remap to HRfeat dropped, the nearest indices
+    at the unshifted query, rel at the shifted query, the bilinear gathers at the unshifted query -- breaks the
+    project's oracle bound |d| <= 1e-4 |ref| + 1e-6 on hrfeat or on flow by at least 10x.  Stage 2 run on the right
+    hrfeat and a wrong flow brings the RGB at least 50x closer to the bound than that flow was (STAGE1_FLOW_ONLY,
+    and rel_swapped seen through its flow).  About the reference and the inputs only: nothing of the kernels is asked."""
+    import stage2_inputs as S
+    HH, WW = grid
+    feat, inp, t, img = _stage1_case(image)
+    hrf, flow = O.decode_stage1(feat, inp, t, sd, HH, WW, img=img, shift=shift)
+    assert np.isfinite(hrf).all() and np.isfinite(flow).all()
+    rgb = O.decode_stage2(feat, inp, hrf, flow, t, sd, HH, WW, img=img)
+    names = [n for n in STAGE1_MUTANTS if n != ("nearest_image" if image else "lr_for_hr")]
+    names += STAGE1_SHIFT_MUTANTS if shift is not None else []
+    worst, factor = {}, {}
+    for name in names:
+        with monkeypatch.context() as mp:
+            mh, mf = _stage1_mutant(name, mp, sd, feat, inp, t, HH, WW, img, shift)
+        rh, rf = S.bound_ratio(mh, hrf), S.bound_ratio(mf, flow)
+        worst[name] = (float(rh.max()), float(rf.max()))
+        if name in STAGE1_FLOW_ONLY:
+            assert np.array_equal(mh, hrf), name
+        if name == "replicate_padding" and shift is None:
+            assert rh.max() == 0 and rf[:, 4:HH - 4, 4:WW - 4].max() == 0 and rf.max() > 0
+        if name in STAGE1_FLOW_ONLY or name == "rel_swapped":
+            rr = float(S.bound_ratio(O.decode_stage2(feat, inp, hrf, mf, t, sd, HH, WW, img=img), rgb).max())
+            factor[name] = (float(rf.max()), rr)
+    print(grid, "hrimg" if image else "lr", shift, "hrfeat / flow x bound:",
+          {k: (round(a, 1), round(b, 1)) for k, (a, b) in worst.items()})
+    print(grid, "hrimg" if image else "lr", shift, "flow x bound -> RGB x bound:",
+          {k: (round(a, 1), round(b, 2)) for k, (a, b) in factor.items()})
+    assert min(max(v) for v in worst.values()) >= 10, worst
+    assert all(a >= 50 * b for a, b in factor.values()), factor
+    again = O.decode_stage1(feat, inp, t, sd, HH, WW, img=img, shift=shift)              # the patches are undone
+    assert np.array_equal(again[0], hrf) and np.array_equal(again[1], flow)
+
+
+def test_stage1_oracle_in_fp32_is_within_the_bound(sd):
+    """The room the bound leaves: decode_stage1 run in fp32 stays inside |d| <= 1e-4 |ref| + 1e-6 of the fp64 run,
+    on both outputs, at every (grid, image, shift) the GPU tests use (stage1_cases.CASES)."""
+    import stage1_cases as C
+    import stage2_inputs as S
+    worst = 0.0
+    for case in C.CASES:
+        (HH, WW), image, shift = case
+        feat, inp, t, img = _stage1_case(image)
+        ref = O.decode_stage1(feat, inp, t, sd, HH, WW, img=img, shift=shift)
+        r32 = O.decode_stage1(feat, inp, t, sd, HH, WW, dtype=np.float32, img=img, shift=shift)
+        assert r32[0].dtype == np.float32 and r32[1].dtype == np.float32
+        ratios = [float(S.bound_ratio(a, b).max()) for a, b in zip(r32, ref)]
+        print(C.case_id(case), "fp32 oracle / bound: hrfeat %.4f flow %.4f" % tuple(ratios))
+        worst = max(worst, *ratios)
+    assert worst <= 1.0
