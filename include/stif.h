@@ -363,7 +363,8 @@ typedef struct {
  * of the whole virtual grid; pixel (py, px) of the rectangle uses the table entries y0 + py, x0 + px.  flow:
  * [n][hh][ww][4]; hrfeat: the pixel's row in the F layout (F must contain the query rectangle; with F = the
  * query rectangle that is [n][hh][ww][64]).  flow = NULL: feat_imnet only (HRfeat of the rectangle, e.g. of an
- * F rectangle larger than the window stage 2 is run for).  Tables with hr_y / hr_x are STIF_E_INVALID. */
+ * F rectangle larger than the window stage 2 is run for).  Tables with hr_y / hr_x are STIF_E_INVALID (the
+ * windowed flow stage of a shifted query is stif_dec_flow_win). */
 int stif_dec_stage1_win(const float* proj, const float* mlp, const stif_dec_tables* tab, const stif_dec_image* img,
                         const float* t, float* hrfeat, float* flow, int n, int h, int w, int HH, int WW, int flags,
                         int* status, void* stream, const stif_dec_window* win);
@@ -379,6 +380,45 @@ int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int
 int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
                         const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n, int h,
                         int w, int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win);
+
+/* ---- local ensemble over a window (decoding_localensemble, Sakuya_arch_test.py:962-1085): per shift k (k = 0..3
+ * numbers the reference's shifts (-1,-1), (-1,1), (1,-1), (1,1)): stif_dec_stage1_win(flow = NULL) with the shifted
+ * tables (hr_y = hr_x = NULL) over an F that holds the remap rectangle, stif_dec_flow_win, stif_dec_bounds, a
+ * feat-only pass over a larger F if the box asks for one, stif_dec_stage2_blend_win -- the four shifts one after
+ * the other on one stream (see stif_dec_stage2_blend_win for the order). ---- */
+
+/* flow_imnet alone over the query rectangle, with the tables of a shifted query (hr_y / hr_x required): the HRfeat
+ * operand of pixel (py, px) is the row of HR pixel (hr_y[py], hr_x[px]), read from hrfeat in the F layout.  F need
+ * not contain the query rectangle; it must contain the remap rectangle [hr_y[y0], hr_y[y0 + hh - 1]] x
+ * [hr_x[x0], hr_x[x0 + ww - 1]] (the tables are monotone).  Every index is clamped into F before use; if one had to
+ * be, bit 2 (value 4) is OR'ed into *status (F was too small: the flow is wrong, no read left the buffer).
+ * flow: [n][hh][ww][4], bit-identical to stif_dec_stage1_ex's flow with the same tables at the same pixels.
+ * img must be NULL (STIF_E_INVALID otherwise). */
+int stif_dec_flow_win(const float* proj, const float* mlp, const stif_dec_tables* tab, const stif_dec_image* img,
+                      const float* t, const float* hrfeat, float* flow, int n, int h, int w, int HH, int WW, int flags,
+                      int* status, void* stream, const stif_dec_window* win);
+
+/* The blend of decode k into the output.  Zero-initialise, then fill.  rel_y[j] / rel_x[j]: the rel_y / rel_x
+ * tables (stif_dec_tables, whole virtual grid) of shift j = 0..3 in the reference's order.  The weight of decode k
+ * at (py, px) is computed in the epilogue, in fp32 with every operation rounded on its own:
+ * a_j = |rel_y[j][py] * rel_x[j][px]| + 1e-9f, tot = ((a_0 + a_1) + a_2) + a_3, w_k = a_(3-k) / tot. */
+typedef struct {
+  int k;                       /* which of the four decodes this launch is: 0..3 */
+  int accumulate;              /* 0: out = w_k * rgb (out is not read); 1: out = fma(rgb, w_k, out) */
+  const float* rel_y[4];
+  const float* rel_x[4];
+} stif_dec_blend;
+
+/* stif_dec_stage2_win with the local ensemble's blending epilogue: the first of a window's four launches
+ * (accumulate = 0) stores w_k * rgb, the other three store fma(rgb, w_k, out), one after the other on one stream.
+ * stif_dec_blend4 as built for gfx950 computes fma(p_3, w_3, fma(p_2, w_2, fma(p_0, w_0, p_1 * w_1))) (the
+ * compiler contracts its first sum into the second product), so the launch order k = 1, 0, 2, 3 gives its bits;
+ * the order 0, 1, 2, 3 gives the uncontracted sum's first rounding instead (a last-place difference).  Each
+ * output element is written by one lane (no atomics).  img must be NULL.  Status bits as stif_dec_stage2_win. */
+int stif_dec_stage2_blend_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                              const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n,
+                              int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                              const stif_dec_blend* blend, const stif_dec_window* win);
 
 /* ---- evaluation: PSNR / SSIM of decoded frames against ground truth (myutils.py:1151-1174, util.py:105-174) ---- */
 

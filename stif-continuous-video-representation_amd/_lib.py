@@ -71,6 +71,12 @@ class DecWindow(C.Structure):
         ("out_item", C.c_longlong), ("out_plane", C.c_longlong), ("out_pitch", C.c_int)]
 
 
+class DecBlend(C.Structure):
+    """stif_dec_blend: which of the local ensemble's four decodes a blending stage 2 is, whether it adds to the
+    output or starts it, and the rel_y / rel_x tables of the four shifted queries its weight is computed from."""
+    _fields_ = [("k", C.c_int), ("accumulate", C.c_int), ("rel_y", _P * 4), ("rel_x", _P * 4)]
+
+
 METRIC_Y, METRIC_SSIM, METRIC_FLOAT = 1, 2, 4   # stif_metric_args.flags (stif.h STIF_METRIC_*)
 FSSIM_VOLUME, FSSIM_PLANAR = 0, 1               # stif_metric_float's mode (stif.h STIF_FSSIM_*)
 
@@ -130,6 +136,10 @@ EXPORTS = {
     "stif_dec_bounds": (C.c_int, [_P, C.POINTER(DecTables), _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(DecWindow)]),
     "stif_dec_stage2_win": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecImage), _P, _P]
                             + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
+    "stif_dec_flow_win": (C.c_int, [_P, _P, C.POINTER(DecTables), C.POINTER(DecImage), _P, _P, _P]
+                          + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
+    "stif_dec_stage2_blend_win": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecImage), _P, _P]
+                                  + [C.c_int] * 6 + [_P, _P, C.POINTER(DecBlend), C.POINTER(DecWindow)]),
     "stif_dec_blend4": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "stif_upsample_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "stif_resize_frames": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int,

@@ -274,21 +274,54 @@ STIF_DEV Pixel pixel_of(int wv, int lane, int n, int HH, int WW, const stif_dec_
   return o;
 }
 
+// The local ensemble's blend weight of decode bl.k at row gy / column gx of the virtual grid, as
+// coords.ensemble_weights computes it in numpy's fp32: area_j = |rel_y_j rel_x_j| + 1e-9 of the four shifted
+// queries, tot = ((a_0 + a_1) + a_2) + a_3, decode k weighted by the diagonally opposite area (3 - k) over tot.
+// Every operation rounds on its own (no contraction) and the division is the correctly rounded one.
+STIF_DEV float blend_weight(const stif_dec_blend& bl, int gy, int gx) {
+#pragma clang fp contract(off)
+  float a[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) a[j] = __fadd_rn(fabsf(__fmul_rn(bl.rel_y[j][gy], bl.rel_x[j][gx])), 1e-9f);
+  const float tot = __fadd_rn(__fadd_rn(__fadd_rn(a[0], a[1]), a[2]), a[3]);
+  const float ak = bl.k == 0 ? a[3] : bl.k == 1 ? a[2] : bl.k == 2 ? a[1] : a[0];
+  return __fdiv_rn(ak, tot);
+}
+
 // Stage 2's epilogue: the pixel's RGB (o4 + bias) into the NCHW output -- WIN: through win's output addressing --
 // and, REPORT, the range report.  Stage 1's flow counts too: the warpgrid clamp maps a NaN flow to a finite grid,
 // so an out-of-range flow_imnet operand would otherwise leave a finite but wrong pixel.
-template <bool WIN, bool REPORT>
+// BLEND (local ensemble, decode bl.k of four launched one after the other on one stream): the first launch
+// (bl.accumulate = 0) stores w_k rgb without reading out, the others store fma(rgb, w_k, out), spelled out so that
+// they cannot come out differently.  k_blend4 as the compiler builds it for gfx950 contracts
+// `r = p0 w0; r += p1 w1` into fma(p0, w0, p1 * w1): its one rounded product is decode 1's, then come the fmas of
+// decodes 0, 2 and 3 -- so launching the decodes in the order 1, 0, 2, 3 reproduces its bits (model.py does).
+// The pixel's lane owns its three output elements: no atomics.
+template <bool WIN, bool REPORT, bool BLEND = false>
 STIF_DEV void store_rgb(float* __restrict__ out, const float* __restrict__ mlp, const float* o4, const f32x4 fv,
-                        int item, int py, int px, int HH, int WW, const stif_dec_window& win, int* status) {
+                        int item, int py, int px, int HH, int WW, const stif_dec_window& win, int* status,
+                        const stif_dec_blend& bl) {
+  static_assert(WIN || !BLEND, "the blending epilogue is the windowed stages'");
   const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
   float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
                  : out + (size_t)item * 3 * plane + (size_t)py * WW + px;
   bool bad = not_finite((fv[0] + fv[1]) + (fv[2] + fv[3]));
+  float rgb[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float v = o4[c] + mlp[E_B4 + c];
-    bad |= not_finite(v);
-    o[c * plane] = v;
+    rgb[c] = o4[c] + mlp[E_B4 + c];
+    bad |= not_finite(rgb[c]);
+    if constexpr (!BLEND) o[c * plane] = rgb[c];
+  }
+  if constexpr (BLEND) {
+    const float wk = blend_weight(bl, win.y0 + py, win.x0 + px);
+    if (!bl.accumulate) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c * plane] = __fmul_rn(rgb[c], wk);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c * plane] = __fmaf_rn(rgb[c], wk, o[c * plane]);
+    }
   }
   if constexpr (REPORT) report_range_w<WIN>(status, bad);
 }
@@ -388,14 +421,16 @@ template <int MODE, bool HRIMG>
 constexpr int S1 = OCC1<MODE, HRIMG> == 4 ? 4 : OCC1<MODE, HRIMG> == 3 ? 6 : SEG1;
 // WIN: the pixels are those of win's query rectangle (row-major, hh x ww per item); the tables are read at the
 // pixel's row / column of the virtual grid, flow is written at the pixel's index in the rectangle and HRfeat at its
-// place in win's F rectangle; the whole-grid instantiations (WIN false) never read win.
+// place in win's F rectangle; the whole-grid instantiations (WIN false) never read win.  WIN and MODE 2: the
+// remapped HRfeat row is read from the F layout, its index clamped into F and a clamp reported (bit 2 of *status,
+// which no other instantiation touches), as bilin_hr does with bit 1.
 template <int MODE, bool HRIMG, int F16, bool WIN>
 __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<MODE, HRIMG>))) void k_dec1(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      stif_dec_tables tb, stif_dec_image im,
                                                      const float* __restrict__ tq, float* __restrict__ hrfeat,
                                                      float* __restrict__ flow, int n, int h, int w, int HH,
-                                                     int WW, stif_dec_window win) {
-  static_assert(!(WIN && MODE == 2), "the local ensemble's remapped HRfeat operand has no windowed form");
+                                                     int WW, stif_dec_window win, int* status) {
+  static_assert(!(WIN && MODE == 2 && HRIMG), "the windowed flow-only stage takes no high-resolution image");
   // two segment buffers of SEG1 tiles + the flow's last layer (plain [4][256], resident)
   constexpr bool OCC3 = S1<MODE, HRIMG> != SEG1;             // 3 or 4 workgroups per CU
   constexpr bool OCC4 = OCC1<MODE, HRIMG> == 4;
@@ -511,10 +546,17 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
     // the query's HRfeat operand: the HR pixel nearest to the shifted query (grid_sample nearest
     // of HRfeat at coord_, Sakuya_arch_test.py:1022-1025)
     Bilin b;
-    b.o00 = b.o01 = b.o10 = b.o11 = tb.hr_y[py] * WW + tb.hr_x[px];
+    if constexpr (WIN) {
+      const int ry = tb.hr_y[py] - win.fy0, rx = tb.hr_x[px] - win.fx0;
+      const int y = min(max(ry, 0), win.fh - 1), x = min(max(rx, 0), win.fw - 1);
+      if (status != nullptr && (y != ry || x != rx)) atomicOr(status, 4);
+      b.o00 = b.o01 = b.o10 = b.o11 = y * win.fw + x;
+    } else {
+      b.o00 = b.o01 = b.o10 = b.o11 = tb.hr_y[py] * WW + tb.hr_x[px];
+    }
     b.w00 = 1.f;
     b.w01 = b.w10 = b.w11 = 0.f;
-    gather64<8>(hr, hrfeat + (size_t)item * HH * WW * 64, 64, 0, b, hf);
+    gather64<8>(hr, hrfeat + (size_t)item * (WIN ? (size_t)win.fh * win.fw : (size_t)HH * WW) * 64, 64, 0, b, hf);
   }
 
   // ---- flow_imnet layer 0: W[:, :64] . HRfeat + bilinear(P2 at the HR centre) + w_t * t + b
@@ -610,12 +652,13 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
 // WIN: the pixels are those of win's query rectangle, flow is read at the
 // pixel's index in the rectangle, the linspace base at its row / column of the virtual grid, HRfeat in win's F
 // rectangle (bilin_hr) and the RGB goes through win's output addressing.
-template <bool HRIMG, int F16, bool WIN>
+template <bool HRIMG, int F16, bool WIN, bool BLEND = false>
 __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DEC2_WPE))) void k_dec2(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      const float* __restrict__ hrfeat, const float* __restrict__ flow,
                                                      stif_dec_tables tb, stif_dec_image im,
                                                      const float* __restrict__ tq, float* __restrict__ out, int n,
-                                                     int h, int w, int HH, int WW, int* status, stif_dec_window win) {
+                                                     int h, int w, int HH, int WW, int* status, stif_dec_window win,
+                                                     stif_dec_blend bl) {
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEG * T];
   const int lane = threadIdx.x & 63, hf = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
@@ -738,7 +781,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) o4[c] += __shfl_xor(o4[c], 32);   // the other lane half's 128 features
-  if (pix.valid && hf == 0) store_rgb<WIN, F16 != 0>(out, mlp, o4, fv, item, py, px, HH, WW, win, status);
+  if (pix.valid && hf == 0) store_rgb<WIN, F16 != 0, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
 }
 
 
@@ -822,11 +865,11 @@ STIF_DEV void gather_q(R32* dst, const float* __restrict__ base, int stride, int
   }
 }
 
-template <bool WIN>   // WIN: as k_dec2's
+template <bool WIN, bool BLEND = false>   // WIN, BLEND: as k_dec2's
 __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec2q(
     const float* __restrict__ proj, const float* __restrict__ mlp, const float* __restrict__ hrfeat,
     const float* __restrict__ flow, stif_dec_tables tb, const float* __restrict__ tq, float* __restrict__ out, int n,
-    int h, int w, int HH, int WW, int* status, stif_dec_window win) {
+    int h, int w, int HH, int WW, int* status, stif_dec_window win, stif_dec_blend bl) {
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEGQ * T];
   const int lane = threadIdx.x & 63, q = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -962,7 +1005,7 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
     o4[c] += __shfl_xor(o4[c], 16);
     o4[c] += __shfl_xor(o4[c], 32);
   }
-  if (pix.valid && q == 0) store_rgb<WIN, true>(out, mlp, o4, fv, item, py, px, HH, WW, win, status);
+  if (pix.valid && q == 0) store_rgb<WIN, true, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
 }
 
 // k_dec_bounds: the box (rows ymin..ymax, columns xmin..xmax of the virtual grid, inclusive) of every HRfeat corner
@@ -1129,7 +1172,7 @@ int dec_stage1(const char* me, const float* proj, const float* mlp, const stif_d
     with_bool(f16, [&](auto f16x3) {
       hipLaunchKernelGGL((k_dec1<decltype(mode)::value, decltype(hrimg)::value, decltype(f16x3)::value, WIN>), grid,
                          dim3(NW1 * 64), 0, (hipStream_t)stream, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH,
-                         WW, wn);
+                         WW, wn, (int*)nullptr);
     });
   };
   if constexpr (WIN) {
@@ -1146,13 +1189,48 @@ int dec_stage1(const char* me, const float* proj, const float* mlp, const stif_d
   return stif_check_launch(me);
 }
 
-// Stage 2 behind its three entry points (WIN as dec_stage1's).  f16x3 operands without an HR image go to k_dec2q
+// The windowed flow-only stage (local ensemble): flow_imnet over win's query rectangle, its HRfeat operand the row of
+// HR pixel (hr_y, hr_x) in the F layout.  F need not hold the query rectangle, only the remap rectangle -- which the
+// kernel enforces (clamp + bit 2 of *status), since the tables live on the device.
+int dec_flow_win(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
+                 const stif_dec_image* img, const float* t, const float* hrfeat, float* flow, int n, int h, int w,
+                 int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win) {
+  if (!proj || !mlp || !tables_ok(tab) || !t || !hrfeat || !flow || n < 1 || h < 1 || w < 1)
+    return window_fail(me, "bad arguments (null pointer or empty shape)");
+  if (img) return window_fail(me, "a high-resolution image (img) is not supported here: pass NULL");
+  if (!tab->hr_y || !tab->hr_x) return window_fail(me, "the tables carry no hr_y / hr_x remap (local ensemble)");
+  stif_dec_window wn{};
+  if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
+  const long long total = (long long)n * wn.hh * wn.ww;
+  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
+  with_bool(flags & STIF_CONV_F16X3, [&](auto f16x3) {
+    // MODE 2 only reads hrfeat
+    hipLaunchKernelGGL((k_dec1<2, false, decltype(f16x3)::value, true>), grid, dim3(NW1 * 64), 0, (hipStream_t)stream,
+                       proj, mlp, *tab, stif_dec_image{}, t, const_cast<float*>(hrfeat), flow, n, h, w, HH, WW, wn,
+                       status);
+  });
+  return stif_check_launch(me);
+}
+
+// the reason a stif_dec_blend is invalid, or null
+const char* blend_invalid(const stif_dec_blend* b) {
+  if (!b) return "null blend";
+  if (b->k < 0 || b->k > 3) return "blend k outside 0..3";
+  if (b->accumulate != 0 && b->accumulate != 1) return "blend accumulate must be 0 or 1";
+  for (int j = 0; j < 4; ++j)
+    if (!b->rel_y[j] || !b->rel_x[j]) return "blend with a null rel_y / rel_x table";
+  return nullptr;
+}
+
+// Stage 2 behind its entry points (WIN as dec_stage1's).  blend (WIN only; checked by the caller): the blending
+// epilogue of the local ensemble instead of the plain store.  f16x3 operands without an HR image go to k_dec2q
 // (16 pixels per wave, four waves per SIMD: C2 stage 2 17.55-17.79 -> 17.32-17.34 ms, profiles/r04_dec2q4_ab.log);
 // the fp32 and the HR-image stages to k_dec2.
 template <bool WIN>
 int dec_stage2(const char* me, const float* proj, const float* mlp, const float* hrfeat, const float* flow,
                const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n, int h, int w,
-               int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win) {
+               int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win,
+               const stif_dec_blend* blend = nullptr) {
   const bool args_ok = proj && mlp && hrfeat && flow && tables_ok(tab) && image_ok(img) && t && out && n >= 1 &&
                        h >= 1 && w >= 1;
   stif_dec_window wn{};
@@ -1166,9 +1244,21 @@ int dec_stage2(const char* me, const float* proj, const float* mlp, const float*
   const long long total = (long long)n * (WIN ? wn.hh : HH) * (WIN ? wn.ww : WW);
   auto grid = [&](int wg_pixels) { return dim3((unsigned)((total + wg_pixels - 1) / wg_pixels)); };
   hipStream_t st = (hipStream_t)stream;
+  const stif_dec_blend bl = blend ? *blend : stif_dec_blend{};
+  if constexpr (WIN) {
+    if (blend) {   // no high-resolution image (the caller's check): k_dec2q, or k_dec2 for fp32 operands
+      if (f16)
+        hipLaunchKernelGGL((k_dec2q<true, true>), grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat,
+                           flow, *tab, t, out, n, h, w, HH, WW, status, wn, bl);
+      else
+        hipLaunchKernelGGL((k_dec2<false, 0, true, true>), grid(DEC2_NW * 32), dim3(DEC2_NW * 64), 0, st, proj, mlp,
+                           hrfeat, flow, *tab, stif_dec_image{}, t, out, n, h, w, HH, WW, status, wn, bl);
+      return stif_check_launch(me);
+    }
+  }
   if (f16 && !img) {
     hipLaunchKernelGGL(k_dec2q<WIN>, grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
-                       out, n, h, w, HH, WW, status, wn);
+                       out, n, h, w, HH, WW, status, wn, bl);
   } else {
     const stif_dec_image im = img ? *img : stif_dec_image{};
     with_bool(img != nullptr, [&](auto hrimg) {
@@ -1176,7 +1266,7 @@ int dec_stage2(const char* me, const float* proj, const float* mlp, const float*
         if constexpr (decltype(hrimg)::value || !decltype(f16x3)::value)   // the other pair is k_dec2q's, above
           hipLaunchKernelGGL((k_dec2<decltype(hrimg)::value, decltype(f16x3)::value, WIN>), grid(DEC2_NW * 32),
                              dim3(DEC2_NW * 64), 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW,
-                             status, wn);
+                             status, wn, bl);
       });
     });
   }
@@ -1227,6 +1317,25 @@ extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const fl
                                    const stif_dec_window* win) {
   return dec_stage2<true>("stif_dec_stage2_win", proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, flags,
                           status, stream, win);
+}
+
+extern "C" int stif_dec_flow_win(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                 const stif_dec_image* img, const float* t, const float* hrfeat, float* flow, int n,
+                                 int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                 const stif_dec_window* win) {
+  return dec_flow_win("stif_dec_flow_win", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, status,
+                      stream, win);
+}
+
+extern "C" int stif_dec_stage2_blend_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                         const stif_dec_tables* tab, const stif_dec_image* img, const float* t,
+                                         float* out, int n, int h, int w, int HH, int WW, int flags, int* status,
+                                         void* stream, const stif_dec_blend* blend, const stif_dec_window* win) {
+  static const char* const me = "stif_dec_stage2_blend_win";
+  if (const char* why = blend_invalid(blend)) return window_fail(me, why);
+  if (img) return window_fail(me, "a high-resolution image (img) is not supported here: pass NULL");
+  return dec_stage2<true>(me, proj, mlp, hrfeat, flow, tab, nullptr, t, out, n, h, w, HH, WW, flags, status, stream,
+                          win, blend);
 }
 
 extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int n, int HH, int WW,

@@ -796,17 +796,22 @@ class LunaTokis(nn.Module):
         _drain(self._decode_steps(proj, [self._time_vec(tq, B) for tq in times], HH, WW, tab, outs, image))
         return outs
 
-    def decoding(self, times=None, scale=None, window=None, tile=None):
+    def decoding(self, times=None, scale=None, window=None, tile=None, ensemble=False):
         """LunaTokis.decoding (:364-459): list over times of [B,3,HH,WW] (unclamped).
 
         window=(y0, x0, hh, ww): only that rectangle of the virtual HH x WW grid, [B,3,hh,ww], bit-identical to
         the crop of the full decode and at the cost of the rectangle (``_decode_windowed``).  tile=(th, tw): the
         same output as without it, rendered by windows of at most th x tw, so the decoder scratch is bounded by
         the largest tile's HRfeat rectangle instead of HH * WW.  Either reads a few ints back from the device per
-        window and time, so such a call cannot be captured in a hipGraph."""
-        return self._call(self._decoding, times, scale, window, tile)
+        window and time, so such a call cannot be captured in a hipGraph.
 
-    def _decoding(self, times=None, scale=None, window=None, tile=None):
+        ensemble=True: the reference's local ensemble (decoding_localensemble, :962-1085) for any batch, window or
+        tile -- four decodes with the query shifted by half an LR pixel, blended per HR pixel by the diagonally
+        opposite |rel_y rel_x| area (``_decode_ensemble``); bit-identical to ``decoding_localensemble`` item by
+        item.  Over the whole grid without tiles it reads nothing back and can be captured."""
+        return self._call(self._decoding, times, scale, window, tile, ensemble)
+
+    def _decoding(self, times=None, scale=None, window=None, tile=None, ensemble=False):
         if times is None:
             raise ValueError("times must be a list of query times")
         if self._feat is None:
@@ -815,6 +820,8 @@ class LunaTokis(nn.Module):
         HH, WW = _hr_size(H, Wd, scale)
         tab = self._tab(H, Wd, HH, WW)
         tvs = [self._time_vec(tq, B) for tq in times]
+        if ensemble:
+            return self._decode_ensemble(tvs, H, Wd, HH, WW, window, tile)
         if window is not None or tile is not None:
             return self._decode_windowed(tvs, HH, WW, tab, window, tile)
         outs = [self._empty(B, 3, HH, WW) for _ in times]
@@ -826,12 +833,12 @@ class LunaTokis(nn.Module):
             proj, [t[a:b] for t in tvs], HH, WW, tab, [o[a:b] for o in outs]))
         return outs
 
-    def decoding_pairs(self, pairs, times=None, scale=None):
+    def decoding_pairs(self, pairs, times=None, scale=None, ensemble=False):
         """``decoding`` for the items ``pairs`` (indices into the current latent, in that order) only: list over
         times of [len(pairs),3,HH,WW]; a query time holds one value or one per selected pair.  Items are decoded
         independently, so each output equals that item's slice of a ``decoding`` of the whole latent bit for bit.
         The latent is left as it is (the video stream renderer decodes the pairs of a chunk that share a number
-        of query times in one call)."""
+        of query times in one call).  ensemble: as ``decoding``'s."""
         feat, inp = self.__dict__.get("_feat"), self.__dict__.get("inp")
         if feat is None:
             raise RuntimeError("decoding needs gen_feat first")
@@ -840,11 +847,11 @@ class LunaTokis(nn.Module):
         if not pairs or min(pairs) < 0 or max(pairs) >= B:
             raise ValueError(f"pairs must be indices into the {B} items of the latent, got {pairs}")
         if pairs == list(range(B)):
-            return self.decoding(times, scale)
+            return self.decoding(times, scale, ensemble=ensemble)
         idx = torch.tensor(pairs, device=feat.device, dtype=torch.long)
         self._feat, self.inp = feat.index_select(1, idx), inp.index_select(0, idx)
         try:
-            return self.decoding(times, scale)
+            return self.decoding(times, scale, ensemble=ensemble)
         finally:
             self._feat, self.inp = feat, inp
 
@@ -952,6 +959,100 @@ class LunaTokis(nn.Module):
         if st is not None and int(st.item()) & 2:
             raise L.StifError("windowed decode: stage 2 gathered outside its HRfeat rectangle (stif_dec_bounds and "
                               "stage 2 disagree): the result is wrong")
+        return outs
+
+    # ------------------------------------------------------------------ local ensemble over windows
+    def _ensemble_steps(self, proj, tvs, HH, WW, tabs, outs, rect):
+        """The local ensemble of every query time for the window ``rect`` into ``outs`` ([n,3,hh,ww] views;
+        generator).  Per time and per shift k (``tabs``: the four shifted tables in the reference's order): HRfeat
+        of the shifted query over the remap rectangle R_k, which the host knows from the monotone hr_y / hr_x tables;
+        the flow over W with its HRfeat operand read at (hr_y, hr_x) from R_k; the box of stage 2's gathers;
+        F = box U R_k, and HRfeat over F if that is larger than R_k; stage 2 over W, blending w_k rgb into ``out``
+        in place (the first stores, the others accumulate -- the four launches of a window follow each other on one
+        stream, in ops.ENSEMBLE_BLEND_ORDER, the order that gives stif_dec_blend4's roundings).  One shift's HRfeat and flow are alive at a time.  A window that is the whole grid takes F = the
+        whole grid and reads nothing back."""
+        n = proj.shape[0]
+        y0, x0, hh, ww = rect
+        whole = rect == (0, 0, HH, WW)
+        mlp, fl, st = self.layers["dec.mlp"], self._dec_flags, self._status
+        win = ops.dec_window(rect, HH, WW)
+        blends = {k: ops.dec_blend(k, tabs, accumulate=i > 0) for i, k in enumerate(ops.ENSEMBLE_BLEND_ORDER)}
+        box = None if whole else torch.empty(4, device=self.device, dtype=torch.int32)
+
+        def hrfeat(tab, frect, a, b, t):   # feat_imnet at the shifted query over frect, items [a, b)
+            hf = self._empty(b - a, frect[2], frect[3], 64)
+            ops.dec_stage1(proj[a:b], mlp, tab.plain, t[a:b], hf, None, flags=fl, status=st,
+                           window=ops.dec_window(frect, HH, WW))
+            return hf
+
+        for t, out in zip(tvs, outs):
+            largest = None
+            for k in ops.ENSEMBLE_BLEND_ORDER:
+                tab = tabs[k]
+                rrect = rect if whole else tab.remap_rect(rect)
+                flow = self._empty(n, hh, ww, 4)
+                hrf = hrfeat(tab, rrect, 0, n, t)
+                ops.dec_flow_win(proj, mlp, tab, t, hrf, flow, flags=fl, status=st,
+                                 window=ops.dec_window(rect, HH, WW, rrect))
+                frect = rrect
+                if not whole:
+                    ops.dec_bounds(flow, tab, box, win)
+                    ymin, ymax, xmin, xmax = box.tolist()   # the device-to-host read (synchronises this stream)
+                    fy0, fx0 = min(ymin, rrect[0]), min(xmin, rrect[1])
+                    frect = (fy0, fx0, max(ymax + 1, rrect[0] + rrect[2]) - fy0,
+                             max(xmax + 1, rrect[1] + rrect[3]) - fx0)
+                per = max(1, self.dec_chunk_px // (frect[2] * frect[3]))
+                if largest is None or frect[2] * frect[3] > largest[2] * largest[3]:
+                    largest = frect
+                self.window_peak_scratch_bytes = max(
+                    self.window_peak_scratch_bytes, n * (rrect[2] * rrect[3] * 256 + hh * ww * 16),
+                    min(n, per) * frect[2] * frect[3] * 256 + n * hh * ww * 16)
+                wf = ops.dec_window(rect, HH, WW, frect)
+                if frect == rrect:
+                    ops.dec_stage2(proj, mlp, hrf, flow, tab, t, out, flags=fl, status=st, window=wf, blend=blends[k])
+                    del hrf
+                else:
+                    del hrf   # the caching allocator reuses it for the F buffer (same stream)
+                    for a in range(0, n, per):
+                        b = min(n, a + per)
+                        hf = hrfeat(tab, frect, a, b, t)
+                        ops.dec_stage2(proj[a:b], mlp, hf, flow[a:b], tab, t[a:b], out[a:b], flags=fl, status=st,
+                                       window=wf, blend=blends[k])
+                        del hf
+                del flow
+            self.last_window_F = largest
+            yield
+
+    def _decode_ensemble(self, tvs, H, Wd, HH, WW, window, tile):
+        """``decoding(ensemble=True)`` over ``window`` (None: the whole grid) by tiles of at most ``tile`` (None:
+        one), each a window blended in place into the output through its strides (``_ensemble_steps``).
+        ``last_window_F`` is the largest HRfeat rectangle of the four shifts of the last window decoded and
+        ``window_peak_scratch_bytes`` the largest HRfeat + flow scratch alive in the call (one shift's)."""
+        B = tvs[0].shape[0] if tvs else self._feat.shape[1]
+        region = check_window((0, 0, HH, WW) if window is None else window, HH, WW)
+        rects = [region] if tile is None else tile_windows(region, tile)
+        whole = rects == [(0, 0, HH, WW)]
+        if not whole and torch.cuda.is_current_stream_capturing():
+            raise L.StifError("a windowed / tiled decode reads the HRfeat bounding box back on the host: "
+                              "it cannot be captured in a hipGraph")
+        tabs = [self._tab(H, Wd, HH, WW, s) for s in ops.ENSEMBLE_SHIFTS]
+        ry, rx, rh, rw = region
+        outs = [self._empty(B, 3, rh, rw) for _ in tvs]
+        self.last_window_F, self.window_peak_scratch_bytes = None, 0
+        st = self._status
+        if st is not None and self._dec_flags == 0 and not whole:
+            st.zero_()   # fp32 operands: only the windows' bits 1 and 2 are read below
+        per = max(1, self.dec_chunk_px // max(r[2] * r[3] for r in rects))
+
+        def tiles(proj, a, b):
+            for r in rects:
+                views = [o[a:b, :, r[0] - ry:r[0] - ry + r[2], r[1] - rx:r[1] - rx + r[3]] for o in outs]
+                yield from self._ensemble_steps(proj, [t[a:b] for t in tvs], HH, WW, tabs, views, r)
+        self._decode_passes(B, per, True, tiles)
+        # with F the whole grid no index can leave it: nothing to read back (the call may be being captured)
+        if st is not None and not whole and int(st.item()) & 6:
+            raise L.StifError("windowed ensemble decode: a gather left its HRfeat rectangle (the remap rectangle or "
+                              "stif_dec_bounds disagrees with the kernels): the result is wrong")
         return outs
 
     def decoding_window(self, times=None, scale=None, center=(0.0, 0.0), size=None):

@@ -333,7 +333,8 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, ke
 
 class DecTablesDev:
     """Device copies of coords.dec_tables(h, w, HH, WW[, shift]) + the C struct pointing at them.
-    With a shift (local ensemble) the HR remap tables are set too."""
+    With a shift (local ensemble) the HR remap tables are set too; ``plain`` is then the same tables without the
+    remap (hr_y = hr_x = NULL), as the windowed feat-only pass of a shifted query takes them."""
 
     def __init__(self, h, w, HH, WW, device="cuda", shift=None):
         tab = dec_tables(h, w, HH, WW, shift)
@@ -341,6 +342,43 @@ class DecTablesDev:
         self._t = {k: torch.from_numpy(np.ascontiguousarray(tab[k])).to(device) for k in keys}
         self.c = L.DecTables(*[self._t[k].data_ptr() for k in keys])
         self.shape = (h, w, HH, WW)
+        self.plain = self
+        if shift is not None:
+            self.plain = object.__new__(DecTablesDev)
+            self.plain._t, self.plain.shape, self.plain.plain = self._t, self.shape, self.plain
+            self.plain.c = L.DecTables(*[self._t[k].data_ptr() for k in TABLE_ORDER])
+            # the remap rectangle of a window is known on the host: the tables are monotone
+            self.hr_y, self.hr_x = tab["hr_y"], tab["hr_x"]
+
+    def remap_rect(self, rect):
+        """The rectangle (y0, x0, hh, ww) of HR pixels whose HRfeat the flow stage of a shifted query reads for the
+        window ``rect``: [hr_y[y0], hr_y[y0 + hh - 1]] x [hr_x[x0], hr_x[x0 + ww - 1]]."""
+        return remap_rect(self.hr_y, self.hr_x, rect)
+
+
+def remap_rect(hr_y, hr_x, rect):
+    """``DecTablesDev.remap_rect`` from the (monotone) host tables hr_y / hr_x of coords.dec_tables(shift=)."""
+    y0, x0, hh, ww = rect
+    ry0, ry1, rx0, rx1 = int(hr_y[y0]), int(hr_y[y0 + hh - 1]), int(hr_x[x0]), int(hr_x[x0 + ww - 1])
+    return ry0, rx0, ry1 - ry0 + 1, rx1 - rx0 + 1
+
+
+ENSEMBLE_SHIFTS = [(vx, vy) for vx in (-1, 1) for vy in (-1, 1)]   # the reference's order (:1006-1007)
+# The order the four decodes are blended in place: stif_dec_blend4, as built, rounds decode 1's product and fuses
+# the other three (stif.h stif_dec_stage2_blend_win), so this order gives decoding_localensemble's bits
+ENSEMBLE_BLEND_ORDER = (1, 0, 2, 3)
+
+
+def dec_blend(k, tables4, accumulate=True) -> L.DecBlend:
+    """The stif_dec_blend of decode ``k`` given the four shifted DecTablesDev in ENSEMBLE_SHIFTS order;
+    accumulate=False for the first decode blended into an output (it stores, the others add)."""
+    if len(tables4) != 4:
+        raise ValueError("dec_blend: the tables of the four shifted queries")
+    b = L.DecBlend()
+    b.k, b.accumulate = int(k), int(bool(accumulate))
+    for j, tb in enumerate(tables4):
+        b.rel_y[j], b.rel_x[j] = tb._t["rel_y"].data_ptr(), tb._t["rel_x"].data_ptr()
+    return b
 
 
 class DecImageDev:
@@ -421,6 +459,20 @@ def dec_stage1(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, image: "DecImag
             _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream(), *tail)
 
 
+def dec_flow_win(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, flags=0, status=None, window: L.DecWindow = None):
+    """The windowed flow-only stage of a shifted query (``tables`` with the remap): flow [n, hh, ww, 4] over the
+    window, its HRfeat operand read at (hr_y, hr_x) from ``hrfeat`` over the window's F rectangle, which has to hold
+    the window's remap rectangle (``tables.remap_rect``); bit 2 of ``status`` reports an F that does not."""
+    n, h, w, _ = proj.shape
+    if window is None:
+        raise ValueError("dec_flow_win: a window (dec_window) is required")
+    HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
+    if flow is None:
+        raise ValueError("dec_flow_win: flow is the output")
+    _launch("stif_dec_flow_win", None, L.lib().stif_dec_flow_win, _vp(proj), _vp(mlp), C.byref(tables.c), None, _vp(t),
+            _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream(), C.byref(window))
+
+
 def dec_bounds(flow, tables: DecTablesDev, box, window: L.DecWindow):
     """box (4 int32 on the device) = ymin, ymax, xmin, xmax of every HRfeat row / column stage 2 reads for the
     window, given stage 1's flow [n, hh, ww, 4] over it."""
@@ -436,11 +488,15 @@ def dec_bounds(flow, tables: DecTablesDev, box, window: L.DecWindow):
 
 
 def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "DecImageDev" = None, flags=0,
-               status=None, window: L.DecWindow = None):
+               status=None, window: L.DecWindow = None, blend: L.DecBlend = None):
     """window (dec_window): the stage over that rectangle -- hrfeat over its F rectangle, flow [n, hh, ww, 4], and
-    out any [n, 3, hh, ww] view with unit column stride (e.g. a tile of a larger [n, 3, HH, WW] tensor)."""
+    out any [n, 3, hh, ww] view with unit column stride (e.g. a tile of a larger [n, 3, HH, WW] tensor).
+    blend (dec_blend; needs a window, no image): the local ensemble's epilogue -- w_k rgb is stored, or added to
+    what ``out`` holds (blend.accumulate)."""
     n, h, w, _ = proj.shape
     trace = None
+    if blend is not None and (window is None or image is not None):
+        raise ValueError("dec_stage2: the blending epilogue is the windowed stage's, without a high-resolution image")
     if window is not None:
         HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
         if tuple(out.shape) != (n, 3, window.hh, window.ww) or (window.ww > 1 and out.stride(3) != 1):
@@ -448,6 +504,8 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
         win = L.DecWindow.from_buffer_copy(window)
         win.out_item, win.out_plane, win.out_pitch = out.stride(0), out.stride(1), out.stride(2)
         what, fn, tail = "stif_dec_stage2_win", L.lib().stif_dec_stage2_win, (C.byref(win),)
+        if blend is not None:
+            what, fn, tail = "stif_dec_stage2_blend_win", L.lib().stif_dec_stage2_blend_win, (C.byref(blend), C.byref(win))
     else:
         HH, WW = hrfeat.shape[1:3]
         what, fn, tail = "stif_dec_stage2", L.lib().stif_dec_stage2_ex, ()

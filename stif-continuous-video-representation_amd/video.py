@@ -56,14 +56,17 @@ def single_forward(model, imgs_in: torch.Tensor, times=None):
         return model(x, [torch.tensor([t])[None] for t in ts])
 
 
-def run_sequence(model, frames: torch.Tensor, times=None, scale=None, window=None):
+def run_sequence(model, frames: torch.Tensor, times=None, scale=None, window=None, ensemble=False):
     """frames [F,3,h,w] -> list over the F-1 pairs of lists over times of [3,HH,WW]; window=(y0, x0, hh, ww):
-    only that rectangle of every output frame, [3,hh,ww] (LunaTokis.decoding's window)."""
+    only that rectangle of every output frame, [3,hh,ww] (LunaTokis.decoding's window); ensemble: every frame
+    decoded with the local ensemble (LunaTokis.decoding's ensemble)."""
     with torch.no_grad():
         fr = pad_to_4(frames)
         model.gen_feat_window(fr)
         ts = HARNESS_TIMES if times is None else times
         kw = {} if window is None else {"window": window}
+        if ensemble:
+            kw["ensemble"] = True
         preds = model.decoding([torch.tensor([t])[None] for t in ts], scale, **kw)
     return [[p[i] for p in preds] for i in range(frames.shape[0] - 1)]
 
@@ -184,7 +187,7 @@ def _gt_float_planes(g: torch.Tensor, device) -> torch.Tensor:
 
 
 def evaluate_sequence(model, frames: torch.Tensor, gt, times=None, scale=None, channels: str = "y",
-                      metric: str = "quantised"):
+                      metric: str = "quantised", ensemble=False):
     """run_sequence + the reference's scoring loop (myutils.py:1155-1174) on the device.  gt[pair][time] is the
     ground truth of that output frame, uint8 BGR [H, W, 3] (numpy or torch, as cv2.imread), or None to skip it.
     When pad_to_4 padded the input the outputs are larger than the ground truth: the top-left H x W crop of the
@@ -192,12 +195,13 @@ def evaluate_sequence(model, frames: torch.Tensor, gt, times=None, scale=None, c
     myutils.eval_metrics instead (metrics.eval_metrics: calc_psnr and ssim_matlab on the unquantised floats;
     `channels` does not apply); there a ground truth may also be a float RGB [3, H, W] tensor, and must be at
     least 11 x 11.  Returns {"psnr", "ssim": lists over pairs of lists over times (None where skipped),
-    "avg_psnr", "avg_ssim": means over the scored frames (the reference's "AVG PSNR / AVG SSIM"), "count"}."""
+    "avg_psnr", "avg_ssim": means over the scored frames (the reference's "AVG PSNR / AVG SSIM"), "count"}.
+    ensemble: the frames scored are the local ensemble's (run_sequence)."""
     from . import metrics as M
     if metric not in ("quantised", "float"):
         raise ValueError('metric must be "quantised" or "float"')
     fl = metric == "float"
-    outs = run_sequence(model, frames, times, scale)
+    outs = run_sequence(model, frames, times, scale, ensemble=ensemble)
     flags = M.mode_flags(channels, True)
     where, sums = [], []
     for i, row in enumerate(outs):
@@ -232,11 +236,11 @@ def _frame_key(name: str):
 
 
 def evaluate_folder(model, lr_dir: str, gt_dir: str, times=None, scale=None, channels: str = "y",
-                    metric: str = "quantised"):
+                    metric: str = "quantised", ensemble=False):
     """evaluate_sequence for frames on disk: lr_dir holds the low-resolution input frames, gt_dir the ground
     truth of the output frames in output order (pair-major, then time: the numbering run_folder writes under
     HR/); output frames beyond the last file in gt_dir are not scored.  Files are read with PIL and flipped to
-    BGR as run_folder does; numeric names sort by value.  `metric` as in evaluate_sequence.  Prints the two
+    BGR as run_folder does; numeric names sort by value.  `metric` and `ensemble` as in evaluate_sequence.  Prints the two
     averages in the reference's format."""
     from PIL import Image
 
@@ -249,7 +253,7 @@ def evaluate_folder(model, lr_dir: str, gt_dir: str, times=None, scale=None, cha
     nt = len(HARNESS_TIMES if times is None else times)
     gts = [read(gt_dir, nm) for nm in sorted(os.listdir(gt_dir), key=_frame_key)]
     gt = [[gts[i * nt + k] if i * nt + k < len(gts) else None for k in range(nt)] for i in range(len(lr) - 1)]
-    res = evaluate_sequence(model, frames.contiguous(), gt, times, scale, channels, metric)
+    res = evaluate_sequence(model, frames.contiguous(), gt, times, scale, channels, metric, ensemble)
     print("AVG PSNR: {:.4f}, AVG SSIM: {:.4f}".format(res["avg_psnr"], res["avg_ssim"]))
     return res
 
@@ -306,12 +310,15 @@ def scene_scores(sad, h, w, prev=None):
     return scores, prev
 
 
-def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw, scene_threshold=None, hold_pairs=(), cuts=None):
+def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw, scene_threshold=None, hold_pairs=(), cuts=None,
+                   ensemble=False):
     """render_stream's core.  ``chunks`` yields device tensors [k, 3, h_n, w_n] of new input frames, already
     zero-padded to a multiple of 4 (k >= 1; the pairs of a chunk are its frames plus the previous chunk's last).
     Gradients are switched off around the model calls only, never across a yield.  scene_threshold / hold_pairs /
     cuts: render_stream's; a cut pair is never fused, breaks the run of pairs on either side, and its outputs
-    repeat the model's rendering of one of its two frames."""
+    repeat the model's rendering of one of its two frames.  ensemble: every decode, the held frames' included, is
+    the local ensemble's (LunaTokis.decoding_pairs)."""
+    ekw = {"ensemble": True} if ensemble else {}
     hn, wn = _padded_size(h, w)
     OH, OW = out_hw
     grid = (int(round(OH * hn / h)), int(round(OW * wn / w)))      # virtual grid of the padded frame
@@ -335,7 +342,7 @@ def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw, scene_threshold
         with torch.no_grad():
             model.gen_feat_window(torch.cat([x[i:i + 1], x[i:i + 1]]),
                                   frame_feats=tuple(torch.cat([f[i:i + 1], f[i:i + 1]]) for f in feats))
-            o = model.decoding_pairs([0], [torch.zeros(1, dtype=torch.float32)], grid)[0][0]
+            o = model.decoding_pairs([0], [torch.zeros(1, dtype=torch.float32)], grid, **ekw)[0][0]
         return o[:, :OH, :OW]
 
     for x in chunks:
@@ -385,7 +392,7 @@ def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw, scene_threshold
             while b < P and per[b] and not cut[b]:
                 b += 1
             B = fuse(x, feats, a, b)
-            yield from _decode_run(model, per[a:b], grid, OH, OW)
+            yield from _decode_run(model, per[a:b], grid, OH, OW, ekw)
             a = b
         base += P
         if not per[-1] and not last_cut and pending == (base, 0):
@@ -401,13 +408,14 @@ def _render_chunks(model, chunks, h, w, fps_in, fps_out, out_hw, scene_threshold
         yield closing if closing is not None else held(last, last_feats, 0)
     elif pending == (base, 0):
         # the stream ended on an output instant: the last pair (the last item of the model's latent) at t = 1
-        yield from _decode_run(model, [[]] * (B - 1) + [[1]], grid, OH, OW)
+        yield from _decode_run(model, [[]] * (B - 1) + [[1]], grid, OH, OW, ekw)
 
 
-def _decode_run(model, per, grid, OH, OW):
+def _decode_run(model, per, grid, OH, OW, ekw={}):
     """Decode the model's current latent (one item per entry of ``per``) at each item's own query times and yield
     the top-left OH x OW crops in display order.  Items are grouped by their number of queries, one decoding call
-    per group with per-item times, so no frame is decoded that is not yielded."""
+    per group with per-item times, so no frame is decoded that is not yielded.  ekw: further keywords of
+    decoding_pairs (the local ensemble)."""
     groups = {}
     for i, ts in enumerate(per):
         if ts:
@@ -416,7 +424,7 @@ def _decode_run(model, per, grid, OH, OW):
     for cnt, idx in groups.items():
         times = [torch.tensor([float(per[i][k]) for i in idx], dtype=torch.float32) for k in range(cnt)]
         with torch.no_grad():
-            preds = model.decoding_pairs(idx, times, grid)
+            preds = model.decoding_pairs(idx, times, grid, **ekw)
         for j, i in enumerate(idx):
             outs[i] = [p[j] for p in preds]
         del preds
@@ -436,7 +444,7 @@ def _out_size(h, w, scale, out_size):
 
 
 def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_pairs=8, scene_threshold=None,
-                  hold_pairs=(), cuts=None):
+                  hold_pairs=(), cuts=None, ensemble=False):
     """Render a video of any length at any output frame rate in bounded memory.  ``frames``: an iterable of RGB
     float [3, h, w] frames in [0, 1] (host or device) at ``fps_in``; yields device float [3, OH, OW] frames
     (unclamped) at ``fps_out`` in display order, (OH, OW) = ``out_size`` or (h, w) * ``scale``.  The output frames
@@ -449,6 +457,9 @@ def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_
     round(OW w_n / w)), and the yielded frame its top-left OH x OW crop -- for h, w multiples of 4 exactly
     ``decoding(scale=(OH, OW))``.  Alive at a time: at most chunk_pairs + 1 input frames, one chunk's features and
     latents, and the decoded frames of one chunk that have not been yielded yet.
+
+    ``ensemble``: every frame, held frames at scene cuts included, is decoded with the local ensemble
+    (``LunaTokis.decoding(ensemble=True)``: no seams at LR pixel borders, about four times the decode).
 
     Scene cuts (off by default).  ``scene_threshold``: a float switches the detector on -- one ``ops.scene_sad`` per
     chunk over its frames (the carried last frame first) and one read-back of its pair sums; pair p is a cut when
@@ -492,18 +503,18 @@ def render_stream(model, frames, fps_in, fps_out, scale=4, out_size=None, chunk_
             yield x
 
     return _render_chunks(model, chunks(), h, w, fps_in, fps_out, _out_size(h, w, scale, out_size), scene_threshold,
-                          hold_pairs, cuts)
+                          hold_pairs, cuts, ensemble)
 
 
 def render_y4m(model, src, dst, fps_out=None, multiplier=8, scale=4, chunk_pairs=8, matrix="auto", out_size=None,
-               scene_threshold=None, hold_pairs=(), cuts=None):
+               scene_threshold=None, hold_pairs=(), cuts=None, ensemble=False):
     """Render a YUV4MPEG2 stream to another: reader -> upload -> yuv_to_rgb -> render_stream -> rgb_to_yuv ->
     download -> writer.  src / dst: paths or binary file objects (pipes work: nothing seeks).  The output runs at
     ``fps_out`` (default: ``multiplier`` x the input rate) and (h, w) * ``scale`` (or ``out_size`` = (OH, OW)); it
     keeps the input's chroma layout, depth, range, matrix ("auto": BT.709 for an input luma >= 1280 wide or >= 720
     high, else BT.601) and X tags, so colours survive the round trip.  Uploads and downloads go through pinned host
     buffers, one chunk of input frames / one chunk's worth of output frames at a time.  scene_threshold / hold_pairs / cuts:
-    render_stream's scene-cut arguments (the detector scores the converted RGB frames).  Returns (frames read,
+    render_stream's scene-cut arguments (the detector scores the converted RGB frames); ensemble: render_stream's.  Returns (frames read,
     frames written)."""
     from fractions import Fraction
 
@@ -559,7 +570,7 @@ def render_y4m(model, src, dst, fps_out=None, multiplier=8, scale=4, chunk_pairs
 
             k = 0
             for frame in _render_chunks(model, chunks(), h, w, fps_in, fps_o, (OH, OW), scene_threshold, hold_pairs,
-                                        cuts):
+                                        cuts, ensemble):
                 ops.rgb_to_yuv(frame[None], fmt_out, out=ybuf[k:k + 1])   # the crop, converted in place
                 del frame
                 k += 1

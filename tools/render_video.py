@@ -57,6 +57,8 @@ def main(argv=None):
     ap.add_argument("--scene-threshold", type=float, help="detect scene cuts: hold a frame where the cut score of a "
                     "pair (video.scene_scores, in [0, 1]) exceeds this; off when not given")
     ap.add_argument("--hold-pairs", default="", help="comma-separated pair indices to treat as cuts, e.g. 12,340")
+    ap.add_argument("--ensemble", action="store_true", help="decode every frame with the local ensemble (four "
+                    "shifted decodes blended per pixel: no seams at LR pixel borders, about four times the decode)")
     opt = ap.parse_args(argv)
     stif = stif_pkg.load()
     model = build_model(stif, opt)
@@ -71,7 +73,7 @@ def main(argv=None):
     nin, nout = stif.video.render_y4m(model, src, dst, fps_out=opt.fps_out, multiplier=opt.multiplier,
                                       scale=opt.scale, chunk_pairs=opt.chunk_pairs, matrix=opt.matrix,
                                       out_size=out_size, scene_threshold=opt.scene_threshold, hold_pairs=hold,
-                                      cuts=cuts)
+                                      cuts=cuts, ensemble=opt.ensemble)
     print(f"{nin} frames in, {nout} frames out", file=sys.stderr)
     if opt.scene_threshold is not None or hold:
         print(f"{len(cuts)} cut pairs: {','.join(map(str, cuts))}", file=sys.stderr)
