@@ -420,6 +420,33 @@ int stif_dec_stage2_blend_win(const float* proj, const float* mlp, const float* 
                               int h, int w, int HH, int WW, int flags, int* status, void* stream,
                               const stif_dec_blend* blend, const stif_dec_window* win);
 
+/* ---- time fields: every output pixel decoded at its own query time (LunaTokis.decoding with times[c] of shape
+ * [bs, HH*WW], Sakuya_arch_test.py:364-459) ---- */
+
+/* The query time of pixel (gy, gx) of the virtual HH x WW grid of item i is t[i * item + gy * row + gx * col]:
+ * strides in elements, each >= 0, 0 broadcasts.  {t, 1, 0, 0} is the per-item vector the other entry points take;
+ * {t, HH * WW, WW, 1} a dense [n][HH][WW] field; {t, 0, 1, 0} one time per row for every item.  A window does not
+ * move the field: its pixel (py, px) reads the field at (y0 + py, x0 + px).  The values are not validated (the
+ * reference imposes no range). */
+typedef struct { const float* t; long long item, row, col; } stif_dec_time;
+
+/* stif_dec_stage1_ex (win = NULL: the whole grid; flow must then be given or NULL as below) or stif_dec_stage1_win
+ * (win given) with a time field: HRfeat of pixel q and its flow are computed with t(q).  flow = NULL: feat_imnet
+ * only, e.g. over an F rectangle larger than the window -- the field is then read at F's pixels.  A pixel whose
+ * field value is v gets bit for bit what the per-item call with t = v gives it.  STIF_E_INVALID, each with its
+ * reason in stif_last_error: img != NULL, tables with hr_y / hr_x, a null t (the struct or its pointer), a negative
+ * stride. */
+int stif_dec_stage1_tf(const float* proj, const float* mlp, const stif_dec_tables* tab, const stif_dec_image* img,
+                       const stif_dec_time* t, float* hrfeat, float* flow, int n, int h, int w, int HH, int WW,
+                       int flags, int* status, void* stream, const stif_dec_window* win);
+/* stif_dec_stage2_ex (win = NULL) or stif_dec_stage2_win (win given) with a time field: pixel p gathers the HRfeat
+ * rows at its warped grids -- each computed with its own pixel's time by stage 1 -- and adds w_t * t(p), as the
+ * reference does when it grid-samples an HRfeat map built with a per-pixel time.  Status bits and the invalid
+ * arguments as above. */
+int stif_dec_stage2_tf(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                       const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t, float* out, int n,
+                       int h, int w, int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win);
+
 /* ---- evaluation: PSNR / SSIM of decoded frames against ground truth (myutils.py:1151-1174, util.py:105-174) ---- */
 
 /* stif_metric_args.flags */

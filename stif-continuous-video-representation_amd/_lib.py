@@ -77,6 +77,12 @@ class DecBlend(C.Structure):
     _fields_ = [("k", C.c_int), ("accumulate", C.c_int), ("rel_y", _P * 4), ("rel_x", _P * 4)]
 
 
+class DecTimeField(C.Structure):
+    """stif_dec_time: the query time of pixel (gy, gx) of item i is t[i * item + gy * row + gx * col] (strides in
+    elements, >= 0, 0 broadcasts)."""
+    _fields_ = [("t", _P), ("item", C.c_longlong), ("row", C.c_longlong), ("col", C.c_longlong)]
+
+
 METRIC_Y, METRIC_SSIM, METRIC_FLOAT = 1, 2, 4   # stif_metric_args.flags (stif.h STIF_METRIC_*)
 FSSIM_VOLUME, FSSIM_PLANAR = 0, 1               # stif_metric_float's mode (stif.h STIF_FSSIM_*)
 
@@ -140,6 +146,10 @@ EXPORTS = {
                           + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
     "stif_dec_stage2_blend_win": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecImage), _P, _P]
                                   + [C.c_int] * 6 + [_P, _P, C.POINTER(DecBlend), C.POINTER(DecWindow)]),
+    "stif_dec_stage1_tf": (C.c_int, [_P, _P, C.POINTER(DecTables), C.POINTER(DecImage), C.POINTER(DecTimeField), _P, _P]
+                           + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
+    "stif_dec_stage2_tf": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecImage),
+                                     C.POINTER(DecTimeField), _P] + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
     "stif_dec_blend4": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "stif_upsample_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "stif_resize_frames": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int,

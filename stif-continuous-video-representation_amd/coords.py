@@ -101,6 +101,37 @@ def ensemble_weights(h: int, w: int, HH: int, WW: int) -> list:
     return [(areas[3 - k] / tot).astype(F32) for k in range(4)]
 
 
+def classify_time_query(shape, B: int, HH: int, WW: int) -> tuple:
+    """What an entry of ``times`` of this shape means for a latent of ``B`` items decoded at HH x WW:
+    ``("vector", None)`` -- 1 or B elements, of any shape: one time for all items or one per item; or
+    ``("field", (b, hh, ww))`` -- a time per output pixel: the tensor, reshaped to (b, hh, ww) (each 1 or the full
+    size), broadcasts to [B, HH, WW].  Fields are [HH, WW], [B, HH, WW], [B, 1, HH, WW], any shape of up to three
+    dims that broadcasts to [B, HH, WW] ([HH, 1], [B, HH, 1], [WW], ...) and the reference's own [B, HH * WW] (or
+    [1, HH * WW]).  Anything else is a ValueError."""
+    shape = tuple(int(s) for s in shape)
+    numel = int(np.prod(shape, dtype=np.int64)) if shape else 1
+    if numel in (1, B):
+        return "vector", None
+    full = (B, HH, WW)
+    if len(shape) == 2 and shape[0] in (1, B) and shape[1] == HH * WW:   # times[c] of Sakuya_arch_test.py:397
+        return "field", (shape[0], HH, WW)
+    s3 = shape
+    if len(s3) == 4 and s3[1] == 1:
+        s3 = (s3[0],) + s3[2:]
+    if len(s3) <= 3:
+        s3 = (1,) * (3 - len(s3)) + s3
+        if all(s in (1, f) for s, f in zip(s3, full)):
+            return "field", s3
+    raise ValueError(f"a time query of shape {shape} is neither 1 or {B} values nor a field that broadcasts to "
+                     f"[{B}, {HH}, {WW}]")
+
+
+def row_time_field(HH: int, t: float, skew: float) -> np.ndarray:
+    """A rolling-shutter style time field, [HH, 1] fp32: row y is decoded at t + skew * (y / (HH - 1) - 0.5)."""
+    y = np.arange(HH, dtype=np.float64) / max(HH - 1, 1)
+    return (float(t) + float(skew) * (y - 0.5)).astype(F32).reshape(HH, 1)
+
+
 def check_window(window, HH: int, WW: int) -> tuple:
     """A window ``(y0, x0, hh, ww)`` of the virtual HH x WW grid as four ints; ValueError unless it is a
     non-empty rectangle inside the grid."""

@@ -274,6 +274,23 @@ STIF_DEV Pixel pixel_of(int wv, int lane, int n, int HH, int WW, const stif_dec_
   return o;
 }
 
+// The query time of a pixel.  TF false: one value per item, tq[item] (the scalar kernels).  TF true (time field):
+// every pixel its own, t[item * item + gy * row + gx * col] at row gy / column gx of the virtual grid -- strides in
+// elements, 0 broadcasts.  A tail lane redoes the last pixel (pixel_of), so its read is one a valid lane makes too.
+template <bool TF>
+struct TimeArg {
+  typedef const float* __restrict__ type;
+};
+template <>
+struct TimeArg<true> {
+  typedef stif_dec_time type;
+};
+template <bool TF>
+STIF_DEV float time_at(const typename TimeArg<TF>::type& tq, int item, int gy, int gx) {
+  if constexpr (TF) return tq.t[item * tq.item + gy * tq.row + gx * tq.col];
+  else return tq[item];
+}
+
 // The local ensemble's blend weight of decode bl.k at row gy / column gx of the virtual grid, as
 // coords.ensemble_weights computes it in numpy's fp32: area_j = |rel_y_j rel_x_j| + 1e-9 of the four shifted
 // queries, tot = ((a_0 + a_1) + a_2) + a_3, decode k weighted by the diagonally opposite area (3 - k) over tot.
@@ -424,13 +441,15 @@ constexpr int S1 = OCC1<MODE, HRIMG> == 4 ? 4 : OCC1<MODE, HRIMG> == 3 ? 6 : SEG
 // place in win's F rectangle; the whole-grid instantiations (WIN false) never read win.  WIN and MODE 2: the
 // remapped HRfeat row is read from the F layout, its index clamped into F and a clamp reported (bit 2 of *status,
 // which no other instantiation touches), as bilin_hr does with bit 1.
-template <int MODE, bool HRIMG, int F16, bool WIN>
+// TF: the time-field variant (time_at), MODE 0 / 1 without the HR image only; everything else is the scalar twin's.
+template <int MODE, bool HRIMG, int F16, bool WIN, bool TF = false>
 __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<MODE, HRIMG>))) void k_dec1(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      stif_dec_tables tb, stif_dec_image im,
-                                                     const float* __restrict__ tq, float* __restrict__ hrfeat,
+                                                     typename TimeArg<TF>::type tq, float* __restrict__ hrfeat,
                                                      float* __restrict__ flow, int n, int h, int w, int HH,
                                                      int WW, stif_dec_window win, int* status) {
   static_assert(!(WIN && MODE == 2 && HRIMG), "the windowed flow-only stage takes no high-resolution image");
+  static_assert(!TF || (MODE != 2 && !HRIMG), "a time field has no local-ensemble and no HR-image form");
   // two segment buffers of SEG1 tiles + the flow's last layer (plain [4][256], resident)
   constexpr bool OCC3 = S1<MODE, HRIMG> != SEG1;             // 3 or 4 workgroups per CU
   constexpr bool OCC4 = OCC1<MODE, HRIMG> == 4;
@@ -454,7 +473,13 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
   const int item = pix.item;
   // row / column of the virtual grid
   const int py = WIN ? win.y0 + pix.ly : pix.ly, px = WIN ? win.x0 + pix.lx : pix.lx;
-  const float t = tq[item];
+  // the scalar kernels load the item's time once; a time-field kernel reads its pixel's time where it is used (feat
+  // layer 0, flow layer 0) and does not keep it in a register across the feat stage
+  const float t = TF ? 0.f : time_at<TF>(tq, item, py, px);
+  auto time = [&]() {
+    if constexpr (TF) return time_at<TF>(tq, item, py, px);
+    else return t;
+  };
   const float* P = proj + (size_t)item * h * w * PROJ_C;
 
   f32x16 hr[2] = {f32x16{0}, f32x16{0}};
@@ -463,7 +488,7 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
   // ---- feat_imnet layer 0: z = P1[nearest] + w_rel . rel + w_t * t  (bias folded into P1)
   f32x16 x0[2];
   {
-    const float ry = tb.rel_y[py], rx = tb.rel_x[px];
+    const float ry = tb.rel_y[py], rx = tb.rel_x[px], t = time();
     const float* p1 = P + ((size_t)tb.near_y[py] * w + tb.near_x[px]) * PROJ_C;
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot)
@@ -563,6 +588,7 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
   f32x16 z[2];
   {
     const Bilin b = bilin_tab(tb, py, px, w);
+    const float t = time();
     // loads in flight sized to the register budget: 8 corner loads (32 VGPRs, four memory latencies) at 128
     // registers, 16 (64 VGPRs, two latencies) at 168, all 32 (128 VGPRs, one latency) at 256
     if (OCC4) gather64<2>(z, P, PROJ_C, 64, b, hf);
@@ -652,13 +678,14 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
 // WIN: the pixels are those of win's query rectangle, flow is read at the
 // pixel's index in the rectangle, the linspace base at its row / column of the virtual grid, HRfeat in win's F
 // rectangle (bilin_hr) and the RGB goes through win's output addressing.
-template <bool HRIMG, int F16, bool WIN, bool BLEND = false>
+template <bool HRIMG, int F16, bool WIN, bool BLEND = false, bool TF = false>   // TF: as k_dec1's
 __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DEC2_WPE))) void k_dec2(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      const float* __restrict__ hrfeat, const float* __restrict__ flow,
                                                      stif_dec_tables tb, stif_dec_image im,
-                                                     const float* __restrict__ tq, float* __restrict__ out, int n,
+                                                     typename TimeArg<TF>::type tq, float* __restrict__ out, int n,
                                                      int h, int w, int HH, int WW, int* status, stif_dec_window win,
                                                      stif_dec_blend bl) {
+  static_assert(!TF || (!HRIMG && !BLEND), "a time field has no HR-image and no blending form");
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEG * T];
   const int lane = threadIdx.x & 63, hf = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
@@ -671,7 +698,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   const Pixel pix = pixel_of<DEC2_NW, 32, WIN>(wv, lane, n, HH, WW, win);
   const long long pc = pix.pc;
   const int item = pix.item, py = pix.ly, px = pix.lx;   // row / column in the rectangle
-  const float t = tq[item];
+  const float t = time_at<TF>(tq, item, WIN ? win.y0 + py : py, WIN ? win.x0 + px : px);
   const float* P = proj + (size_t)item * h * w * PROJ_C;
   const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
 
@@ -865,11 +892,12 @@ STIF_DEV void gather_q(R32* dst, const float* __restrict__ base, int stride, int
   }
 }
 
-template <bool WIN, bool BLEND = false>   // WIN, BLEND: as k_dec2's
+template <bool WIN, bool BLEND = false, bool TF = false>   // WIN, BLEND, TF: as k_dec2's
 __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec2q(
     const float* __restrict__ proj, const float* __restrict__ mlp, const float* __restrict__ hrfeat,
-    const float* __restrict__ flow, stif_dec_tables tb, const float* __restrict__ tq, float* __restrict__ out, int n,
+    const float* __restrict__ flow, stif_dec_tables tb, typename TimeArg<TF>::type tq, float* __restrict__ out, int n,
     int h, int w, int HH, int WW, int* status, stif_dec_window win, stif_dec_blend bl) {
+  static_assert(!TF || !BLEND, "a time field has no blending form");
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEGQ * T];
   const int lane = threadIdx.x & 63, q = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -892,7 +920,7 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
   const Pixel pix = pixel_of<NW, 16, WIN>(wv, lane, n, HH, WW, win);
   const long long pc = pix.pc;
   const int item = pix.item, py = pix.ly, px = pix.lx;   // row / column in the rectangle
-  const float t = tq[item];
+  const float t = time_at<TF>(tq, item, WIN ? win.y0 + py : py, WIN ? win.x0 + px : px);
   const float* P = proj + (size_t)item * h * w * PROJ_C;
   const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
 
@@ -1273,7 +1301,85 @@ int dec_stage2(const char* me, const float* proj, const float* mlp, const float*
   return stif_check_launch(me);
 }
 
+// ---- time fields: the stages with a query time per pixel (stif_dec_time) instead of one per item
+// the reason a time-field call is invalid before its generic argument check, or null
+const char* time_field_invalid(const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t) {
+  if (img) return "a high-resolution image (img) has no time-field form: pass NULL";
+  if (tab && (tab->hr_y || tab->hr_x)) return "tables with hr_y / hr_x (local ensemble) have no time-field form";
+  if (!t || !t->t) return "null time field (t)";
+  if (t->item < 0 || t->row < 0 || t->col < 0) return "negative time-field stride";
+  return nullptr;
+}
+
+// the window of a time-field call resolved into wn (win null: the whole grid, wn untouched), or the reason it is invalid
+const char* tf_window(const stif_dec_window* win, int HH, int WW, stif_dec_window* wn) {
+  if (win) return window_resolve(win, HH, WW, wn);
+  return HH < 2 || WW < 2 || (long long)HH * WW > INT_MAX ? "bad virtual grid size" : nullptr;
+}
+
+int dec_stage1_tf(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
+                  const stif_dec_image* img, const stif_dec_time* t, float* hrfeat, float* flow, int n, int h, int w,
+                  int HH, int WW, int flags, void* stream, const stif_dec_window* win) {
+  if (const char* why = time_field_invalid(tab, img, t)) return window_fail(me, why);
+  if (!proj || !mlp || !tables_ok(tab) || !hrfeat || n < 1 || h < 1 || w < 1)
+    return window_fail(me, "bad arguments (null pointer or empty shape)");
+  stif_dec_window wn{};
+  if (const char* why = tf_window(win, HH, WW, &wn)) return window_fail(me, why);
+  if (win && !f_holds_query(wn)) return window_fail(me, "the F rectangle does not contain the query rectangle");
+  const long long total = (long long)n * (win ? wn.hh : HH) * (win ? wn.ww : WW);
+  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
+  with_bool(flags & STIF_CONV_F16X3, [&](auto f16x3) {
+    with_bool(win != nullptr, [&](auto windowed) {
+      with_bool(flow != nullptr, [&](auto fused) {   // a null flow is the feat-only pass
+        hipLaunchKernelGGL((k_dec1<decltype(fused)::value ? 0 : 1, false, decltype(f16x3)::value,
+                                   decltype(windowed)::value, true>),
+                           grid, dim3(NW1 * 64), 0, (hipStream_t)stream, proj, mlp, *tab, stif_dec_image{}, *t, hrfeat,
+                           flow, n, h, w, HH, WW, wn, (int*)nullptr);
+      });
+    });
+  });
+  return stif_check_launch(me);
+}
+
+int dec_stage2_tf(const char* me, const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                  const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t, float* out, int n,
+                  int h, int w, int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win) {
+  if (const char* why = time_field_invalid(tab, img, t)) return window_fail(me, why);
+  if (!proj || !mlp || !hrfeat || !flow || !tables_ok(tab) || !out || n < 1 || h < 1 || w < 1)
+    return window_fail(me, "bad arguments (null pointer or empty shape)");
+  stif_dec_window wn{};
+  if (const char* why = tf_window(win, HH, WW, &wn)) return window_fail(me, why);
+  const long long total = (long long)n * (win ? wn.hh : HH) * (win ? wn.ww : WW);
+  auto grid = [&](int wg_pixels) { return dim3((unsigned)((total + wg_pixels - 1) / wg_pixels)); };
+  hipStream_t st = (hipStream_t)stream;
+  with_bool(win != nullptr, [&](auto windowed) {
+    constexpr bool WIN = decltype(windowed)::value;
+    if (flags & STIF_CONV_F16X3)
+      hipLaunchKernelGGL((k_dec2q<WIN, false, true>), grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat,
+                         flow, *tab, *t, out, n, h, w, HH, WW, status, wn, stif_dec_blend{});
+    else
+      hipLaunchKernelGGL((k_dec2<false, 0, WIN, false, true>), grid(DEC2_NW * 32), dim3(DEC2_NW * 64), 0, st, proj, mlp,
+                         hrfeat, flow, *tab, stif_dec_image{}, *t, out, n, h, w, HH, WW, status, wn, stif_dec_blend{});
+  });
+  return stif_check_launch(me);
+}
+
 }  // namespace
+
+extern "C" int stif_dec_stage1_tf(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                  const stif_dec_image* img, const stif_dec_time* t, float* hrfeat, float* flow, int n,
+                                  int h, int w, int HH, int WW, int flags, int* /*status*/, void* stream,
+                                  const stif_dec_window* win) {
+  return dec_stage1_tf("stif_dec_stage1_tf", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, stream, win);
+}
+
+extern "C" int stif_dec_stage2_tf(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                  const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t,
+                                  float* out, int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                  const stif_dec_window* win) {
+  return dec_stage2_tf("stif_dec_stage2_tf", proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, flags, status,
+                       stream, win);
+}
 
 // status: stage 2 checks both stage-1 outputs it reads (flow, and HRfeat through the RGB; stif.h), so stage 1 has
 // nothing to report

@@ -30,7 +30,7 @@ from torch import nn
 from . import _lib as L
 from . import ops
 from . import weights as W
-from .coords import check_window, ensemble_weights, tile_windows, window_from_center
+from .coords import check_window, classify_time_query, ensemble_weights, tile_windows, window_from_center
 from .packing import pack_model
 
 _CONST_LOCK = threading.Lock()   # _const's dict is shared by DataParallel replicas (replicate() threads)
@@ -758,6 +758,29 @@ class LunaTokis(nn.Module):
             raise ValueError("each time query must hold 1 or B values")
         return t.contiguous()
 
+    def _time_query(self, tq, B, HH, WW):
+        """An entry of ``times`` as the decoder stages take it: the [B] time vector (``_time_vec``), or, for a
+        tensor that ``coords.classify_time_query`` finds to be a field over the HH x WW grid, an ``ops.DecTime``.
+        A float32 view already on the device is used through its strides (a broadcast dim costs no memory);
+        anything else is copied to the device once."""
+        if isinstance(tq, np.ndarray):
+            tq = torch.from_numpy(tq)
+        if not isinstance(tq, torch.Tensor):
+            return self._time_vec(tq, B)
+        kind, s3 = classify_time_query(tq.shape, B, HH, WW)
+        if kind == "vector":
+            return self._time_vec(tq, B)
+        v = tq.detach().to(self.device, torch.float32)
+        try:
+            v = v.view(s3)
+        except RuntimeError:   # e.g. [B, HH * WW] rows that are no [HH, WW] view
+            v = v.reshape(s3)
+        return ops.DecTime.of(v)
+
+    @staticmethod
+    def _is_field(tq, B, HH, WW):
+        return isinstance(tq, (torch.Tensor, np.ndarray)) and classify_time_query(tq.shape, B, HH, WW)[0] == "field"
+
     def _tab(self, H, Wd, HH, WW, shift=None):
         key = (str(self.device), H, Wd, HH, WW, shift)
         if key not in self._tables:
@@ -799,6 +822,12 @@ class LunaTokis(nn.Module):
     def decoding(self, times=None, scale=None, window=None, tile=None, ensemble=False):
         """LunaTokis.decoding (:364-459): list over times of [B,3,HH,WW] (unclamped).
 
+        An entry of ``times`` holds 1 or B values, or is a time field: a tensor that broadcasts to [B, HH, WW]
+        ([HH, WW], [B, HH, WW], [B, 1, HH, WW], [HH, 1] ..., or the reference's [B, HH * WW];
+        ``coords.classify_time_query``), every output pixel then decoded at its own time -- HRfeat and flow of pixel
+        q with t(q), the RGB of pixel p from the HRfeat rows at its warped grids and t(p).  With window= / tile=
+        the field stays that of the virtual grid.  Not with ensemble=True.
+
         window=(y0, x0, hh, ww): only that rectangle of the virtual HH x WW grid, [B,3,hh,ww], bit-identical to
         the crop of the full decode and at the cost of the rectangle (``_decode_windowed``).  tile=(th, tw): the
         same output as without it, rendered by windows of at most th x tw, so the decoder scratch is bounded by
@@ -818,8 +847,11 @@ class LunaTokis(nn.Module):
             raise RuntimeError("decoding needs gen_feat first")
         _, B, H, Wd, _ = self._feat.shape
         HH, WW = _hr_size(H, Wd, scale)
+        if ensemble and any(self._is_field(tq, B, HH, WW) for tq in times):
+            raise ValueError("a time field is not supported with ensemble=True (the reference's local ensemble "
+                             "takes its times as the batch)")
         tab = self._tab(H, Wd, HH, WW)
-        tvs = [self._time_vec(tq, B) for tq in times]
+        tvs = [self._time_query(tq, B, HH, WW) for tq in times]
         if ensemble:
             return self._decode_ensemble(tvs, H, Wd, HH, WW, window, tile)
         if window is not None or tile is not None:
@@ -849,6 +881,24 @@ class LunaTokis(nn.Module):
         if pairs == list(range(B)):
             return self.decoding(times, scale, ensemble=ensemble)
         idx = torch.tensor(pairs, device=feat.device, dtype=torch.long)
+        if times is not None and len(pairs) != B:
+            # a time field over the latent's B items: its items are selected like the latent's (a field with
+            # len(pairs) items, or with none, is taken as it is -- as a vector of len(pairs) values is)
+            _, _, H, Wd, _ = feat.shape
+            HH, WW = _hr_size(H, Wd, scale)
+
+            def select(tq):
+                if not isinstance(tq, (torch.Tensor, np.ndarray)) or int(np.prod(tuple(tq.shape))) in (1, len(pairs)):
+                    return tq
+                try:
+                    kind, s3 = classify_time_query(tq.shape, B, HH, WW)
+                except ValueError:
+                    return tq   # decoding classifies it against the selected items
+                if kind != "field" or s3[0] != B:
+                    return tq
+                tq = torch.from_numpy(tq) if isinstance(tq, np.ndarray) else tq
+                return tq.detach().reshape(s3).index_select(0, idx.to(tq.device))
+            times = [select(tq) for tq in times]
         self._feat, self.inp = feat.index_select(1, idx), inp.index_select(0, idx)
         try:
             return self.decoding(times, scale, ensemble=ensemble)
@@ -882,6 +932,8 @@ class LunaTokis(nn.Module):
         _, B, H, Wd, _ = self._feat.shape
         s = 4 if scale is None else int(scale)
         HH, WW = H * s, Wd * s
+        if any(self._is_field(tq, B, HH, WW) for tq in times):
+            raise ValueError("a time field is not supported in decoding_test (high-resolution image)")
         windowed = window is not None or tile is not None
         proj = None if windowed else self._projection(lr_image=False)   # a windowed decode projects per pass
         image = ops.DecImageDev(self.inp, 4, HH, WW)
@@ -939,7 +991,7 @@ class LunaTokis(nn.Module):
         if torch.cuda.is_current_stream_capturing():
             raise L.StifError("a windowed / tiled decode reads the HRfeat bounding box back on the host: "
                               "it cannot be captured in a hipGraph")
-        B = tvs[0].shape[0] if tvs else self._feat.shape[1]
+        B = self._feat.shape[1]   # every entry of tvs holds (or, a field without item stride, serves) B items
         region = check_window((0, 0, HH, WW) if window is None else window, HH, WW)
         rects = [region] if tile is None else tile_windows(region, tile)
         ry, rx, rh, rw = region
@@ -1069,6 +1121,12 @@ class LunaTokis(nn.Module):
         size = (4 * H, 4 * Wd) if size is None else size
         return self.decoding(times, scale, window=window_from_center(center, HH, WW, size))
 
+    @staticmethod
+    def _no_fields(times, where):
+        for tq in times or ():
+            if isinstance(tq, (torch.Tensor, np.ndarray)) and int(np.prod(tuple(tq.shape))) > 1:
+                raise ValueError(f"a time field is not supported in {where}: its times are floats, decoded as the batch")
+
     def decoding_fasttest(self, times=None, scale=None):
         """LunaTokis.decoding_fasttest (:863-960): `times` is a list of floats, the latent a batch of
         one; all times come back as one batch [len(times), 3, HH, WW]."""
@@ -1079,6 +1137,7 @@ class LunaTokis(nn.Module):
             raise RuntimeError("decoding needs gen_feat first")
         if self._feat.shape[1] != 1:
             raise ValueError("decoding_fasttest batches the query times: the latent must have batch 1")
+        self._no_fields(times, "decoding_fasttest")
         tq = [torch.tensor([[float(t)]]) for t in times]
         return torch.cat(self._decoding(tq, scale), 0)
 
@@ -1093,6 +1152,7 @@ class LunaTokis(nn.Module):
             raise RuntimeError("decoding needs gen_feat first")
         if self._feat.shape[1] != 1:
             raise ValueError("decoding_localensemble batches the query times: the latent must have batch 1")
+        self._no_fields(times, "decoding_localensemble")
         proj = self._projection()
         _, H, Wd, _ = proj.shape
         HH, WW = _hr_size(H, Wd, scale)

@@ -441,12 +441,68 @@ def _win_shapes(window, tables, n, hrfeat, flow):
     return HH, WW
 
 
+class DecTime:
+    """A time field for dec_stage1 / dec_stage2 in place of the [n] time tensor: the query time of pixel (gy, gx) of
+    the virtual HH x WW grid of item i is ``t`` at element offset i * item + gy * row + gx * col from its first
+    element (stif_dec_time; strides >= 0, 0 broadcasts).  ``n``: the items the field holds (None with item = 0: any
+    number).  ``DecTime.of(v)`` takes a [b, hh, ww] fp32 device tensor or view, each dim 1 or the full size -- a dim
+    of size 1 and an expanded dim broadcast.  ``f[a:b]`` is the field of items [a, b), as ``t[a:b]`` of a vector."""
+
+    def __init__(self, t: torch.Tensor, item: int, row: int, col: int, n=None, offset: int = 0, grid=None):
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError("DecTime: expected a float32 CUDA tensor")
+        if min(item, row, col) < 0:
+            raise ValueError("DecTime: strides must be >= 0")
+        self.t, self.item, self.row, self.col, self.n, self.offset = t, int(item), int(row), int(col), n, int(offset)
+        self.grid = grid   # (hh, ww) the field spans, each 1 or the grid's size; checked against the tables' grid
+        self.c = L.DecTimeField(t.data_ptr() + 4 * self.offset, self.item, self.row, self.col)
+
+    @classmethod
+    def of(cls, v: torch.Tensor):
+        if v.dim() != 3:
+            raise ValueError(f"DecTime.of: a [b, hh, ww] tensor, got {tuple(v.shape)}")
+        st = [0 if v.shape[d] == 1 else v.stride(d) for d in range(3)]
+        return cls(v, *st, n=None if st[0] == 0 else v.shape[0], grid=tuple(v.shape[1:]))
+
+    @property
+    def shape(self):
+        return (self.n,)
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice) or s.step not in (None, 1):
+            raise TypeError("DecTime: only item slices [a:b]")
+        if self.n is None:
+            return self
+        a, b, _ = s.indices(self.n)
+        return DecTime(self.t, self.item, self.row, self.col, max(0, b - a), self.offset + a * self.item, self.grid)
+
+
+def _time_field_call(t, n, image, tables, what):
+    if image is not None or "hr_y" in tables._t and tables.c.hr_y:
+        raise ValueError(f"{what}: a time field has no high-resolution-image and no local-ensemble form")
+    if t.n is not None and t.n != n:
+        raise ValueError(f"{what}: the time field holds {t.n} items, the call has {n}")
+    HH, WW = tables.shape[2:]
+    if t.grid is not None and (t.grid[0] not in (1, HH) or t.grid[1] not in (1, WW)):
+        raise ValueError(f"{what}: a time field over {t.grid} does not broadcast to the {HH} x {WW} grid")
+
+
 def dec_stage1(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, image: "DecImageDev" = None, flags=0, status=None,
                window: L.DecWindow = None):
     """window (dec_window): the stage over that rectangle of the tables' grid -- flow [n, hh, ww, 4] (None: HRfeat
-    only), hrfeat over the window's F rectangle."""
+    only), hrfeat over the window's F rectangle.  t: the [n] time tensor, or a DecTime (a time per pixel of the
+    tables' grid; no image, no shifted tables)."""
     n, h, w, _ = proj.shape
     trace = None
+    if isinstance(t, DecTime):
+        _time_field_call(t, n, image, tables, "dec_stage1")
+        HH, WW = _win_shapes(window, tables, n, hrfeat, flow) if window is not None else hrfeat.shape[1:3]
+        if window is None and TRACE is not None:
+            trace = (("dec1",), 2.0 * 62464 * n * HH * WW)
+        _launch("stif_dec_stage1_tf", trace, L.lib().stif_dec_stage1_tf, _vp(proj), _vp(mlp), C.byref(tables.c), None,
+                C.byref(t.c), _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream(),
+                C.byref(window) if window is not None else None)
+        return
     if window is not None:
         HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
         what, fn, tail = "stif_dec_stage1_win", L.lib().stif_dec_stage1_win, (C.byref(window),)
@@ -497,6 +553,11 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
     trace = None
     if blend is not None and (window is None or image is not None):
         raise ValueError("dec_stage2: the blending epilogue is the windowed stage's, without a high-resolution image")
+    tf = isinstance(t, DecTime)
+    if tf:
+        _time_field_call(t, n, image, tables, "dec_stage2")
+        if blend is not None:
+            raise ValueError("dec_stage2: a time field has no blending (local-ensemble) form")
     if window is not None:
         HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
         if tuple(out.shape) != (n, 3, window.hh, window.ww) or (window.ww > 1 and out.stride(3) != 1):
@@ -504,15 +565,20 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
         win = L.DecWindow.from_buffer_copy(window)
         win.out_item, win.out_plane, win.out_pitch = out.stride(0), out.stride(1), out.stride(2)
         what, fn, tail = "stif_dec_stage2_win", L.lib().stif_dec_stage2_win, (C.byref(win),)
+        if tf:
+            what, fn = "stif_dec_stage2_tf", L.lib().stif_dec_stage2_tf
         if blend is not None:
             what, fn, tail = "stif_dec_stage2_blend_win", L.lib().stif_dec_stage2_blend_win, (C.byref(blend), C.byref(win))
     else:
         HH, WW = hrfeat.shape[1:3]
         what, fn, tail = "stif_dec_stage2", L.lib().stif_dec_stage2_ex, ()
+        if tf:
+            what, fn, tail = "stif_dec_stage2_tf", L.lib().stif_dec_stage2_tf, (None,)
         if TRACE is not None:   # per HR px: encode_imnet HRfeat part + layers 1-4 (94,976 MAC)
             trace = (("dec2",), 2.0 * 94976 * n * HH * WW)
     _launch(what, trace, fn, _vp(proj), _vp(mlp), _vp(hrfeat), _vp(flow), C.byref(tables.c),
-            C.byref(image.c) if image else None, _vp(t), _vp(out), n, h, w, HH, WW, flags, _vp(status), _stream(), *tail)
+            C.byref(image.c) if image else None, C.byref(t.c) if tf else _vp(t), _vp(out), n, h, w, HH, WW, flags,
+            _vp(status), _stream(), *tail)
 
 
 # ----------------------------------------------------------------------------- video I/O (planar YUV <-> RGB)

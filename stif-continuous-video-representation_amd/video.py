@@ -59,7 +59,8 @@ def single_forward(model, imgs_in: torch.Tensor, times=None):
 def run_sequence(model, frames: torch.Tensor, times=None, scale=None, window=None, ensemble=False):
     """frames [F,3,h,w] -> list over the F-1 pairs of lists over times of [3,HH,WW]; window=(y0, x0, hh, ww):
     only that rectangle of every output frame, [3,hh,ww] (LunaTokis.decoding's window); ensemble: every frame
-    decoded with the local ensemble (LunaTokis.decoding's ensemble)."""
+    decoded with the local ensemble (LunaTokis.decoding's ensemble).  A tensor entry of ``times`` is passed to
+    ``decoding`` as it is -- e.g. a time field ([HH, WW], [HH, 1], ...: every pixel of every pair at its own time)."""
     with torch.no_grad():
         fr = pad_to_4(frames)
         model.gen_feat_window(fr)
@@ -67,7 +68,7 @@ def run_sequence(model, frames: torch.Tensor, times=None, scale=None, window=Non
         kw = {} if window is None else {"window": window}
         if ensemble:
             kw["ensemble"] = True
-        preds = model.decoding([torch.tensor([t])[None] for t in ts], scale, **kw)
+        preds = model.decoding([t if isinstance(t, torch.Tensor) else torch.tensor([t])[None] for t in ts], scale, **kw)
     return [[p[i] for p in preds] for i in range(frames.shape[0] - 1)]
 
 

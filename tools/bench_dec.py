@@ -1,5 +1,7 @@
 """Decoder-only microbenchmark: C0 latents computed once, then REPS x model.decoding (k_pack_lr, the
-LR projection, k_dec1, k_dec2) with HIP-event times per decoder kernel kind."""
+LR projection, k_dec1, k_dec2) with HIP-event times per decoder kernel kind.
+TF=dense|row: the same decode through the time-field kernels -- every query time as a dense [B, HH, WW] field, or as
+a row field ([B, HH, 1], column stride 0), of the constant value, so the output is the scalar decode's."""
 import os
 import sys
 
@@ -19,8 +21,15 @@ model = stif.LunaTokis(64, 6, 8, 5, 40, device=dev)
 model.load_state_dict(sd, strict=True)
 frames = bench.synth_frames(0, nframes, H, W, dev)
 tq = [torch.tensor([[t]], device=dev) for t in times]
+tf = os.environ.get("TF", "")
+if tf not in ("", "dense", "row"):
+    raise SystemExit(f"TF must be dense or row, got {tf!r}")
 with torch.no_grad():
     model.gen_feat_window(frames)
+    if tf:
+        B, _, HH, WW = model.decoding(tq[:1], None)[0].shape
+        tq = [torch.full((B, HH, WW if tf == "dense" else 1), float(t), device=dev) for t in times]
+        print(f"TF={tf}: time fields of shape {tuple(tq[0].shape)}", flush=True)
     model.decoding(tq, None)
     torch.cuda.synchronize()
     probe = bench.KernelTimer(None)
