@@ -447,6 +447,44 @@ int stif_dec_stage2_tf(const float* proj, const float* mlp, const float* hrfeat,
                        const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t, float* out, int n,
                        int h, int w, int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win);
 
+/* ---- point queries: any set of pixels of the virtual grid, each at its own time, at the cost of those pixels.
+ * The RGB of point (item i, row y, column x, time t) is bit for bit what stif_dec_stage1_ex / stif_dec_stage2_ex with
+ * the per-item time t write at [i][:][y][x].  The eight HRfeat rows stage 2 gathers for a point (the corners of its
+ * two warped grids) are computed with the point's own time -- unlike a time field, where a corner row carries the
+ * corner pixel's time -- so every point is an independent sample of the scalar-time decode.  Corners are not shared
+ * between points (two points at one pixel with different times have different corner rows): a point costs about
+ * nine feat_imnet evaluations instead of one, and a dense block of pixels is cheaper as a window.
+ * Per call: stif_dec_stage1_pts (flow, and the points' own HRfeat) -> stif_dec_corners_pts (the corner list)
+ * -> stif_dec_stage1_pts over the corner list with flow = NULL (the compact HRfeat [n][npts][8][64])
+ * -> stif_dec_stage2_pts.  Nothing is read back between them. ---- */
+
+/* point p of item i: row y[i * y_item + p], column x[i * x_item + p], time t[i * t_item + p * t_point];
+ * strides in elements, >= 0, 0 broadcasts; npts >= 1 points per item */
+typedef struct { const int* y; const int* x; const float* t; long long y_item, x_item, t_item, t_point; int npts; } stif_dec_points;
+
+/* Every kernel that reads y / x clamps them into the HH x WW grid before use; if it had to, bit 3 (value 8) is
+ * OR'ed into *status (the value of that point is the clamped pixel's; no read left a buffer).  All three entry
+ * points return STIF_E_INVALID, with the reason in stif_last_error, for a null pointer, npts < 1, n * 8 * npts
+ * beyond INT_MAX, a negative stride and tables with hr_y / hr_x. */
+
+/* Stage 1 over the points: hrfeat [n][npts][64] and flow [n][npts][4], each point's bit for bit those of
+ * stif_dec_stage1_ex at its pixel with its time.  flow = NULL: feat_imnet only. */
+int stif_dec_stage1_pts(const float* proj, const float* mlp, const stif_dec_tables* tab, const stif_dec_points* pts,
+                        float* hrfeat, float* flow, int n, int h, int w, int HH, int WW, int flags, int* status,
+                        void* stream);
+/* The HRfeat corner pixels stage 2 gathers for every point given its flow [n][npts][4], as a point list of 8 * npts
+ * entries per item: cy, cx (clamped rows / columns) and ct (the point's time) are [n][8 * npts]; entries 8 p + 0..3
+ * are the corners (y0, x0), (y0, x1), (y1, x0), (y1, x1) of point p's first warped grid, 8 p + 4..7 those of its
+ * second; corners of weight zero are listed too.  {cy, cx, ct, 8 * npts, 8 * npts, 8 * npts, 1, 8 * npts} is the
+ * stif_dec_points of the feat-only pass. */
+int stif_dec_corners_pts(const float* flow, const stif_dec_tables* tab, const stif_dec_points* pts, int* cy, int* cx,
+                         float* ct, int n, int HH, int WW, int* status, void* stream);
+/* Stage 2 over the points: hrfeat8 [n][npts][8][64] holds the corner rows in stif_dec_corners_pts' order, flow is
+ * stage 1's; out [n][3][npts].  Bit 0 of *status as stif_dec_stage2_ex (OR'ed in, so bit 3 survives). */
+int stif_dec_stage2_pts(const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
+                        const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h, int w,
+                        int HH, int WW, int flags, int* status, void* stream);
+
 /* ---- evaluation: PSNR / SSIM of decoded frames against ground truth (myutils.py:1151-1174, util.py:105-174) ---- */
 
 /* stif_metric_args.flags */

@@ -83,7 +83,14 @@ class DecTimeField(C.Structure):
     _fields_ = [("t", _P), ("item", C.c_longlong), ("row", C.c_longlong), ("col", C.c_longlong)]
 
 
-METRIC_Y, METRIC_SSIM, METRIC_FLOAT = 1, 2, 4   # stif_metric_args.flags (stif.h STIF_METRIC_*)
+class DecPointList(C.Structure):
+    """stif_dec_points: point p of item i is row y[i * y_item + p], column x[i * x_item + p] of the virtual grid at
+    time t[i * t_item + p * t_point] (strides in elements, >= 0, 0 broadcasts); npts points per item."""
+    _fields_ = [("y", _P), ("x", _P), ("t", _P), ("y_item", C.c_longlong), ("x_item", C.c_longlong),
+                ("t_item", C.c_longlong), ("t_point", C.c_longlong), ("npts", C.c_int)]
+
+
+METRIC_Y, METRIC_SSIM, METRIC_FLOAT = 1, 2, 4  # stif_metric_args.flags (stif.h STIF_METRIC_*)
 FSSIM_VOLUME, FSSIM_PLANAR = 0, 1               # stif_metric_float's mode (stif.h STIF_FSSIM_*)
 
 
@@ -150,6 +157,12 @@ EXPORTS = {
                            + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
     "stif_dec_stage2_tf": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecImage),
                                      C.POINTER(DecTimeField), _P] + [C.c_int] * 6 + [_P, _P, C.POINTER(DecWindow)]),
+    "stif_dec_stage1_pts": (C.c_int, [_P, _P, C.POINTER(DecTables), C.POINTER(DecPointList), _P, _P]
+                            + [C.c_int] * 6 + [_P, _P]),
+    "stif_dec_corners_pts": (C.c_int, [_P, C.POINTER(DecTables), C.POINTER(DecPointList), _P, _P, _P]
+                             + [C.c_int] * 3 + [_P, _P]),
+    "stif_dec_stage2_pts": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecPointList), _P]
+                            + [C.c_int] * 6 + [_P, _P]),
     "stif_dec_blend4": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "stif_upsample_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "stif_resize_frames": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int,

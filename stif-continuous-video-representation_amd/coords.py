@@ -126,6 +126,66 @@ def classify_time_query(shape, B: int, HH: int, WW: int) -> tuple:
                      f"[{B}, {HH}, {WW}]")
 
 
+def classify_point_query(y_shape, x_shape, t_shape, B: int) -> tuple:
+    """What the arguments of ``decoding_points`` of these shapes mean for a latent of ``B`` items:
+    ``(n, ys, xs, ts)`` -- n points per item, and for ``y``, ``x`` and ``times`` the two-dim shape (items, points)
+    to view each as, a dim of 1 broadcasting: ys / xs are (1, n) for an [n] list shared by every item or (B, n) for
+    a list per item; ts is (1, 1) for one value, (B, 1) for [B] (a time per item), (1, n) for [n] (a time per
+    point, shared by the items) or (B, n).  A one-dim ``times`` of B elements is [B], also when B == n: a time per
+    point that all items share has then to be given as [B, n] (or expanded).  Anything else is a ValueError."""
+    B = int(B)
+
+    def coord(shape, name):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) == 1 and shape[0] >= 1:
+            return (1, shape[0])
+        if len(shape) == 2 and shape[0] == B and shape[1] >= 1:
+            return shape
+        raise ValueError(f"{name} of shape {shape} is neither [n] nor [{B}, n] with n >= 1")
+
+    ys, xs = coord(y_shape, "y"), coord(x_shape, "x")
+    n = ys[1]
+    if xs[1] != n:
+        raise ValueError(f"y holds {n} points per item, x {xs[1]}")
+    t_shape = tuple(int(s) for s in t_shape)
+    numel = int(np.prod(t_shape, dtype=np.int64)) if t_shape else 1
+    if numel == 1:
+        ts = (1, 1)
+    elif t_shape == (B,):
+        ts = (B, 1)
+    elif t_shape == (n,):
+        ts = (1, n)
+    elif t_shape == (B, n):
+        ts = (B, n)
+    else:
+        raise ValueError(f"times of shape {t_shape} is neither one value, [{B}], [{n}] nor [{B}, {n}]")
+    return n, ys, xs, ts
+
+
+def point_strides(shape2, strides) -> tuple:
+    """(item, point) element strides of a tensor viewed as ``shape2`` (``classify_point_query``) with ``strides``:
+    a dim of size 1 broadcasts (stride 0)."""
+    return tuple(0 if s == 1 else int(st) for s, st in zip(shape2, strides))
+
+
+def check_points(y, x, HH: int, WW: int) -> None:
+    """IndexError unless every row of ``y`` is in [0, HH) and every column of ``x`` in [0, WW) (host arrays)."""
+    for name, v, size in (("y", y, HH), ("x", x, WW)):
+        v = np.asarray(v)
+        if v.size and (int(v.min()) < 0 or int(v.max()) >= size):
+            bad = v[(v < 0) | (v >= size)].reshape(-1)[0]
+            raise IndexError(f"point {name} = {int(bad)} is outside the virtual grid axis of {size}")
+
+
+def point_passes(B: int, n: int, chunk_px: int) -> tuple:
+    """The passes of a point decode whose compact HRfeat (8 corner rows per point) stays within ``chunk_px`` rows
+    per pass: ``(items, ranges)`` -- at most ``items`` items per pass, and the point ranges [p0, p1) of at most
+    ``max(1, chunk_px // 8)`` points that cover [0, n)."""
+    pp = max(1, int(chunk_px) // 8)
+    ranges = [(p0, min(n, p0 + pp)) for p0 in range(0, n, pp)]
+    return max(1, min(int(B), int(chunk_px) // (8 * min(n, pp)))), ranges
+
+
 def row_time_field(HH: int, t: float, skew: float) -> np.ndarray:
     """A rolling-shutter style time field, [HH, 1] fp32: row y is decoded at t + skew * (y / (HH - 1) - 0.5)."""
     y = np.arange(HH, dtype=np.float64) / max(HH - 1, 1)

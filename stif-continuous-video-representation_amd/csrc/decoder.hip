@@ -169,23 +169,37 @@ STIF_DEV WarpGrids warp_grids(const f32x4 fv, float bx, float by, int WW, int HH
   return g;
 }
 
-// The range report of stage 2; the windowed kernels OR bit 0 in, so that bilin_hr's bit 1 survives it
-template <bool WIN>
+// The addressing forms of the pixel front end (pixel_of): the whole HH x WW grid, the query rectangle of a
+// stif_dec_window, or a list of points (stif_dec_points).  The kernels take the form as a template argument; the
+// bool WIN of the host code converts to the first two.
+constexpr int GRID = 0, WINDOW = 1, PTS = 2;
+
+// The range report of stage 2; the windowed and the point kernels OR bit 0 in, so that bilin_hr's bit 1 and the
+// points' bit 3 survive it
+template <bool OR>
 STIF_DEV void report_range_w(int* status, bool bad) {
-  if constexpr (WIN) {
+  if constexpr (OR) {
     if (status != nullptr && bad) atomicOr(status, 1);
   } else {
     report_range(status, bad);
   }
 }
 
-// The HRfeat gather of stage 2 at grid (gx, gy).  WIN: hrfeat holds the F rectangle of the grid, [fh][fw][64]; a
+// The HRfeat gather of stage 2 at grid (gx, gy).  WINDOW: hrfeat holds the F rectangle of the grid, [fh][fw][64]; a
 // corner outside it is clamped into it and reported (bit 1 of *status), so a too-small F gives a flagged wrong
-// result and never an out-of-range read.
-template <bool WIN>
-STIF_DEV Bilin bilin_hr(float gx, float gy, int WW, int HH, const stif_dec_window& win, int* status) {
-  if constexpr (!WIN) {
+// result and never an out-of-range read.  PTS: hrfeat holds the eight corner rows of every point, [npts][8][64] in
+// k_dec_corners' order, and the corners of this grid are rows slot .. slot + 3 (slot = 8 p for grid 1, 8 p + 4 for
+// grid 2) -- the offsets depend on nothing the kernel computes, the weights are bilin_corners' as everywhere.
+template <int FORM>
+STIF_DEV Bilin bilin_hr(float gx, float gy, int WW, int HH, const stif_dec_window& win, int* status, int slot = 0) {
+  if constexpr (FORM == GRID) {
     return bilin(gx, gy, WW, HH);
+  } else if constexpr (FORM == PTS) {
+    const Corners c = bilin_corners(gx, gy, WW, HH);
+    Bilin b;
+    b.o00 = slot; b.o01 = slot + 1; b.o10 = slot + 2; b.o11 = slot + 3;
+    b.w00 = c.w00; b.w01 = c.w01; b.w10 = c.w10; b.w11 = c.w11;
+    return b;
   } else {
     const Corners c = bilin_corners(gx, gy, WW, HH);
     const int ry0 = c.cy0 - win.fy0, ry1 = c.cy1 - win.fy0, rx0 = c.cx0 - win.fx0, rx1 = c.cx1 - win.fx0;
@@ -255,39 +269,73 @@ STIF_DEV f32x4 img_sample(const float* __restrict__ I, const Bilin& b, int hf) {
 // The HR pixel a lane works on, in workgroups of NW waves at PPW pixels per wave (lane & (PPW - 1): the other lanes
 // hold the same pixels).  The pixels are counted over the whole HH x WW grid or, WIN, over win's query rectangle
 // (row-major per item); lanes past the end redo the last pixel and store nothing (valid).
+// PTS: the pixels are the n * npts points of a stif_dec_points (item pc / npts, point pt = pc % npts); ly / lx are
+// the point's row / column of the virtual grid, clamped into it (point_yx).
 struct Pixel {
   bool valid;
-  long long pc;     // index among all n * rows * columns pixels
+  long long pc;     // index among all n * rows * columns pixels (PTS: n * npts points)
   int item, ly, lx; // item, row and column in the grid / rectangle
+  int pt;           // PTS: the point's index in its item's list
 };
-template <int NW, int PPW, bool WIN>
-STIF_DEV Pixel pixel_of(int wv, int lane, int n, int HH, int WW, const stif_dec_window& win) {
-  const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
-  const long long total = (long long)n * GH * GW;
-  const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW + wv) * PPW + (lane & (PPW - 1));
+// Row and column of point pt of `item`, clamped into the HH x WW grid: every table read and every address made from
+// them stays inside its buffer whatever the list holds.  A clamp is reported as bit 3 (value 8) of *status.
+STIF_DEV void point_yx(const stif_dec_points& pts, int item, int pt, int HH, int WW, int* status, int& y, int& x) {
+  const int ry = pts.y[item * pts.y_item + pt], rx = pts.x[item * pts.x_item + pt];
+  y = min(max(ry, 0), HH - 1), x = min(max(rx, 0), WW - 1);
+  if (status != nullptr && (y != ry || x != rx)) atomicOr(status, 8);
+}
+template <int NW, int PPW, int FORM, class TQ>
+STIF_DEV Pixel pixel_of(int wv, int lane, int n, int HH, int WW, const stif_dec_window& win, const TQ& tq,
+                        int* status) {
   Pixel o;
-  o.valid = p < total;
-  o.pc = o.valid ? p : total - 1;
-  o.item = (int)(o.pc / ((long long)GH * GW));
-  const int rem = (int)(o.pc - (long long)o.item * GH * GW);
-  o.ly = rem / GW, o.lx = rem - o.ly * GW;
+  if constexpr (FORM == PTS) {
+    const long long total = (long long)n * tq.npts;
+    const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW + wv) * PPW + (lane & (PPW - 1));
+    o.valid = p < total;
+    o.pc = o.valid ? p : total - 1;
+    o.item = (int)(o.pc / tq.npts);
+    o.pt = (int)(o.pc - (long long)o.item * tq.npts);
+    point_yx(tq, o.item, o.pt, HH, WW, status, o.ly, o.lx);
+  } else {
+    constexpr bool WIN = FORM == WINDOW;
+    const int GH = WIN ? win.hh : HH, GW = WIN ? win.ww : WW;   // the rectangle the pixels are counted over
+    // the count before the lane's index, in this order: computed the other way round the existing kernels come out
+    // with a different schedule and register allocation
+    const long long total = (long long)n * GH * GW;
+    const long long p = ((long long)xcd_block(blockIdx.x, gridDim.x) * NW + wv) * PPW + (lane & (PPW - 1));
+    o.valid = p < total;
+    o.pc = o.valid ? p : total - 1;
+    o.item = (int)(o.pc / ((long long)GH * GW));
+    const int rem = (int)(o.pc - (long long)o.item * GH * GW);
+    o.ly = rem / GW, o.lx = rem - o.ly * GW;
+    o.pt = 0;
+  }
   return o;
 }
 
-// The query time of a pixel.  TF false: one value per item, tq[item] (the scalar kernels).  TF true (time field):
-// every pixel its own, t[item * item + gy * row + gx * col] at row gy / column gx of the virtual grid -- strides in
-// elements, 0 broadcasts.  A tail lane redoes the last pixel (pixel_of), so its read is one a valid lane makes too.
-template <bool TF>
+// The query time of a pixel, by the kind TQ of the kernel's time argument.  0: one value per item, tq[item] (the
+// scalar kernels).  1 (time field): every pixel its own, t[item * item + gy * row + gx * col] at row gy / column gx
+// of the virtual grid -- strides in elements, 0 broadcasts.  2 (points): t[item * t_item + pt * t_point] of the
+// stif_dec_points, which is the kernel's point list as well.  A tail lane redoes the last pixel (pixel_of), so its
+// read is one a valid lane makes too.
+template <int TQ>
 struct TimeArg {
   typedef const float* __restrict__ type;
 };
 template <>
-struct TimeArg<true> {
+struct TimeArg<1> {
   typedef stif_dec_time type;
 };
-template <bool TF>
-STIF_DEV float time_at(const typename TimeArg<TF>::type& tq, int item, int gy, int gx) {
-  if constexpr (TF) return tq.t[item * tq.item + gy * tq.row + gx * tq.col];
+template <>
+struct TimeArg<2> {
+  typedef stif_dec_points type;
+};
+template <int FORM, bool TF>
+constexpr int TQK = FORM == PTS ? 2 : TF ? 1 : 0;
+template <int TQ>
+STIF_DEV float time_at(const typename TimeArg<TQ>::type& tq, int item, int gy, int gx, int pt = 0) {
+  if constexpr (TQ == 2) return tq.t[item * tq.t_item + pt * tq.t_point];
+  else if constexpr (TQ == 1) return tq.t[item * tq.item + gy * tq.row + gx * tq.col];
   else return tq[item];
 }
 
@@ -314,10 +362,12 @@ STIF_DEV float blend_weight(const stif_dec_blend& bl, int gy, int gx) {
 // `r = p0 w0; r += p1 w1` into fma(p0, w0, p1 * w1): its one rounded product is decode 1's, then come the fmas of
 // decodes 0, 2 and 3 -- so launching the decodes in the order 1, 0, 2, 3 reproduces its bits (model.py does).
 // The pixel's lane owns its three output elements: no atomics.
-template <bool WIN, bool REPORT, bool BLEND = false>
+// PTS: the caller passes the [n][3][npts] output as a one-row grid (py = 0, px = the point, HH = 1, WW = npts).
+template <int FORM, bool REPORT, bool BLEND = false>
 STIF_DEV void store_rgb(float* __restrict__ out, const float* __restrict__ mlp, const float* o4, const f32x4 fv,
                         int item, int py, int px, int HH, int WW, const stif_dec_window& win, int* status,
                         const stif_dec_blend& bl) {
+  constexpr bool WIN = FORM == WINDOW;
   static_assert(WIN || !BLEND, "the blending epilogue is the windowed stages'");
   const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
   float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
@@ -340,7 +390,7 @@ STIF_DEV void store_rgb(float* __restrict__ out, const float* __restrict__ mlp, 
       for (int c = 0; c < 3; ++c) o[c * plane] = __fmaf_rn(rgb[c], wk, o[c * plane]);
     }
   }
-  if constexpr (REPORT) report_range_w<WIN>(status, bad);
+  if constexpr (REPORT) report_range_w<FORM != GRID>(status, bad);
 }
 
 // ---- weight streaming: a workgroup consumes its MLP weight tiles segment by segment; each segment
@@ -442,14 +492,20 @@ constexpr int S1 = OCC1<MODE, HRIMG> == 4 ? 4 : OCC1<MODE, HRIMG> == 3 ? 6 : SEG
 // remapped HRfeat row is read from the F layout, its index clamped into F and a clamp reported (bit 2 of *status,
 // which no other instantiation touches), as bilin_hr does with bit 1.
 // TF: the time-field variant (time_at), MODE 0 / 1 without the HR image only; everything else is the scalar twin's.
-template <int MODE, bool HRIMG, int F16, bool WIN, bool TF = false>
+// FORM PTS (MODE 0 / 1, no HR image): the pixels are the points of tq, a stif_dec_points, each with its own time;
+// HRfeat and flow are stored at the point's running index, the whole-grid layout over the point list; a row /
+// column clamped into the grid is reported as bit 3 of *status (pixel_of).
+template <int MODE, bool HRIMG, int F16, int FORM, bool TF = false>
 __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<MODE, HRIMG>))) void k_dec1(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      stif_dec_tables tb, stif_dec_image im,
-                                                     typename TimeArg<TF>::type tq, float* __restrict__ hrfeat,
+                                                     typename TimeArg<TQK<FORM, TF>>::type tq, float* __restrict__ hrfeat,
                                                      float* __restrict__ flow, int n, int h, int w, int HH,
                                                      int WW, stif_dec_window win, int* status) {
+  constexpr bool WIN = FORM == WINDOW;
+  constexpr int TQ = TQK<FORM, TF>;
   static_assert(!(WIN && MODE == 2 && HRIMG), "the windowed flow-only stage takes no high-resolution image");
   static_assert(!TF || (MODE != 2 && !HRIMG), "a time field has no local-ensemble and no HR-image form");
+  static_assert(FORM != PTS || (MODE != 2 && !HRIMG && !TF), "a point list has no local-ensemble and no HR-image form");
   // two segment buffers of SEG1 tiles + the flow's last layer (plain [4][256], resident)
   constexpr bool OCC3 = S1<MODE, HRIMG> != SEG1;             // 3 or 4 workgroups per CU
   constexpr bool OCC4 = OCC1<MODE, HRIMG> == 4;
@@ -467,7 +523,7 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
     dma_tiles<NW1>(B1, rm, L_W0, 4, wv, lane);
     dma_tiles<NW1>(B1 + 4 * T, rm, L_W1, 4, wv, lane);
   }
-  const Pixel pix = pixel_of<NW1, 32, WIN>(wv, lane, n, HH, WW, win);
+  const Pixel pix = pixel_of<NW1, 32, FORM>(wv, lane, n, HH, WW, win, tq, status);
   const bool valid = pix.valid;
   const long long pc = pix.pc;
   const int item = pix.item;
@@ -475,9 +531,9 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
   const int py = WIN ? win.y0 + pix.ly : pix.ly, px = WIN ? win.x0 + pix.lx : pix.lx;
   // the scalar kernels load the item's time once; a time-field kernel reads its pixel's time where it is used (feat
   // layer 0, flow layer 0) and does not keep it in a register across the feat stage
-  const float t = TF ? 0.f : time_at<TF>(tq, item, py, px);
+  const float t = TF ? 0.f : time_at<TQ>(tq, item, py, px, pix.pt);
   auto time = [&]() {
-    if constexpr (TF) return time_at<TF>(tq, item, py, px);
+    if constexpr (TF) return time_at<TQ>(tq, item, py, px);
     else return t;
   };
   const float* P = proj + (size_t)item * h * w * PROJ_C;
@@ -678,14 +734,20 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
 // WIN: the pixels are those of win's query rectangle, flow is read at the
 // pixel's index in the rectangle, the linspace base at its row / column of the virtual grid, HRfeat in win's F
 // rectangle (bilin_hr) and the RGB goes through win's output addressing.
-template <bool HRIMG, int F16, bool WIN, bool BLEND = false, bool TF = false>   // TF: as k_dec1's
+// FORM PTS: the pixels are the points of tq (flow at the point's index, the linspace base at its clamped row /
+// column, its own time), hrfeat holds the points' corner rows [n][npts][8][64] (bilin_hr) and the RGB goes to
+// out[item][c][point].
+template <bool HRIMG, int F16, int FORM, bool BLEND = false, bool TF = false>   // TF: as k_dec1's
 __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DEC2_WPE))) void k_dec2(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      const float* __restrict__ hrfeat, const float* __restrict__ flow,
                                                      stif_dec_tables tb, stif_dec_image im,
-                                                     typename TimeArg<TF>::type tq, float* __restrict__ out, int n,
+                                                     typename TimeArg<TQK<FORM, TF>>::type tq, float* __restrict__ out, int n,
                                                      int h, int w, int HH, int WW, int* status, stif_dec_window win,
                                                      stif_dec_blend bl) {
+  constexpr bool WIN = FORM == WINDOW;
+  constexpr int TQ = TQK<FORM, TF>;
   static_assert(!TF || (!HRIMG && !BLEND), "a time field has no HR-image and no blending form");
+  static_assert(FORM != PTS || (!HRIMG && !BLEND && !TF), "a point list has no HR-image and no blending form");
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEG * T];
   const int lane = threadIdx.x & 63, hf = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
@@ -695,12 +757,13 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   // segments: [L0: 8 tiles] [L1: 4] then per layer-2 tile kt: [W2 rows kt (2) + W3 column kt (8)],
   // then [W4: 8]
   dma_tiles<DEC2_NW>(B0, rm, E_W0, 8, wv, lane);
-  const Pixel pix = pixel_of<DEC2_NW, 32, WIN>(wv, lane, n, HH, WW, win);
+  const Pixel pix = pixel_of<DEC2_NW, 32, FORM>(wv, lane, n, HH, WW, win, tq, status);
   const long long pc = pix.pc;
   const int item = pix.item, py = pix.ly, px = pix.lx;   // row / column in the rectangle
-  const float t = time_at<TF>(tq, item, WIN ? win.y0 + py : py, WIN ? win.x0 + px : px);
+  const float t = time_at<TQ>(tq, item, WIN ? win.y0 + py : py, WIN ? win.x0 + px : px, pix.pt);
   const float* P = proj + (size_t)item * h * w * PROJ_C;
   const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
+  if constexpr (FORM == PTS) HRF = hrfeat + (size_t)item * tq.npts * 8 * 64;   // eight corner rows per point
 
   // warpgrid and the decoder's clamp (warp_grids)
   const f32x4 fv = ld4(flow + (size_t)pc * 4);
@@ -732,7 +795,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
       img_mma(z, mlp + I_E2, img_sample(I, bilin(wg.g2x, wg.g2y, im.iw, im.ih), hf), lane);
     }
     asm volatile("" ::: "memory");
-    gather64<8>(q, HRF, 64, 0, bilin_hr<WIN>(wg.g1x, wg.g1y, WW, HH, win, status), hf);   // q_feat1 -> W0 columns 0..63
+    gather64<8>(q, HRF, 64, 0, bilin_hr<FORM>(wg.g1x, wg.g1y, WW, HH, win, status, 8 * pix.pt), hf);   // q_feat1 -> W0 columns 0..63
     lds_dma_barrier();
     dma_tiles<DEC2_NW>(B1, rm, E_W1, 4, wv, lane);
     {
@@ -743,7 +806,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
         for (int kt = 0; kt < 2; ++kt) tile_mma<F16>(z[ot], B0 + (ot * 4 + kt) * T, qs[kt], lane);
     }
     asm volatile("" ::: "memory");
-    gather64<8>(q, HRF, 64, 0, bilin_hr<WIN>(wg.g2x, wg.g2y, WW, HH, win, status), hf);   // q_feat2 -> W0 columns 64..127
+    gather64<8>(q, HRF, 64, 0, bilin_hr<FORM>(wg.g2x, wg.g2y, WW, HH, win, status, 8 * pix.pt + 4), hf);   // q_feat2 -> W0 columns 64..127
     const XT<F16> qs[2] = {xop<F16>(q[0]), xop<F16>(q[1])};
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot) {
@@ -808,7 +871,10 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) o4[c] += __shfl_xor(o4[c], 32);   // the other lane half's 128 features
-  if (pix.valid && hf == 0) store_rgb<WIN, F16 != 0, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
+  if (pix.valid && hf == 0) {
+    if constexpr (FORM == PTS) store_rgb<PTS, F16 != 0>(out, mlp, o4, fv, item, 0, pix.pt, 1, tq.npts, win, status, bl);
+    else store_rgb<FORM, F16 != 0, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
+  }
 }
 
 
@@ -892,12 +958,15 @@ STIF_DEV void gather_q(R32* dst, const float* __restrict__ base, int stride, int
   }
 }
 
-template <bool WIN, bool BLEND = false, bool TF = false>   // WIN, BLEND, TF: as k_dec2's
+template <int FORM, bool BLEND = false, bool TF = false>   // FORM, BLEND, TF: as k_dec2's
 __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_dec2q(
     const float* __restrict__ proj, const float* __restrict__ mlp, const float* __restrict__ hrfeat,
-    const float* __restrict__ flow, stif_dec_tables tb, typename TimeArg<TF>::type tq, float* __restrict__ out, int n,
-    int h, int w, int HH, int WW, int* status, stif_dec_window win, stif_dec_blend bl) {
+    const float* __restrict__ flow, stif_dec_tables tb, typename TimeArg<TQK<FORM, TF>>::type tq,
+    float* __restrict__ out, int n, int h, int w, int HH, int WW, int* status, stif_dec_window win, stif_dec_blend bl) {
+  constexpr bool WIN = FORM == WINDOW;
+  constexpr int TQ = TQK<FORM, TF>;
   static_assert(!TF || !BLEND, "a time field has no blending form");
+  static_assert(FORM != PTS || (!BLEND && !TF), "a point list has no blending form");
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEGQ * T];
   const int lane = threadIdx.x & 63, q = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -917,12 +986,13 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
       dec_dma(rm, dst + j * T + (i & 3) * 256, lane, src * 4);
     }
   };
-  const Pixel pix = pixel_of<NW, 16, WIN>(wv, lane, n, HH, WW, win);
+  const Pixel pix = pixel_of<NW, 16, FORM>(wv, lane, n, HH, WW, win, tq, status);
   const long long pc = pix.pc;
   const int item = pix.item, py = pix.ly, px = pix.lx;   // row / column in the rectangle
-  const float t = time_at<TF>(tq, item, WIN ? win.y0 + py : py, WIN ? win.x0 + px : px);
+  const float t = time_at<TQ>(tq, item, WIN ? win.y0 + py : py, WIN ? win.x0 + px : px, pix.pt);
   const float* P = proj + (size_t)item * h * w * PROJ_C;
   const float* HRF = hrfeat + (WIN ? (size_t)item * win.fh * win.fw * 64 : (size_t)item * HH * WW * 64);
+  if constexpr (FORM == PTS) HRF = hrfeat + (size_t)item * tq.npts * 8 * 64;   // eight corner rows per point
 
   // warpgrid (warplayer.py:25-39) and the decoder's clamp (Sakuya_arch_test.py:428,441), as k_dec2
   const f32x4 fv = ld4(flow + (size_t)pc * 4);
@@ -947,7 +1017,7 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
           z[ot].s[s][e] = (z[ot].s[s][e] + (g[ot].s[s][e] + wt[e] * t + bb[e])) * ACC_IN<1>;
       }
     asm volatile("" ::: "memory");
-    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(wg.g1x, wg.g1y, WW, HH, win, status), q);   // q_feat1 -> W0 columns 0..63
+    gather_q(g, HRF, 64, 0, bilin_hr<FORM>(wg.g1x, wg.g1y, WW, HH, win, status, 8 * pix.pt), q);   // q_feat1 -> W0 columns 0..63
     lds_dma_barrier();                                      // layer 0 landed in B0
     dma_tiles<NW>(B1, rm, Q_W1, 4, wv, lane);
     {
@@ -958,7 +1028,7 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
         for (int kt = 0; kt < 2; ++kt) tile_q(z[ot], B0 + (ot * 4 + kt) * T, qs[kt], lane);
     }
     asm volatile("" ::: "memory");
-    gather_q(g, HRF, 64, 0, bilin_hr<WIN>(wg.g2x, wg.g2y, WW, HH, win, status), q);   // q_feat2 -> W0 columns 64..127
+    gather_q(g, HRF, 64, 0, bilin_hr<FORM>(wg.g2x, wg.g2y, WW, HH, win, status, 8 * pix.pt + 4), q);   // q_feat2 -> W0 columns 64..127
     const XQ qs[2] = {xq(g[0]), xq(g[1])};
 #pragma unroll
     for (int ot = 0; ot < 2; ++ot) {
@@ -1033,7 +1103,10 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
     o4[c] += __shfl_xor(o4[c], 16);
     o4[c] += __shfl_xor(o4[c], 32);
   }
-  if (pix.valid && q == 0) store_rgb<WIN, true, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
+  if (pix.valid && q == 0) {
+    if constexpr (FORM == PTS) store_rgb<PTS, true>(out, mlp, o4, fv, item, 0, pix.pt, 1, tq.npts, win, status, bl);
+    else store_rgb<FORM, true, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
+  }
 }
 
 // k_dec_bounds: the box (rows ymin..ymax, columns xmin..xmax of the virtual grid, inclusive) of every HRfeat corner
@@ -1070,6 +1143,32 @@ __global__ __launch_bounds__(256) void k_dec_bounds(const float* __restrict__ fl
     atomicMax(box + 1, ymax);
     atomicMin(box + 2, xmin);
     atomicMax(box + 3, xmax);
+  }
+}
+
+// k_dec_corners: k_dec_bounds' sibling for point lists.  Per point, from its stage-1 flow: the eight HRfeat corner
+// pixels stage 2 gathers -- warp_grids + bilin_corners on stage 2's operands -- written as a point list of 8 npts
+// entries per item, slots 8 p + 0..3 the corners 00, 01, 10, 11 (row digit first) of grid 1 and 8 p + 4..7 those
+// of grid 2, each with the point's time: a feat-only stage 1 over that list gives the [npts][8][64] rows bilin_hr's
+// point form addresses.  Corners of weight 0 are written too (stage 2 loads them).
+__global__ __launch_bounds__(256) void k_dec_corners(const float* __restrict__ flow, stif_dec_tables tb,
+                                                     stif_dec_points pts, int* __restrict__ cy, int* __restrict__ cx,
+                                                     float* __restrict__ ct, long long total, int HH, int WW,
+                                                     int* status) {
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
+    const int item = (int)(p / pts.npts), pt = (int)(p - (long long)item * pts.npts);
+    int y, x;
+    point_yx(pts, item, pt, HH, WW, status, y, x);
+    const float t = time_at<2>(pts, item, y, x, pt);
+    const WarpGrids g = warp_grids(ld4(flow + (size_t)p * 4), tb.lin_x[x], tb.lin_y[y], WW, HH);
+    const Corners c[2] = {bilin_corners(g.g1x, g.g1y, WW, HH), bilin_corners(g.g2x, g.g2y, WW, HH)};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const Corners& a = c[k >> 2];
+      cy[p * 8 + k] = (k & 2) ? a.cy1 : a.cy0;
+      cx[p * 8 + k] = (k & 1) ? a.cx1 : a.cx0;
+      ct[p * 8 + k] = t;
+    }
   }
 }
 
@@ -1364,7 +1463,82 @@ int dec_stage2_tf(const char* me, const float* proj, const float* mlp, const flo
   return stif_check_launch(me);
 }
 
+// ---- point queries: the stages over a list of points (stif_dec_points) instead of a grid or a rectangle
+// the reason a point call is invalid before its generic argument check, or null
+const char* points_invalid(const stif_dec_tables* tab, const stif_dec_points* p, int n, int HH, int WW) {
+  if (!p || !p->y || !p->x || !p->t) return "null point list (pts or its y, x or t)";
+  if (p->npts < 1) return "npts < 1";
+  if (p->y_item < 0 || p->x_item < 0 || p->t_item < 0 || p->t_point < 0) return "negative point stride";
+  if (n >= 1 && (long long)n * 8 * p->npts > INT_MAX) return "n * 8 * npts exceeds INT_MAX";
+  if (tab && (tab->hr_y || tab->hr_x)) return "tables with hr_y / hr_x (local ensemble) have no point form";
+  if (HH < 2 || WW < 2 || (long long)HH * WW > INT_MAX) return "bad virtual grid size";
+  return nullptr;
+}
+
+int dec_stage1_pts(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
+                   const stif_dec_points* pts, float* hrfeat, float* flow, int n, int h, int w, int HH, int WW,
+                   int flags, int* status, void* stream) {
+  if (!proj || !mlp || !tables_ok(tab) || !hrfeat || n < 1 || h < 1 || w < 1)
+    return window_fail(me, "bad arguments (null pointer or empty shape)");
+  if (const char* why = points_invalid(tab, pts, n, HH, WW)) return window_fail(me, why);
+  const long long total = (long long)n * pts->npts;
+  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
+  with_bool(flags & STIF_CONV_F16X3, [&](auto f16x3) {
+    with_bool(flow != nullptr, [&](auto fused) {   // a null flow is the feat-only pass
+      hipLaunchKernelGGL((k_dec1<decltype(fused)::value ? 0 : 1, false, decltype(f16x3)::value, PTS>), grid,
+                         dim3(NW1 * 64), 0, (hipStream_t)stream, proj, mlp, *tab, stif_dec_image{}, *pts, hrfeat, flow,
+                         n, h, w, HH, WW, stif_dec_window{}, status);
+    });
+  });
+  return stif_check_launch(me);
+}
+
+int dec_stage2_pts(const char* me, const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
+                   const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h, int w, int HH,
+                   int WW, int flags, int* status, void* stream) {
+  if (!proj || !mlp || !hrfeat8 || !flow || !tables_ok(tab) || !out || n < 1 || h < 1 || w < 1)
+    return window_fail(me, "bad arguments (null pointer or empty shape)");
+  if (const char* why = points_invalid(tab, pts, n, HH, WW)) return window_fail(me, why);
+  const long long total = (long long)n * pts->npts;
+  auto grid = [&](int wg_pixels) { return dim3((unsigned)((total + wg_pixels - 1) / wg_pixels)); };
+  hipStream_t st = (hipStream_t)stream;
+  if (flags & STIF_CONV_F16X3)
+    hipLaunchKernelGGL((k_dec2q<PTS>), grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat8, flow, *tab,
+                       *pts, out, n, h, w, HH, WW, status, stif_dec_window{}, stif_dec_blend{});
+  else
+    hipLaunchKernelGGL((k_dec2<false, 0, PTS>), grid(DEC2_NW * 32), dim3(DEC2_NW * 64), 0, st, proj, mlp, hrfeat8, flow,
+                       *tab, stif_dec_image{}, *pts, out, n, h, w, HH, WW, status, stif_dec_window{}, stif_dec_blend{});
+  return stif_check_launch(me);
+}
+
 }  // namespace
+
+extern "C" int stif_dec_stage1_pts(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                   const stif_dec_points* pts, float* hrfeat, float* flow, int n, int h, int w, int HH,
+                                   int WW, int flags, int* status, void* stream) {
+  return dec_stage1_pts("stif_dec_stage1_pts", proj, mlp, tab, pts, hrfeat, flow, n, h, w, HH, WW, flags, status,
+                        stream);
+}
+
+extern "C" int stif_dec_corners_pts(const float* flow, const stif_dec_tables* tab, const stif_dec_points* pts, int* cy,
+                                    int* cx, float* ct, int n, int HH, int WW, int* status, void* stream) {
+  static const char* const me = "stif_dec_corners_pts";
+  if (!flow || !tables_ok(tab) || !cy || !cx || !ct || n < 1)
+    return window_fail(me, "bad arguments (null pointer or n < 1)");
+  if (const char* why = points_invalid(tab, pts, n, HH, WW)) return window_fail(me, why);
+  const long long total = (long long)n * pts->npts;
+  const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_dec_corners, dim3(blocks), dim3(256), 0, (hipStream_t)stream, flow, *tab, *pts, cy, cx, ct,
+                     total, HH, WW, status);
+  return stif_check_launch(me);
+}
+
+extern "C" int stif_dec_stage2_pts(const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
+                                   const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h,
+                                   int w, int HH, int WW, int flags, int* status, void* stream) {
+  return dec_stage2_pts("stif_dec_stage2_pts", proj, mlp, hrfeat8, flow, tab, pts, out, n, h, w, HH, WW, flags, status,
+                        stream);
+}
 
 extern "C" int stif_dec_stage1_tf(const float* proj, const float* mlp, const stif_dec_tables* tab,
                                   const stif_dec_image* img, const stif_dec_time* t, float* hrfeat, float* flow, int n,

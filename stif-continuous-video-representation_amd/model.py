@@ -30,7 +30,8 @@ from torch import nn
 from . import _lib as L
 from . import ops
 from . import weights as W
-from .coords import check_window, classify_time_query, ensemble_weights, tile_windows, window_from_center
+from .coords import (check_points, check_window, classify_point_query, classify_time_query, ensemble_weights,
+                     point_passes, point_strides, tile_windows, window_from_center)
 from .packing import pack_model
 
 _CONST_LOCK = threading.Lock()   # _const's dict is shared by DataParallel replicas (replicate() threads)
@@ -904,6 +905,119 @@ class LunaTokis(nn.Module):
             return self.decoding(times, scale, ensemble=ensemble)
         finally:
             self._feat, self.inp = feat, inp
+
+    # ------------------------------------------------------------------ point queries
+    def decoding_points(self, y, x, times, scale=None, pairs=None, return_flow=False):
+        """The decode at a set of points: [B, 3, n] float32 on the device, unclamped, in the order given -- point p
+        of item b is, bit for bit, ``decoding([t], scale)[0][b, :, y, x]`` with that point's scalar time t.  With
+        ``return_flow`` also stage 1's flow [B, 4, n] in HR pixels.
+
+        ``y``, ``x``: integer rows / columns of the virtual HH x WW grid, [n] (the same points for every item) or
+        [B, n].  ``times``: a float, [B] (a time per item), [n] (a time per point) or [B, n]; a one-dim tensor of B
+        values is [B] also when B == n (``coords.classify_point_query``).  int32 / float32 tensors already on the
+        device are read in place through their strides; anything else is copied to the device once.
+
+        Every point is an independent sample of the scalar-time decode: the eight HRfeat rows stage 2 gathers for
+        it are computed with the point's own time (in a time field a gathered row carries its own pixel's time).
+        Nothing is shared between points, so a point costs about nine feat_imnet evaluations instead of one and a
+        dense block of pixels is cheaper as ``decoding(window=)``.  Measured on the C0 latent (six items, 512 x 512
+        grid, DESIGN.md section 3e'''): 4,096 points per item take 0.32 ms against 1.95 ms of the full decode, and
+        the full decode followed by an index wins above about 90,000 points per item, a third of the grid.
+
+        Host indices (lists, numpy, CPU tensors) are checked before any launch (IndexError).  Device indices are not
+        read back: the kernels clamp them into the grid and flag it, the flag is read once after the launches
+        (IndexError) -- not while the stream is being captured and not with range_check='off', when valid indices
+        are the caller's responsibility (they are still clamped).  ``pairs``: as ``decoding_pairs`` -- only those
+        items of the latent, B = len(pairs)."""
+        if pairs is None:
+            return self._call(self._decoding_points, y, x, times, scale, return_flow)
+        feat, inp = self.__dict__.get("_feat"), self.__dict__.get("inp")
+        if feat is None:
+            raise RuntimeError("decoding needs gen_feat first")
+        pairs = [int(i) for i in pairs]
+        if not pairs or min(pairs) < 0 or max(pairs) >= feat.shape[1]:
+            raise ValueError(f"pairs must be indices into the {feat.shape[1]} items of the latent, got {pairs}")
+        idx = torch.tensor(pairs, device=feat.device, dtype=torch.long)
+        self._feat, self.inp = feat.index_select(1, idx), inp.index_select(0, idx)
+        try:
+            return self._call(self._decoding_points, y, x, times, scale, return_flow)
+        finally:
+            self._feat, self.inp = feat, inp
+
+    def _point_list(self, y, x, times, B, HH, WW):
+        """The arguments of ``decoding_points`` as an ``ops.DecPoints`` over B items."""
+        def host(v):   # the host array of anything that is not on the device, else None
+            if isinstance(v, torch.Tensor):
+                return None if v.is_cuda else v.detach().numpy()
+            return np.asarray(v)
+
+        if not isinstance(times, (torch.Tensor, np.ndarray)):
+            times = np.asarray(times, dtype=np.float32)
+        n, ys, xs, ts = classify_point_query(tuple(y.shape) if hasattr(y, "shape") else np.shape(y),
+                                             tuple(x.shape) if hasattr(x, "shape") else np.shape(x),
+                                             tuple(times.shape), B)
+        hy, hx = host(y), host(x)
+        check_points(hy if hy is not None else (), hx if hx is not None else (), HH, WW)
+
+        def coord(v, hv, s2):
+            if hv is not None:
+                v = torch.from_numpy(np.ascontiguousarray(hv, dtype=np.int32))
+            elif v.is_floating_point() or v.dtype == torch.bool:
+                raise TypeError("decoding_points: y and x must be integers")
+            v = v.detach().to(self.device, torch.int32).reshape(s2)
+            if n > 1 and v.stride(1) != 1:
+                v = v.contiguous()
+            return v
+
+        yt, xt = coord(y, hy, ys), coord(x, hx, xs)
+        tt = (torch.from_numpy(times) if isinstance(times, np.ndarray) else times.detach())
+        tt = tt.to(self.device, torch.float32).reshape(ts)
+        (yi, _), (xi, _), (ti, tp) = (point_strides(s, v.stride()) for s, v in ((ys, yt), (xs, xt), (ts, tt)))
+        return ops.DecPoints(yt, xt, tt, yi, xi, ti, tp, n, B)
+
+    def _decoding_points(self, y, x, times, scale=None, return_flow=False):
+        if self._feat is None:
+            raise RuntimeError("decoding needs gen_feat first")
+        _, B, H, Wd, _ = self._feat.shape
+        HH, WW = _hr_size(H, Wd, scale)
+        pts = self._point_list(y, x, times, B, HH, WW)
+        n = pts.npts
+        tab = self._tab(H, Wd, HH, WW)
+        mlp, fl, st = self.layers["dec.mlp"], self._dec_flags, self._status
+        if st is not None and fl == 0:
+            st.zero_()   # fp32 operands: only the points' bit 3 is read below
+        out = self._empty(B, 3, n)
+        flw = self._empty(B, n, 4) if return_flow else None
+        # items and points per pass: 8 corner rows of HRfeat per point, at most dec_chunk_px rows per pass -- the
+        # scratch bound of the whole-grid decode; points are decoded independently, so chunking changes no bit
+        per, ranges = point_passes(B, n, self.dec_chunk_px)
+        whole = len(ranges) == 1
+
+        def body(proj, a, b):
+            k = b - a
+            for p0, p1 in ranges:
+                m = p1 - p0
+                sub = pts.sub(a, b, p0, p1)
+                hrf = self._empty(k, m, 64)
+                flow = flw[a:b] if whole and return_flow else self._empty(k, m, 4)
+                ops.dec_stage1_pts(proj, mlp, tab, sub, hrf, flow, flags=fl, status=st)
+                del hrf   # the point's own HRfeat row: stage 2 reads the corner rows only
+                cy, cx = (torch.empty(k, 8 * m, device=self.device, dtype=torch.int32) for _ in range(2))
+                corners = ops.dec_corners_pts(flow, tab, sub, cy, cx, self._empty(k, 8 * m), status=st)
+                hrf8 = self._empty(k, 8 * m, 64)
+                ops.dec_stage1_pts(proj, mlp, tab, corners, hrf8, None, flags=fl, status=st)
+                o = out[a:b] if whole else self._empty(k, 3, m)
+                ops.dec_stage2_pts(proj, mlp, hrf8, flow, tab, sub, o, flags=fl, status=st)
+                if not whole:
+                    out[a:b, :, p0:p1].copy_(o)
+                    if return_flow:
+                        flw[a:b, p0:p1].copy_(flow)
+                del hrf8, corners, cy, cx, flow, o
+                yield
+        self._decode_passes(B, per, True, body)
+        if st is not None and not torch.cuda.is_current_stream_capturing() and int(st.item()) & 8:
+            raise IndexError(f"decoding_points: a point lies outside the {HH} x {WW} grid")
+        return (out, flw.permute(0, 2, 1).contiguous()) if return_flow else out
 
     def _decode_passes(self, B, per, lr_image, body):
         """The items [0, B) over the ``dec`` lanes, in passes of ``per``: the LR projection of a pass's items

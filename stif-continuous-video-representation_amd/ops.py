@@ -581,6 +581,90 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
             _vp(status), _stream(), *tail)
 
 
+class DecPoints:
+    """A point list for dec_stage1_pts / dec_corners_pts / dec_stage2_pts (stif_dec_points): point p of item i is
+    row ``y`` / column ``x`` (int32) of the tables' grid at element offset i * y_item + p (i * x_item + p) and time
+    ``t`` (float32) at i * t_item + p * t_point from the tensors' first elements; strides >= 0, 0 broadcasts.
+    ``n``: the items the list holds (None when no item stride is set: any number).  ``sub(a, b, p0, p1)`` is the list
+    of points [p0, p1) of items [a, b)."""
+
+    def __init__(self, y, x, t, y_item, x_item, t_item, t_point, npts, n=None, offsets=(0, 0, 0)):
+        for v, dt, name in ((y, torch.int32, "y"), (x, torch.int32, "x"), (t, torch.float32, "t")):
+            if v.dtype != dt or not v.is_cuda:
+                raise ValueError(f"DecPoints: {name} must be a {dt} CUDA tensor")
+        if min(y_item, x_item, t_item, t_point) < 0:
+            raise ValueError("DecPoints: strides must be >= 0")
+        if npts < 1:
+            raise ValueError("DecPoints: at least one point per item")
+        self.y, self.x, self.t, self.n, self.npts = y, x, t, n, int(npts)
+        self.strides = (int(y_item), int(x_item), int(t_item), int(t_point))
+        self.offsets = tuple(int(o) for o in offsets)
+        oy, ox, ot = self.offsets
+        self.c = L.DecPointList(y.data_ptr() + 4 * oy, x.data_ptr() + 4 * ox, t.data_ptr() + 4 * ot, *self.strides,
+                                self.npts)
+
+    def sub(self, a, b, p0, p1):
+        yi, xi, ti, tp = self.strides
+        oy, ox, ot = self.offsets
+        return DecPoints(self.y, self.x, self.t, yi, xi, ti, tp, p1 - p0, None if self.n is None else b - a,
+                         (oy + a * yi + p0, ox + a * xi + p0, ot + a * ti + p0 * tp))
+
+
+def _points_call(pts, n, tables, what):
+    if "hr_y" in tables._t and tables.c.hr_y:
+        raise ValueError(f"{what}: a point list has no local-ensemble form")
+    if pts.n is not None and pts.n != n:
+        raise ValueError(f"{what}: the point list holds {pts.n} items, the call has {n}")
+
+
+def _dense(t, shape, dtype, what):
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor of shape {tuple(shape)}, got "
+                         f"{t.dtype} {tuple(t.shape)}")
+
+
+def dec_stage1_pts(proj, mlp, tables: DecTablesDev, pts: DecPoints, hrfeat, flow, flags=0, status=None):
+    """Stage 1 over a point list: hrfeat [n, npts, 64] and flow [n, npts, 4] (None: HRfeat only) of every point at
+    its own time.  A row / column outside the tables' grid is clamped into it and sets bit 3 of ``status``."""
+    n, h, w, _ = proj.shape
+    _points_call(pts, n, tables, "dec_stage1_pts")
+    _dense(hrfeat, (n, pts.npts, 64), torch.float32, "dec_stage1_pts: hrfeat")
+    if flow is not None:
+        _dense(flow, (n, pts.npts, 4), torch.float32, "dec_stage1_pts: flow")
+    HH, WW = tables.shape[2:]
+    _launch("stif_dec_stage1_pts", None, L.lib().stif_dec_stage1_pts, _vp(proj), _vp(mlp), C.byref(tables.c),
+            C.byref(pts.c), _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream())
+
+
+def dec_corners_pts(flow, tables: DecTablesDev, pts: DecPoints, cy, cx, ct, status=None) -> DecPoints:
+    """The eight HRfeat corner pixels stage 2 gathers for every point, from stage 1's flow [n, npts, 4], into cy, cx
+    (int32) and ct (float32, the point's time), each [n, 8 * npts]; returns them as the point list of the feat-only
+    pass (dec_stage1_pts with flow=None), whose hrfeat [n, 8 * npts, 64] is dec_stage2_pts' hrfeat8."""
+    n = flow.shape[0]
+    _points_call(pts, n, tables, "dec_corners_pts")
+    _dense(flow, (n, pts.npts, 4), torch.float32, "dec_corners_pts: flow")
+    m = 8 * pts.npts
+    for v, dt, name in ((cy, torch.int32, "cy"), (cx, torch.int32, "cx"), (ct, torch.float32, "ct")):
+        _dense(v, (n, m), dt, f"dec_corners_pts: {name}")
+    HH, WW = tables.shape[2:]
+    _launch("stif_dec_corners_pts", None, L.lib().stif_dec_corners_pts, _vp(flow), C.byref(tables.c), C.byref(pts.c),
+            _vp(cy), _vp(cx), _vp(ct), n, HH, WW, _vp(status), _stream())
+    return DecPoints(cy, cx, ct, m, m, m, 1, m, n)
+
+
+def dec_stage2_pts(proj, mlp, hrfeat8, flow, tables: DecTablesDev, pts: DecPoints, out, flags=0, status=None):
+    """Stage 2 over a point list: hrfeat8 [n, 8 * npts, 64] (the corner rows in dec_corners_pts' order), flow
+    [n, npts, 4], out [n, 3, npts]."""
+    n, h, w, _ = proj.shape
+    _points_call(pts, n, tables, "dec_stage2_pts")
+    _dense(hrfeat8, (n, 8 * pts.npts, 64), torch.float32, "dec_stage2_pts: hrfeat8")
+    _dense(flow, (n, pts.npts, 4), torch.float32, "dec_stage2_pts: flow")
+    _dense(out, (n, 3, pts.npts), torch.float32, "dec_stage2_pts: out")
+    HH, WW = tables.shape[2:]
+    _launch("stif_dec_stage2_pts", None, L.lib().stif_dec_stage2_pts, _vp(proj), _vp(mlp), _vp(hrfeat8), _vp(flow),
+            C.byref(tables.c), C.byref(pts.c), _vp(out), n, h, w, HH, WW, flags, _vp(status), _stream())
+
+
 # ----------------------------------------------------------------------------- video I/O (planar YUV <-> RGB)
 _YUV_MATRIX = {"bt601": L.YUV_BT601, "bt709": L.YUV_BT709}
 
