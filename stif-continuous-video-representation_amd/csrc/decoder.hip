@@ -1274,71 +1274,6 @@ int window_fail(const char* entry, const char* why) {
 template <int M>
 using Mode = std::integral_constant<int, M>;
 
-// Stage 1 behind its three entry points.  WIN: `win` is resolved here and the pixels are its query rectangle's;
-// the whole-grid form never looks at `win` and launches the WIN = false kernels, which never read the window.
-template <bool WIN>
-int dec_stage1(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
-               const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h, int w, int HH,
-               int WW, int flags, void* stream, const stif_dec_window* win) {
-  const bool args_ok = proj && mlp && tables_ok(tab) && image_ok(img) && t && hrfeat && n >= 1 && h >= 1 && w >= 1;
-  stif_dec_window wn{};
-  if constexpr (WIN) {   // a null flow is the feat-only pass
-    if (!args_ok) return window_fail(me, "bad arguments (null pointer or empty shape)");
-    if (tab->hr_y || tab->hr_x) return window_fail(me, "tables with hr_y / hr_x (local ensemble) have no windowed form");
-    if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
-    // every pixel of the query rectangle stores its HRfeat row into the F layout
-    if (!f_holds_query(wn)) return window_fail(me, "the F rectangle does not contain the query rectangle");
-  } else if (!args_ok || !flow || HH < 2 || WW < 2 || (!tab->hr_y) != (!tab->hr_x)) {
-    return stif_fail(STIF_E_INVALID, "stif_dec_stage1: bad arguments");
-  }
-  const bool f16 = flags & STIF_CONV_F16X3;
-  const long long total = (long long)n * (WIN ? wn.hh : HH) * (WIN ? wn.ww : WW);
-  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
-  const stif_dec_image im = img ? *img : stif_dec_image{};
-  auto launch = [&](auto mode, auto hrimg) {
-    with_bool(f16, [&](auto f16x3) {
-      hipLaunchKernelGGL((k_dec1<decltype(mode)::value, decltype(hrimg)::value, decltype(f16x3)::value, WIN>), grid,
-                         dim3(NW1 * 64), 0, (hipStream_t)stream, proj, mlp, *tab, im, t, hrfeat, flow, n, h, w, HH,
-                         WW, wn, (int*)nullptr);
-    });
-  };
-  if constexpr (WIN) {
-    with_bool(img != nullptr, [&](auto hrimg) {
-      if (!flow) launch(Mode<1>{}, hrimg);
-      else launch(Mode<0>{}, hrimg);
-    });
-  } else if (tab->hr_y) {   // remapped HRfeat operand: the whole HRfeat map first, then the flow stage
-    launch(Mode<1>{}, std::false_type{});
-    with_bool(img != nullptr, [&](auto hrimg) { launch(Mode<2>{}, hrimg); });
-  } else {
-    with_bool(img != nullptr, [&](auto hrimg) { launch(Mode<0>{}, hrimg); });
-  }
-  return stif_check_launch(me);
-}
-
-// The windowed flow-only stage (local ensemble): flow_imnet over win's query rectangle, its HRfeat operand the row of
-// HR pixel (hr_y, hr_x) in the F layout.  F need not hold the query rectangle, only the remap rectangle -- which the
-// kernel enforces (clamp + bit 2 of *status), since the tables live on the device.
-int dec_flow_win(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
-                 const stif_dec_image* img, const float* t, const float* hrfeat, float* flow, int n, int h, int w,
-                 int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win) {
-  if (!proj || !mlp || !tables_ok(tab) || !t || !hrfeat || !flow || n < 1 || h < 1 || w < 1)
-    return window_fail(me, "bad arguments (null pointer or empty shape)");
-  if (img) return window_fail(me, "a high-resolution image (img) is not supported here: pass NULL");
-  if (!tab->hr_y || !tab->hr_x) return window_fail(me, "the tables carry no hr_y / hr_x remap (local ensemble)");
-  stif_dec_window wn{};
-  if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
-  const long long total = (long long)n * wn.hh * wn.ww;
-  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
-  with_bool(flags & STIF_CONV_F16X3, [&](auto f16x3) {
-    // MODE 2 only reads hrfeat
-    hipLaunchKernelGGL((k_dec1<2, false, decltype(f16x3)::value, true>), grid, dim3(NW1 * 64), 0, (hipStream_t)stream,
-                       proj, mlp, *tab, stif_dec_image{}, t, const_cast<float*>(hrfeat), flow, n, h, w, HH, WW, wn,
-                       status);
-  });
-  return stif_check_launch(me);
-}
-
 // the reason a stif_dec_blend is invalid, or null
 const char* blend_invalid(const stif_dec_blend* b) {
   if (!b) return "null blend";
@@ -1349,58 +1284,6 @@ const char* blend_invalid(const stif_dec_blend* b) {
   return nullptr;
 }
 
-// Stage 2 behind its entry points (WIN as dec_stage1's).  blend (WIN only; checked by the caller): the blending
-// epilogue of the local ensemble instead of the plain store.  f16x3 operands without an HR image go to k_dec2q
-// (16 pixels per wave, four waves per SIMD: C2 stage 2 17.55-17.79 -> 17.32-17.34 ms, profiles/r04_dec2q4_ab.log);
-// the fp32 and the HR-image stages to k_dec2.
-template <bool WIN>
-int dec_stage2(const char* me, const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-               const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n, int h, int w,
-               int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win,
-               const stif_dec_blend* blend = nullptr) {
-  const bool args_ok = proj && mlp && hrfeat && flow && tables_ok(tab) && image_ok(img) && t && out && n >= 1 &&
-                       h >= 1 && w >= 1;
-  stif_dec_window wn{};
-  if constexpr (WIN) {
-    if (!args_ok) return window_fail(me, "bad arguments (null pointer or empty shape)");
-    if (const char* why = window_resolve(win, HH, WW, &wn)) return window_fail(me, why);
-  } else if (!args_ok || HH < 2 || WW < 2) {
-    return stif_fail(STIF_E_INVALID, "stif_dec_stage2: bad arguments");
-  }
-  const bool f16 = flags & STIF_CONV_F16X3;
-  const long long total = (long long)n * (WIN ? wn.hh : HH) * (WIN ? wn.ww : WW);
-  auto grid = [&](int wg_pixels) { return dim3((unsigned)((total + wg_pixels - 1) / wg_pixels)); };
-  hipStream_t st = (hipStream_t)stream;
-  const stif_dec_blend bl = blend ? *blend : stif_dec_blend{};
-  if constexpr (WIN) {
-    if (blend) {   // no high-resolution image (the caller's check): k_dec2q, or k_dec2 for fp32 operands
-      if (f16)
-        hipLaunchKernelGGL((k_dec2q<true, true>), grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat,
-                           flow, *tab, t, out, n, h, w, HH, WW, status, wn, bl);
-      else
-        hipLaunchKernelGGL((k_dec2<false, 0, true, true>), grid(DEC2_NW * 32), dim3(DEC2_NW * 64), 0, st, proj, mlp,
-                           hrfeat, flow, *tab, stif_dec_image{}, t, out, n, h, w, HH, WW, status, wn, bl);
-      return stif_check_launch(me);
-    }
-  }
-  if (f16 && !img) {
-    hipLaunchKernelGGL(k_dec2q<WIN>, grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat, flow, *tab, t,
-                       out, n, h, w, HH, WW, status, wn, bl);
-  } else {
-    const stif_dec_image im = img ? *img : stif_dec_image{};
-    with_bool(img != nullptr, [&](auto hrimg) {
-      with_bool(f16, [&](auto f16x3) {
-        if constexpr (decltype(hrimg)::value || !decltype(f16x3)::value)   // the other pair is k_dec2q's, above
-          hipLaunchKernelGGL((k_dec2<decltype(hrimg)::value, decltype(f16x3)::value, WIN>), grid(DEC2_NW * 32),
-                             dim3(DEC2_NW * 64), 0, st, proj, mlp, hrfeat, flow, *tab, im, t, out, n, h, w, HH, WW,
-                             status, wn, bl);
-      });
-    });
-  }
-  return stif_check_launch(me);
-}
-
-// ---- time fields: the stages with a query time per pixel (stif_dec_time) instead of one per item
 // the reason a time-field call is invalid before its generic argument check, or null
 const char* time_field_invalid(const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t) {
   if (img) return "a high-resolution image (img) has no time-field form: pass NULL";
@@ -1410,61 +1293,7 @@ const char* time_field_invalid(const stif_dec_tables* tab, const stif_dec_image*
   return nullptr;
 }
 
-// the window of a time-field call resolved into wn (win null: the whole grid, wn untouched), or the reason it is invalid
-const char* tf_window(const stif_dec_window* win, int HH, int WW, stif_dec_window* wn) {
-  if (win) return window_resolve(win, HH, WW, wn);
-  return HH < 2 || WW < 2 || (long long)HH * WW > INT_MAX ? "bad virtual grid size" : nullptr;
-}
-
-int dec_stage1_tf(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
-                  const stif_dec_image* img, const stif_dec_time* t, float* hrfeat, float* flow, int n, int h, int w,
-                  int HH, int WW, int flags, void* stream, const stif_dec_window* win) {
-  if (const char* why = time_field_invalid(tab, img, t)) return window_fail(me, why);
-  if (!proj || !mlp || !tables_ok(tab) || !hrfeat || n < 1 || h < 1 || w < 1)
-    return window_fail(me, "bad arguments (null pointer or empty shape)");
-  stif_dec_window wn{};
-  if (const char* why = tf_window(win, HH, WW, &wn)) return window_fail(me, why);
-  if (win && !f_holds_query(wn)) return window_fail(me, "the F rectangle does not contain the query rectangle");
-  const long long total = (long long)n * (win ? wn.hh : HH) * (win ? wn.ww : WW);
-  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
-  with_bool(flags & STIF_CONV_F16X3, [&](auto f16x3) {
-    with_bool(win != nullptr, [&](auto windowed) {
-      with_bool(flow != nullptr, [&](auto fused) {   // a null flow is the feat-only pass
-        hipLaunchKernelGGL((k_dec1<decltype(fused)::value ? 0 : 1, false, decltype(f16x3)::value,
-                                   decltype(windowed)::value, true>),
-                           grid, dim3(NW1 * 64), 0, (hipStream_t)stream, proj, mlp, *tab, stif_dec_image{}, *t, hrfeat,
-                           flow, n, h, w, HH, WW, wn, (int*)nullptr);
-      });
-    });
-  });
-  return stif_check_launch(me);
-}
-
-int dec_stage2_tf(const char* me, const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                  const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t, float* out, int n,
-                  int h, int w, int HH, int WW, int flags, int* status, void* stream, const stif_dec_window* win) {
-  if (const char* why = time_field_invalid(tab, img, t)) return window_fail(me, why);
-  if (!proj || !mlp || !hrfeat || !flow || !tables_ok(tab) || !out || n < 1 || h < 1 || w < 1)
-    return window_fail(me, "bad arguments (null pointer or empty shape)");
-  stif_dec_window wn{};
-  if (const char* why = tf_window(win, HH, WW, &wn)) return window_fail(me, why);
-  const long long total = (long long)n * (win ? wn.hh : HH) * (win ? wn.ww : WW);
-  auto grid = [&](int wg_pixels) { return dim3((unsigned)((total + wg_pixels - 1) / wg_pixels)); };
-  hipStream_t st = (hipStream_t)stream;
-  with_bool(win != nullptr, [&](auto windowed) {
-    constexpr bool WIN = decltype(windowed)::value;
-    if (flags & STIF_CONV_F16X3)
-      hipLaunchKernelGGL((k_dec2q<WIN, false, true>), grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat,
-                         flow, *tab, *t, out, n, h, w, HH, WW, status, wn, stif_dec_blend{});
-    else
-      hipLaunchKernelGGL((k_dec2<false, 0, WIN, false, true>), grid(DEC2_NW * 32), dim3(DEC2_NW * 64), 0, st, proj, mlp,
-                         hrfeat, flow, *tab, stif_dec_image{}, *t, out, n, h, w, HH, WW, status, wn, stif_dec_blend{});
-  });
-  return stif_check_launch(me);
-}
-
-// ---- point queries: the stages over a list of points (stif_dec_points) instead of a grid or a rectangle
-// the reason a point call is invalid before its generic argument check, or null
+// the reason a point call is invalid after its generic argument check, or null
 const char* points_invalid(const stif_dec_tables* tab, const stif_dec_points* p, int n, int HH, int WW) {
   if (!p || !p->y || !p->x || !p->t) return "null point list (pts or its y, x or t)";
   if (p->npts < 1) return "npts < 1";
@@ -1475,49 +1304,266 @@ const char* points_invalid(const stif_dec_tables* tab, const stif_dec_points* p,
   return nullptr;
 }
 
-int dec_stage1_pts(const char* me, const float* proj, const float* mlp, const stif_dec_tables* tab,
-                   const stif_dec_points* pts, float* hrfeat, float* flow, int n, int h, int w, int HH, int WW,
-                   int flags, int* status, void* stream) {
-  if (!proj || !mlp || !tables_ok(tab) || !hrfeat || n < 1 || h < 1 || w < 1)
-    return window_fail(me, "bad arguments (null pointer or empty shape)");
-  if (const char* why = points_invalid(tab, pts, n, HH, WW)) return window_fail(me, why);
-  const long long total = (long long)n * pts->npts;
-  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
-  with_bool(flags & STIF_CONV_F16X3, [&](auto f16x3) {
-    with_bool(flow != nullptr, [&](auto fused) {   // a null flow is the feat-only pass
-      hipLaunchKernelGGL((k_dec1<decltype(fused)::value ? 0 : 1, false, decltype(f16x3)::value, PTS>), grid,
-                         dim3(NW1 * 64), 0, (hipStream_t)stream, proj, mlp, *tab, stif_dec_image{}, *pts, hrfeat, flow,
-                         n, h, w, HH, WW, stif_dec_window{}, status);
-    });
-  });
-  return stif_check_launch(me);
+// ---- One launcher per stage.  An entry point states its query -- whose pixels, which kind of time, which variant
+// of the stage -- and dec_stage1 / dec_stage2 check it, resolve it and launch it.
+struct TimeQ {   // the kernels' time argument, by kind (TimeArg): [n] times, a time field, or a point list
+  int kind;
+  const float* t = nullptr;
+  const stif_dec_time* field = nullptr;
+  const stif_dec_points* pts = nullptr;
+  TimeQ(const float* v) : kind(0), t(v) {}
+  TimeQ(const stif_dec_time* v) : kind(1), field(v) {}
+  TimeQ(const stif_dec_points* v) : kind(2), pts(v) {}
+};
+template <int K>
+auto time_arg(const TimeQ& q) {   // what the kernel takes by value; the checks have seen the pointer
+  if constexpr (K == 2) return *q.pts;
+  else if constexpr (K == 1) return *q.field;
+  else return q.t;
 }
 
-int dec_stage2_pts(const char* me, const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
-                   const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h, int w, int HH,
-                   int WW, int flags, int* status, void* stream) {
-  if (!proj || !mlp || !hrfeat8 || !flow || !tables_ok(tab) || !out || n < 1 || h < 1 || w < 1)
-    return window_fail(me, "bad arguments (null pointer or empty shape)");
-  if (const char* why = points_invalid(tab, pts, n, HH, WW)) return window_fail(me, why);
-  const long long total = (long long)n * pts->npts;
+struct Query {
+  const char* me;                        // the entry point: the prefix of its messages
+  TimeQ time;
+  bool windowed = false;                 // the pixels are win's query rectangle (a point list is never windowed)
+  const stif_dec_window* win = nullptr;
+  bool flow_only = false;                // stage 1: the windowed flow-only stage of a shifted query (MODE 2 over F)
+  bool blending = false;                 // stage 2: the local ensemble's epilogue, as `blend` says
+  const stif_dec_blend* blend = nullptr;
+  int form() const { return time.kind == 2 ? PTS : windowed ? WINDOW : GRID; }
+  bool tf() const { return time.kind == 1; }
+  // the two whole-grid scalar stages reject everything with one text, "<entry>: bad arguments"
+  bool plain() const { return form() == GRID && !tf(); }
+};
+
+// The pixels of q: the window resolved into *wn (zeroes otherwise, which no kernel reads) and their number, or the
+// reason they are invalid.  The plain stages' grid size is part of their one argument check.
+const char* pixels_of(const Query& q, const stif_dec_tables* tab, int n, int HH, int WW, stif_dec_window* wn,
+                      long long* total) {
+  *wn = stif_dec_window{};
+  if (q.form() == PTS) {
+    if (const char* why = points_invalid(tab, q.time.pts, n, HH, WW)) return why;
+    *total = (long long)n * q.time.pts->npts;
+  } else if (q.form() == WINDOW) {
+    if (const char* why = window_resolve(q.win, HH, WW, wn)) return why;
+    *total = (long long)n * wn->hh * wn->ww;
+  } else {
+    if (q.tf() && (HH < 2 || WW < 2 || (long long)HH * WW > INT_MAX)) return "bad virtual grid size";
+    *total = (long long)n * HH * WW;
+  }
+  return nullptr;
+}
+
+// The instantiations the entry points can reach; the rest the kernels' static_asserts refuse, or nothing asks for.
+constexpr bool variant_exists(int form, bool blend, bool tf) {
+  return !(tf && form == PTS) && (!blend || (form == WINDOW && !tf));
+}
+constexpr bool dec1_exists(int mode, bool hrimg, int form, bool tf) {
+  if (tf || form == PTS) return variant_exists(form, false, tf) && mode != 2 && !hrimg;
+  // the whole grid's feat-only pass is the first half of the remapped stage, which takes the image in its second
+  return form == WINDOW ? !(mode == 2 && hrimg) : !(mode == 1 && hrimg);
+}
+constexpr bool dec2_exists(bool hrimg, bool f16, int form, bool blend, bool tf) {
+  // f16x3 operands without an HR image are k_dec2q's
+  return variant_exists(form, blend, tf) && (hrimg || !f16) && !(hrimg && (blend || tf || form == PTS));
+}
+
+// Stage 1.  A null flow is the feat-only pass (MODE 1), which the plain and the flow-only stage do not have.
+// flow_only: flow_imnet over the query rectangle, its HRfeat operand the row of HR pixel (hr_y, hr_x) in the F
+// layout; F need not hold the query rectangle, only the remap rectangle -- which the kernel enforces (clamp + bit 2
+// of *status), since the tables live on the device.
+int dec_stage1(const Query& q, const float* proj, const float* mlp, const stif_dec_tables* tab,
+               const stif_dec_image* img, float* hrfeat, float* flow, int n, int h, int w, int HH, int WW, int flags,
+               int* status, void* stream) {
+  const int form = q.form();
+  if (q.tf())
+    if (const char* why = time_field_invalid(tab, img, q.time.field)) return window_fail(q.me, why);
+  bool ok = proj && mlp && tables_ok(tab) && (q.flow_only || image_ok(img)) && (q.time.kind || q.time.t) && hrfeat &&
+            n >= 1 && h >= 1 && w >= 1;
+  if (q.plain() || q.flow_only) ok = ok && flow;
+  if (q.plain()) ok = ok && HH >= 2 && WW >= 2 && (!tab->hr_y) == (!tab->hr_x);
+  if (!ok) return window_fail(q.me, q.plain() ? "bad arguments" : "bad arguments (null pointer or empty shape)");
+  if (q.flow_only) {
+    if (img) return window_fail(q.me, "a high-resolution image (img) is not supported here: pass NULL");
+    if (!tab->hr_y || !tab->hr_x) return window_fail(q.me, "the tables carry no hr_y / hr_x remap (local ensemble)");
+  } else if (form == WINDOW && (tab->hr_y || tab->hr_x)) {
+    return window_fail(q.me, "tables with hr_y / hr_x (local ensemble) have no windowed form");
+  }
+  stif_dec_window wn;
+  long long total;
+  if (const char* why = pixels_of(q, tab, n, HH, WW, &wn, &total)) return window_fail(q.me, why);
+  // every pixel of the query rectangle stores its HRfeat row into the F layout
+  if (form == WINDOW && !q.flow_only && !f_holds_query(wn))
+    return window_fail(q.me, "the F rectangle does not contain the query rectangle");
+  const dim3 grid((unsigned)((total + NW1 * 32 - 1) / (NW1 * 32)));
+  const stif_dec_image im = img ? *img : stif_dec_image{};
+  auto launch = [&](auto mode, auto hrimg) {
+    with_bool(flags & STIF_CONV_F16X3, [&](auto f16x3) {
+      with_int<GRID, WINDOW, PTS>(form, [&](auto fm) {
+        with_bool(q.tf(), [&](auto field) {
+          constexpr int M = decltype(mode)::value, FM = decltype(fm)::value;
+          constexpr bool H = decltype(hrimg)::value, TF = decltype(field)::value;
+          if constexpr (dec1_exists(M, H, FM, TF))
+            hipLaunchKernelGGL((k_dec1<M, H, decltype(f16x3)::value, FM, TF>), grid, dim3(NW1 * 64), 0,
+                               (hipStream_t)stream, proj, mlp, *tab, im, time_arg<TQK<FM, TF>>(q.time), hrfeat, flow,
+                               n, h, w, HH, WW, wn, status);
+        });
+      });
+    });
+  };
+  if (q.flow_only) {   // MODE 2 only reads hrfeat
+    launch(Mode<2>{}, std::false_type{});
+  } else if (q.plain() && tab->hr_y) {   // remapped HRfeat operand: the whole HRfeat map first, then the flow stage
+    launch(Mode<1>{}, std::false_type{});
+    with_bool(img != nullptr, [&](auto hrimg) { launch(Mode<2>{}, hrimg); });
+  } else {
+    with_bool(img != nullptr, [&](auto hrimg) {
+      if (!flow) launch(Mode<1>{}, hrimg);
+      else launch(Mode<0>{}, hrimg);
+    });
+  }
+  return stif_check_launch(q.me);
+}
+
+// Stage 2.  f16x3 operands without an HR image go to k_dec2q (16 pixels per wave, four waves per SIMD: C2 stage 2
+// 17.55-17.79 -> 17.32-17.34 ms, profiles/r04_dec2q4_ab.log); the fp32 and the HR-image stages to k_dec2.
+int dec_stage2(const Query& q, const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+               const stif_dec_tables* tab, const stif_dec_image* img, float* out, int n, int h, int w, int HH, int WW,
+               int flags, int* status, void* stream) {
+  if (q.blending) {
+    if (const char* why = blend_invalid(q.blend)) return window_fail(q.me, why);
+    if (img) return window_fail(q.me, "a high-resolution image (img) is not supported here: pass NULL");
+  }
+  if (q.tf())
+    if (const char* why = time_field_invalid(tab, img, q.time.field)) return window_fail(q.me, why);
+  bool ok = proj && mlp && hrfeat && flow && tables_ok(tab) && image_ok(img) && (q.time.kind || q.time.t) && out &&
+            n >= 1 && h >= 1 && w >= 1;
+  if (q.plain()) ok = ok && HH >= 2 && WW >= 2;
+  if (!ok) return window_fail(q.me, q.plain() ? "bad arguments" : "bad arguments (null pointer or empty shape)");
+  stif_dec_window wn;
+  long long total;
+  if (const char* why = pixels_of(q, tab, n, HH, WW, &wn, &total)) return window_fail(q.me, why);
+  const bool f16 = flags & STIF_CONV_F16X3;
   auto grid = [&](int wg_pixels) { return dim3((unsigned)((total + wg_pixels - 1) / wg_pixels)); };
   hipStream_t st = (hipStream_t)stream;
-  if (flags & STIF_CONV_F16X3)
-    hipLaunchKernelGGL((k_dec2q<PTS>), grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat8, flow, *tab,
-                       *pts, out, n, h, w, HH, WW, status, stif_dec_window{}, stif_dec_blend{});
-  else
-    hipLaunchKernelGGL((k_dec2<false, 0, PTS>), grid(DEC2_NW * 32), dim3(DEC2_NW * 64), 0, st, proj, mlp, hrfeat8, flow,
-                       *tab, stif_dec_image{}, *pts, out, n, h, w, HH, WW, status, stif_dec_window{}, stif_dec_blend{});
-  return stif_check_launch(me);
+  const stif_dec_image im = img ? *img : stif_dec_image{};
+  const stif_dec_blend bl = q.blending ? *q.blend : stif_dec_blend{};
+  with_int<GRID, WINDOW, PTS>(q.form(), [&](auto fm) {
+    with_bool(q.tf(), [&](auto field) {
+      with_bool(q.blending, [&](auto blend) {
+        constexpr int FM = decltype(fm)::value;
+        constexpr bool TF = decltype(field)::value, B = decltype(blend)::value;
+        if (f16 && !img) {
+          if constexpr (variant_exists(FM, B, TF))
+            hipLaunchKernelGGL((k_dec2q<FM, B, TF>), grid(DEC2Q_NW * 16), dim3(DEC2Q_NW * 64), 0, st, proj, mlp, hrfeat,
+                               flow, *tab, time_arg<TQK<FM, TF>>(q.time), out, n, h, w, HH, WW, status, wn, bl);
+          return;
+        }
+        with_bool(img != nullptr, [&](auto hrimg) {
+          with_bool(f16, [&](auto f16x3) {
+            constexpr bool H = decltype(hrimg)::value, F = decltype(f16x3)::value;
+            if constexpr (dec2_exists(H, F, FM, B, TF))
+              hipLaunchKernelGGL((k_dec2<H, F, FM, B, TF>), grid(DEC2_NW * 32), dim3(DEC2_NW * 64), 0, st, proj, mlp,
+                                 hrfeat, flow, *tab, im, time_arg<TQK<FM, TF>>(q.time), out, n, h, w, HH, WW, status,
+                                 wn, bl);
+          });
+        });
+      });
+    });
+  });
+  return stif_check_launch(q.me);
 }
 
 }  // namespace
 
+// ---- the stage entry points: each states its query and calls its stage's launcher
+// status: stage 2 checks both stage-1 outputs it reads (flow, and HRfeat through the RGB; stif.h), so stage 1 has
+// nothing to report outside the flow-only and the point form
+extern "C" int stif_dec_stage1_ex(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                  const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
+                                  int w, int HH, int WW, int flags, int* /*status*/, void* stream) {
+  return dec_stage1({"stif_dec_stage1", t}, proj, mlp, tab, img, hrfeat, flow, n, h, w, HH, WW, flags, nullptr, stream);
+}
+
+extern "C" int stif_dec_stage1(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                               const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
+                               int w, int HH, int WW, void* stream) {
+  return stif_dec_stage1_ex(proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, 0, nullptr, stream);
+}
+
+extern "C" int stif_dec_stage1_win(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                   const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
+                                   int w, int HH, int WW, int flags, int* /*status*/, void* stream,
+                                   const stif_dec_window* win) {
+  return dec_stage1({"stif_dec_stage1_win", t, true, win}, proj, mlp, tab, img, hrfeat, flow, n, h, w, HH, WW, flags,
+                    nullptr, stream);
+}
+
+extern "C" int stif_dec_flow_win(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                 const stif_dec_image* img, const float* t, const float* hrfeat, float* flow, int n,
+                                 int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                 const stif_dec_window* win) {
+  return dec_stage1({"stif_dec_flow_win", t, true, win, true}, proj, mlp, tab, img, const_cast<float*>(hrfeat), flow,
+                    n, h, w, HH, WW, flags, status, stream);
+}
+
+extern "C" int stif_dec_stage1_tf(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                  const stif_dec_image* img, const stif_dec_time* t, float* hrfeat, float* flow, int n,
+                                  int h, int w, int HH, int WW, int flags, int* /*status*/, void* stream,
+                                  const stif_dec_window* win) {
+  return dec_stage1({"stif_dec_stage1_tf", t, win != nullptr, win}, proj, mlp, tab, img, hrfeat, flow, n, h, w, HH, WW,
+                    flags, nullptr, stream);
+}
+
 extern "C" int stif_dec_stage1_pts(const float* proj, const float* mlp, const stif_dec_tables* tab,
                                    const stif_dec_points* pts, float* hrfeat, float* flow, int n, int h, int w, int HH,
                                    int WW, int flags, int* status, void* stream) {
-  return dec_stage1_pts("stif_dec_stage1_pts", proj, mlp, tab, pts, hrfeat, flow, n, h, w, HH, WW, flags, status,
-                        stream);
+  return dec_stage1({"stif_dec_stage1_pts", pts}, proj, mlp, tab, nullptr, hrfeat, flow, n, h, w, HH, WW, flags,
+                    status, stream);
+}
+
+extern "C" int stif_dec_stage2_ex(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                  const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
+                                  int n, int h, int w, int HH, int WW, int flags, int* status, void* stream) {
+  return dec_stage2({"stif_dec_stage2", t}, proj, mlp, hrfeat, flow, tab, img, out, n, h, w, HH, WW, flags, status,
+                    stream);
+}
+
+extern "C" int stif_dec_stage2(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                               const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n,
+                               int h, int w, int HH, int WW, void* stream) {
+  return stif_dec_stage2_ex(proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, 0, nullptr, stream);
+}
+
+extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                   const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
+                                   int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                   const stif_dec_window* win) {
+  return dec_stage2({"stif_dec_stage2_win", t, true, win}, proj, mlp, hrfeat, flow, tab, img, out, n, h, w, HH, WW,
+                    flags, status, stream);
+}
+
+extern "C" int stif_dec_stage2_blend_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                         const stif_dec_tables* tab, const stif_dec_image* img, const float* t,
+                                         float* out, int n, int h, int w, int HH, int WW, int flags, int* status,
+                                         void* stream, const stif_dec_blend* blend, const stif_dec_window* win) {
+  return dec_stage2({"stif_dec_stage2_blend_win", t, true, win, false, true, blend}, proj, mlp, hrfeat, flow, tab, img,
+                    out, n, h, w, HH, WW, flags, status, stream);
+}
+
+extern "C" int stif_dec_stage2_tf(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
+                                  const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t,
+                                  float* out, int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                  const stif_dec_window* win) {
+  return dec_stage2({"stif_dec_stage2_tf", t, win != nullptr, win}, proj, mlp, hrfeat, flow, tab, img, out, n, h, w,
+                    HH, WW, flags, status, stream);
+}
+
+extern "C" int stif_dec_stage2_pts(const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
+                                   const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h,
+                                   int w, int HH, int WW, int flags, int* status, void* stream) {
+  return dec_stage2({"stif_dec_stage2_pts", pts}, proj, mlp, hrfeat8, flow, tab, nullptr, out, n, h, w, HH, WW, flags,
+                    status, stream);
 }
 
 extern "C" int stif_dec_corners_pts(const float* flow, const stif_dec_tables* tab, const stif_dec_points* pts, int* cy,
@@ -1531,91 +1577,6 @@ extern "C" int stif_dec_corners_pts(const float* flow, const stif_dec_tables* ta
   hipLaunchKernelGGL(k_dec_corners, dim3(blocks), dim3(256), 0, (hipStream_t)stream, flow, *tab, *pts, cy, cx, ct,
                      total, HH, WW, status);
   return stif_check_launch(me);
-}
-
-extern "C" int stif_dec_stage2_pts(const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
-                                   const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h,
-                                   int w, int HH, int WW, int flags, int* status, void* stream) {
-  return dec_stage2_pts("stif_dec_stage2_pts", proj, mlp, hrfeat8, flow, tab, pts, out, n, h, w, HH, WW, flags, status,
-                        stream);
-}
-
-extern "C" int stif_dec_stage1_tf(const float* proj, const float* mlp, const stif_dec_tables* tab,
-                                  const stif_dec_image* img, const stif_dec_time* t, float* hrfeat, float* flow, int n,
-                                  int h, int w, int HH, int WW, int flags, int* /*status*/, void* stream,
-                                  const stif_dec_window* win) {
-  return dec_stage1_tf("stif_dec_stage1_tf", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, stream, win);
-}
-
-extern "C" int stif_dec_stage2_tf(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                                  const stif_dec_tables* tab, const stif_dec_image* img, const stif_dec_time* t,
-                                  float* out, int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
-                                  const stif_dec_window* win) {
-  return dec_stage2_tf("stif_dec_stage2_tf", proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, flags, status,
-                       stream, win);
-}
-
-// status: stage 2 checks both stage-1 outputs it reads (flow, and HRfeat through the RGB; stif.h), so stage 1 has
-// nothing to report
-extern "C" int stif_dec_stage1_ex(const float* proj, const float* mlp, const stif_dec_tables* tab,
-                                  const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
-                                  int w, int HH, int WW, int flags, int* /*status*/, void* stream) {
-  return dec_stage1<false>("stif_dec_stage1", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, stream,
-                           nullptr);
-}
-
-extern "C" int stif_dec_stage1(const float* proj, const float* mlp, const stif_dec_tables* tab,
-                               const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
-                               int w, int HH, int WW, void* stream) {
-  return stif_dec_stage1_ex(proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, 0, nullptr, stream);
-}
-
-extern "C" int stif_dec_stage1_win(const float* proj, const float* mlp, const stif_dec_tables* tab,
-                                   const stif_dec_image* img, const float* t, float* hrfeat, float* flow, int n, int h,
-                                   int w, int HH, int WW, int flags, int* /*status*/, void* stream,
-                                   const stif_dec_window* win) {
-  return dec_stage1<true>("stif_dec_stage1_win", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, stream,
-                          win);
-}
-
-extern "C" int stif_dec_stage2_ex(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                                  const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
-                                  int n, int h, int w, int HH, int WW, int flags, int* status, void* stream) {
-  return dec_stage2<false>("stif_dec_stage2", proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, flags,
-                           status, stream, nullptr);
-}
-
-extern "C" int stif_dec_stage2(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                               const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out, int n,
-                               int h, int w, int HH, int WW, void* stream) {
-  return stif_dec_stage2_ex(proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, 0, nullptr, stream);
-}
-
-extern "C" int stif_dec_stage2_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                                   const stif_dec_tables* tab, const stif_dec_image* img, const float* t, float* out,
-                                   int n, int h, int w, int HH, int WW, int flags, int* status, void* stream,
-                                   const stif_dec_window* win) {
-  return dec_stage2<true>("stif_dec_stage2_win", proj, mlp, hrfeat, flow, tab, img, t, out, n, h, w, HH, WW, flags,
-                          status, stream, win);
-}
-
-extern "C" int stif_dec_flow_win(const float* proj, const float* mlp, const stif_dec_tables* tab,
-                                 const stif_dec_image* img, const float* t, const float* hrfeat, float* flow, int n,
-                                 int h, int w, int HH, int WW, int flags, int* status, void* stream,
-                                 const stif_dec_window* win) {
-  return dec_flow_win("stif_dec_flow_win", proj, mlp, tab, img, t, hrfeat, flow, n, h, w, HH, WW, flags, status,
-                      stream, win);
-}
-
-extern "C" int stif_dec_stage2_blend_win(const float* proj, const float* mlp, const float* hrfeat, const float* flow,
-                                         const stif_dec_tables* tab, const stif_dec_image* img, const float* t,
-                                         float* out, int n, int h, int w, int HH, int WW, int flags, int* status,
-                                         void* stream, const stif_dec_blend* blend, const stif_dec_window* win) {
-  static const char* const me = "stif_dec_stage2_blend_win";
-  if (const char* why = blend_invalid(blend)) return window_fail(me, why);
-  if (img) return window_fail(me, "a high-resolution image (img) is not supported here: pass NULL");
-  return dec_stage2<true>(me, proj, mlp, hrfeat, flow, tab, nullptr, t, out, n, h, w, HH, WW, flags, status, stream,
-                          win, blend);
 }
 
 extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int n, int HH, int WW,

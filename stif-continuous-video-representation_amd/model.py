@@ -58,6 +58,10 @@ def _split(n, k):
     return [(c0, min(n, c0 + per)) for c0 in range(0, n, per)]
 
 
+_NO_CAPTURE = ("a windowed / tiled decode reads the HRfeat bounding box back on the host: "
+               "it cannot be captured in a hipGraph")
+
+
 def _hr_size(H, Wd, scale):
     """(HH, WW) of decoding's virtual grid: ``scale`` itself, x4 by default."""
     return (H * 4, Wd * 4) if scale is None else (int(scale[0]), int(scale[1]))
@@ -872,6 +876,34 @@ class LunaTokis(nn.Module):
         independently, so each output equals that item's slice of a ``decoding`` of the whole latent bit for bit.
         The latent is left as it is (the video stream renderer decodes the pairs of a chunk that share a number
         of query times in one call).  ensemble: as ``decoding``'s."""
+        with self._pairs_selected(pairs, whole_as_is=True) as (pairs, idx, B):
+            if idx is not None and times is not None and len(pairs) != B:
+                # a time field over the latent's B items: its items are selected like the latent's (a field with
+                # len(pairs) items, or with none, is taken as it is -- as a vector of len(pairs) values is)
+                _, _, H, Wd, _ = self._feat.shape
+                HH, WW = _hr_size(H, Wd, scale)
+
+                def select(tq):
+                    if not isinstance(tq, (torch.Tensor, np.ndarray)):
+                        return tq
+                    if int(np.prod(tuple(tq.shape))) in (1, len(pairs)):
+                        return tq
+                    try:
+                        kind, s3 = classify_time_query(tq.shape, B, HH, WW)
+                    except ValueError:
+                        return tq   # decoding classifies it against the selected items
+                    if kind != "field" or s3[0] != B:
+                        return tq
+                    tq = torch.from_numpy(tq) if isinstance(tq, np.ndarray) else tq
+                    return tq.detach().reshape(s3).index_select(0, idx.to(tq.device))
+                times = [select(tq) for tq in times]
+            return self.decoding(times, scale, ensemble=ensemble)
+
+    @contextlib.contextmanager
+    def _pairs_selected(self, pairs, whole_as_is=False):
+        """The latent narrowed to its items ``pairs`` while the block runs, then as it was: yields (pairs as checked
+        ints, their index tensor, the latent's item count).  whole_as_is: ``pairs`` naming every item in order
+        leaves the latent alone (the index tensor is None)."""
         feat, inp = self.__dict__.get("_feat"), self.__dict__.get("inp")
         if feat is None:
             raise RuntimeError("decoding needs gen_feat first")
@@ -879,30 +911,13 @@ class LunaTokis(nn.Module):
         B = feat.shape[1]
         if not pairs or min(pairs) < 0 or max(pairs) >= B:
             raise ValueError(f"pairs must be indices into the {B} items of the latent, got {pairs}")
-        if pairs == list(range(B)):
-            return self.decoding(times, scale, ensemble=ensemble)
+        if whole_as_is and pairs == list(range(B)):
+            yield pairs, None, B
+            return
         idx = torch.tensor(pairs, device=feat.device, dtype=torch.long)
-        if times is not None and len(pairs) != B:
-            # a time field over the latent's B items: its items are selected like the latent's (a field with
-            # len(pairs) items, or with none, is taken as it is -- as a vector of len(pairs) values is)
-            _, _, H, Wd, _ = feat.shape
-            HH, WW = _hr_size(H, Wd, scale)
-
-            def select(tq):
-                if not isinstance(tq, (torch.Tensor, np.ndarray)) or int(np.prod(tuple(tq.shape))) in (1, len(pairs)):
-                    return tq
-                try:
-                    kind, s3 = classify_time_query(tq.shape, B, HH, WW)
-                except ValueError:
-                    return tq   # decoding classifies it against the selected items
-                if kind != "field" or s3[0] != B:
-                    return tq
-                tq = torch.from_numpy(tq) if isinstance(tq, np.ndarray) else tq
-                return tq.detach().reshape(s3).index_select(0, idx.to(tq.device))
-            times = [select(tq) for tq in times]
         self._feat, self.inp = feat.index_select(1, idx), inp.index_select(0, idx)
         try:
-            return self.decoding(times, scale, ensemble=ensemble)
+            yield pairs, idx, B
         finally:
             self._feat, self.inp = feat, inp
 
@@ -931,18 +946,8 @@ class LunaTokis(nn.Module):
         items of the latent, B = len(pairs)."""
         if pairs is None:
             return self._call(self._decoding_points, y, x, times, scale, return_flow)
-        feat, inp = self.__dict__.get("_feat"), self.__dict__.get("inp")
-        if feat is None:
-            raise RuntimeError("decoding needs gen_feat first")
-        pairs = [int(i) for i in pairs]
-        if not pairs or min(pairs) < 0 or max(pairs) >= feat.shape[1]:
-            raise ValueError(f"pairs must be indices into the {feat.shape[1]} items of the latent, got {pairs}")
-        idx = torch.tensor(pairs, device=feat.device, dtype=torch.long)
-        self._feat, self.inp = feat.index_select(1, idx), inp.index_select(0, idx)
-        try:
+        with self._pairs_selected(pairs):
             return self._call(self._decoding_points, y, x, times, scale, return_flow)
-        finally:
-            self._feat, self.inp = feat, inp
 
     def _point_list(self, y, x, times, B, HH, WW):
         """The arguments of ``decoding_points`` as an ``ops.DecPoints`` over B items."""
@@ -1057,45 +1062,80 @@ class LunaTokis(nn.Module):
         return self._decode(proj, times, HH, WW, tab, image)
 
     # ------------------------------------------------------------------ windowed decoding
+    def _window_F(self, flow, tab, box, win, base):
+        """The HRfeat rectangle F of a window: the bounding box of the HRfeat rows / columns stage 2 will gather
+        given stage 1's ``flow``, read back from the device, united with ``base``."""
+        ops.dec_bounds(flow, tab, box, win)
+        ymin, ymax, xmin, xmax = box.tolist()   # the device-to-host read (synchronises this stream)
+        fy0, fx0 = min(ymin, base[0]), min(xmin, base[1])
+        return fy0, fx0, max(ymax + 1, base[0] + base[2]) - fy0, max(xmax + 1, base[1] + base[3]) - fx0
+
+    def _stage2_given_F(self, proj, mlp, tab, feat_tab, t, hrf, flow, out, rect, frect, per, kw, image=None,
+                        blend=None):
+        """Stage 2 over the window ``rect`` into ``out`` with HRfeat over ``frect``.  ``hrf``: that HRfeat where
+        stage 1 left it over all of F; None where F is larger -- the caller has dropped its buffer, which the caching
+        allocator reuses for the F buffer (same stream) -- and HRfeat over F then comes from a feat-only stage 1
+        with ``feat_tab``, ``per`` items a pass.  kw: the stages' flags and status."""
+        HH, WW = tab.shape[2:]
+        wf = ops.dec_window(rect, HH, WW, frect)
+        if hrf is not None:
+            ops.dec_stage2(proj, mlp, hrf, flow, tab, t, out, image, window=wf, blend=blend, **kw)
+            return
+        n = proj.shape[0]
+        for a in range(0, n, per):
+            b = min(n, a + per)
+            img = image.items(a, b) if image is not None else None
+            hf = self._empty(b - a, frect[2], frect[3], 64)
+            ops.dec_stage1(proj[a:b], mlp, feat_tab, t[a:b], hf, None, img, window=ops.dec_window(frect, HH, WW), **kw)
+            ops.dec_stage2(proj[a:b], mlp, hf, flow[a:b], tab, t[a:b], out[a:b], img, window=wf, blend=blend, **kw)
+            del hf
+
     def _window_steps(self, proj, tvs, HH, WW, tab, outs, rect, image=None):
         """Decoder stages of every query time for the window ``rect`` into ``outs`` ([n,3,hh,ww] views; generator).
-        Per time: stage 1 (HRfeat + flow) over the window W; the bounding box of the HRfeat rows / columns stage 2
-        will gather, read back from the device; F = box U W; if F is larger than W, HRfeat over F by a feat-only
-        stage 1 (recomputing W's part: two launches with one layout beat a scatter of W's rows into F, and W is
-        the smaller part whenever the flows matter); stage 2 over W.  The F passes take at most
-        dec_chunk_px // |F| items each."""
+        Per time: stage 1 (HRfeat + flow) over the window W; F = box U W (``_window_F``); if F is larger than W,
+        HRfeat over F by a feat-only stage 1 (recomputing W's part: two launches with one layout beat a scatter of
+        W's rows into F, and W is the smaller part whenever the flows matter); stage 2 over W.  The F passes take at
+        most dec_chunk_px // |F| items each."""
         n = proj.shape[0]
-        y0, x0, hh, ww = rect
-        mlp, fl, st = self.layers["dec.mlp"], self._dec_flags, self._status
+        _, _, hh, ww = rect
+        mlp, kw = self.layers["dec.mlp"], dict(flags=self._dec_flags, status=self._status)
         win = ops.dec_window(rect, HH, WW)
         box = torch.empty(4, device=self.device, dtype=torch.int32)
         for t, out in zip(tvs, outs):
             hrf = self._empty(n, hh, ww, 64)
             flow = self._empty(n, hh, ww, 4)
-            ops.dec_stage1(proj, mlp, tab, t, hrf, flow, image, flags=fl, status=st, window=win)
-            ops.dec_bounds(flow, tab, box, win)
-            ymin, ymax, xmin, xmax = box.tolist()   # the device-to-host read (synchronises this stream)
-            fy0, fx0 = min(ymin, y0), min(xmin, x0)
-            frect = (fy0, fx0, max(ymax + 1, y0 + hh) - fy0, max(xmax + 1, x0 + ww) - fx0)
+            ops.dec_stage1(proj, mlp, tab, t, hrf, flow, image, window=win, **kw)
+            frect = self._window_F(flow, tab, box, win, rect)
             per = max(1, self.dec_chunk_px // (frect[2] * frect[3]))
             self.last_window_F = frect
             self.window_peak_scratch_bytes = max(self.window_peak_scratch_bytes,
                                                  min(n, per) * frect[2] * frect[3] * 272)
-            wf = ops.dec_window(rect, HH, WW, frect)
-            if frect == rect:
-                ops.dec_stage2(proj, mlp, hrf, flow, tab, t, out, image, flags=fl, status=st, window=wf)
-            else:
-                del hrf   # the caching allocator reuses it for the F buffer (same stream)
-                for a in range(0, n, per):
-                    b = min(n, a + per)
-                    img = image.items(a, b) if image is not None else None
-                    hf = self._empty(b - a, frect[2], frect[3], 64)
-                    ops.dec_stage1(proj[a:b], mlp, tab, t[a:b], hf, None, img, flags=fl, status=st,
-                                   window=ops.dec_window(frect, HH, WW))
-                    ops.dec_stage2(proj[a:b], mlp, hf, flow[a:b], tab, t[a:b], out[a:b], img, flags=fl, status=st,
-                                   window=wf)
-                    del hf
+            if frect != rect:
+                hrf = None
+            self._stage2_given_F(proj, mlp, tab, tab, t, hrf, flow, out, rect, frect, per, kw, image)
             yield
+
+    def _decode_tiles(self, tvs, B, region, rects, steps, lr_image, bits, failure):
+        """The windows ``rects`` of ``region``, each written in place into the outputs ([B,3,rh,rw] per entry of
+        ``tvs``) through its strides by ``steps(proj, tvs of the items, views, rect, a, b)`` for the items [a, b) of a
+        pass.  bits: the status bits that say a gather left its HRfeat rectangle, read back after the launches and
+        raised as ``failure`` (0: nothing is read back).  Starts ``last_window_F`` / ``window_peak_scratch_bytes``."""
+        ry, rx, rh, rw = region
+        outs = [self._empty(B, 3, rh, rw) for _ in tvs]
+        self.last_window_F, self.window_peak_scratch_bytes = None, 0
+        st = self._status if bits else None
+        if st is not None and self._dec_flags == 0:
+            st.zero_()   # fp32 operands: only the windows' bits are read below
+        per = max(1, self.dec_chunk_px // max(r[2] * r[3] for r in rects))
+
+        def tiles(proj, a, b):
+            for r in rects:
+                views = [o[a:b, :, r[0] - ry:r[0] - ry + r[2], r[1] - rx:r[1] - rx + r[3]] for o in outs]
+                yield from steps(proj, [t[a:b] for t in tvs], views, r, a, b)
+        self._decode_passes(B, per, lr_image, tiles)
+        if st is not None and int(st.item()) & bits:
+            raise L.StifError(failure)
+        return outs
 
     def _decode_windowed(self, tvs, HH, WW, tab, window, tile, image=None):
         """``decoding`` / ``decoding_test`` (image given) over ``window`` (None: the whole grid), rendered by
@@ -1103,89 +1143,56 @@ class LunaTokis(nn.Module):
         its strides.  ``last_window_F`` is the HRfeat rectangle (fy0, fx0, fh, fw) of the last window decoded and
         ``window_peak_scratch_bytes`` the largest per-pass HRfeat + flow scratch of the call (items x |F| x 272 B)."""
         if torch.cuda.is_current_stream_capturing():
-            raise L.StifError("a windowed / tiled decode reads the HRfeat bounding box back on the host: "
-                              "it cannot be captured in a hipGraph")
+            raise L.StifError(_NO_CAPTURE)
         B = self._feat.shape[1]   # every entry of tvs holds (or, a field without item stride, serves) B items
         region = check_window((0, 0, HH, WW) if window is None else window, HH, WW)
-        rects = [region] if tile is None else tile_windows(region, tile)
-        ry, rx, rh, rw = region
-        outs = [self._empty(B, 3, rh, rw) for _ in tvs]
-        self.last_window_F, self.window_peak_scratch_bytes = None, 0
-        st = self._status
-        if st is not None and self._dec_flags == 0:
-            st.zero_()   # fp32 operands: only the windows' bit 1 is read below
-        per = max(1, self.dec_chunk_px // max(r[2] * r[3] for r in rects))
 
-        def tiles(proj, a, b):
+        def steps(proj, ts, views, r, a, b):
             img = image.items(a, b) if image is not None else None
-            for r in rects:
-                views = [o[a:b, :, r[0] - ry:r[0] - ry + r[2], r[1] - rx:r[1] - rx + r[3]] for o in outs]
-                yield from self._window_steps(proj, [t[a:b] for t in tvs], HH, WW, tab, views, r, img)
-        self._decode_passes(B, per, image is None, tiles)
-        if st is not None and int(st.item()) & 2:
-            raise L.StifError("windowed decode: stage 2 gathered outside its HRfeat rectangle (stif_dec_bounds and "
-                              "stage 2 disagree): the result is wrong")
-        return outs
+            return self._window_steps(proj, ts, HH, WW, tab, views, r, img)
+        return self._decode_tiles(
+            tvs, B, region, [region] if tile is None else tile_windows(region, tile), steps, image is None, 2,
+            "windowed decode: stage 2 gathered outside its HRfeat rectangle (stif_dec_bounds and stage 2 disagree): "
+            "the result is wrong")
 
     # ------------------------------------------------------------------ local ensemble over windows
     def _ensemble_steps(self, proj, tvs, HH, WW, tabs, outs, rect):
         """The local ensemble of every query time for the window ``rect`` into ``outs`` ([n,3,hh,ww] views;
         generator).  Per time and per shift k (``tabs``: the four shifted tables in the reference's order): HRfeat
         of the shifted query over the remap rectangle R_k, which the host knows from the monotone hr_y / hr_x tables;
-        the flow over W with its HRfeat operand read at (hr_y, hr_x) from R_k; the box of stage 2's gathers;
-        F = box U R_k, and HRfeat over F if that is larger than R_k; stage 2 over W, blending w_k rgb into ``out``
-        in place (the first stores, the others accumulate -- the four launches of a window follow each other on one
-        stream, in ops.ENSEMBLE_BLEND_ORDER, the order that gives stif_dec_blend4's roundings).  One shift's HRfeat and flow are alive at a time.  A window that is the whole grid takes F = the
-        whole grid and reads nothing back."""
+        the flow over W with its HRfeat operand read at (hr_y, hr_x) from R_k; F = box U R_k (``_window_F``), and
+        HRfeat over F if that is larger than R_k; stage 2 over W, blending w_k rgb into ``out`` in place (the first
+        stores, the others accumulate -- the four launches of a window follow each other on one stream, in
+        ops.ENSEMBLE_BLEND_ORDER, the order that gives stif_dec_blend4's roundings).  One shift's HRfeat and flow
+        are alive at a time.  A window that is the whole grid takes F = the whole grid and reads nothing back."""
         n = proj.shape[0]
-        y0, x0, hh, ww = rect
+        _, _, hh, ww = rect
         whole = rect == (0, 0, HH, WW)
-        mlp, fl, st = self.layers["dec.mlp"], self._dec_flags, self._status
+        mlp, kw = self.layers["dec.mlp"], dict(flags=self._dec_flags, status=self._status)
         win = ops.dec_window(rect, HH, WW)
-        blends = {k: ops.dec_blend(k, tabs, accumulate=i > 0) for i, k in enumerate(ops.ENSEMBLE_BLEND_ORDER)}
+        blends ={k: ops.dec_blend(k, tabs, accumulate=i > 0) for i, k in enumerate(ops.ENSEMBLE_BLEND_ORDER)}
         box = None if whole else torch.empty(4, device=self.device, dtype=torch.int32)
-
-        def hrfeat(tab, frect, a, b, t):   # feat_imnet at the shifted query over frect, items [a, b)
-            hf = self._empty(b - a, frect[2], frect[3], 64)
-            ops.dec_stage1(proj[a:b], mlp, tab.plain, t[a:b], hf, None, flags=fl, status=st,
-                           window=ops.dec_window(frect, HH, WW))
-            return hf
-
         for t, out in zip(tvs, outs):
             largest = None
             for k in ops.ENSEMBLE_BLEND_ORDER:
                 tab = tabs[k]
                 rrect = rect if whole else tab.remap_rect(rect)
                 flow = self._empty(n, hh, ww, 4)
-                hrf = hrfeat(tab, rrect, 0, n, t)
-                ops.dec_flow_win(proj, mlp, tab, t, hrf, flow, flags=fl, status=st,
-                                 window=ops.dec_window(rect, HH, WW, rrect))
-                frect = rrect
-                if not whole:
-                    ops.dec_bounds(flow, tab, box, win)
-                    ymin, ymax, xmin, xmax = box.tolist()   # the device-to-host read (synchronises this stream)
-                    fy0, fx0 = min(ymin, rrect[0]), min(xmin, rrect[1])
-                    frect = (fy0, fx0, max(ymax + 1, rrect[0] + rrect[2]) - fy0,
-                             max(xmax + 1, rrect[1] + rrect[3]) - fx0)
+                hrf = self._empty(n, rrect[2], rrect[3], 64)   # feat_imnet at the shifted query over R_k
+                ops.dec_stage1(proj, mlp, tab.plain, t, hrf, None, window=ops.dec_window(rrect, HH, WW), **kw)
+                ops.dec_flow_win(proj, mlp, tab, t, hrf, flow, window=ops.dec_window(rect, HH, WW, rrect), **kw)
+                frect = rrect if whole else self._window_F(flow, tab, box, win, rrect)
                 per = max(1, self.dec_chunk_px // (frect[2] * frect[3]))
                 if largest is None or frect[2] * frect[3] > largest[2] * largest[3]:
                     largest = frect
                 self.window_peak_scratch_bytes = max(
                     self.window_peak_scratch_bytes, n * (rrect[2] * rrect[3] * 256 + hh * ww * 16),
                     min(n, per) * frect[2] * frect[3] * 256 + n * hh * ww * 16)
-                wf = ops.dec_window(rect, HH, WW, frect)
-                if frect == rrect:
-                    ops.dec_stage2(proj, mlp, hrf, flow, tab, t, out, flags=fl, status=st, window=wf, blend=blends[k])
-                    del hrf
-                else:
-                    del hrf   # the caching allocator reuses it for the F buffer (same stream)
-                    for a in range(0, n, per):
-                        b = min(n, a + per)
-                        hf = hrfeat(tab, frect, a, b, t)
-                        ops.dec_stage2(proj[a:b], mlp, hf, flow[a:b], tab, t[a:b], out[a:b], flags=fl, status=st,
-                                       window=wf, blend=blends[k])
-                        del hf
-                del flow
+                if frect != rrect:
+                    hrf = None
+                self._stage2_given_F(proj, mlp, tab, tab.plain, t, hrf, flow, out, rect, frect, per, kw,
+                                     blend=blends[k])
+                del hrf, flow
             self.last_window_F = largest
             yield
 
@@ -1197,29 +1204,17 @@ class LunaTokis(nn.Module):
         B = tvs[0].shape[0] if tvs else self._feat.shape[1]
         region = check_window((0, 0, HH, WW) if window is None else window, HH, WW)
         rects = [region] if tile is None else tile_windows(region, tile)
+        # with F the whole grid no index can leave it: nothing to read back, and the call may be being captured
         whole = rects == [(0, 0, HH, WW)]
         if not whole and torch.cuda.is_current_stream_capturing():
-            raise L.StifError("a windowed / tiled decode reads the HRfeat bounding box back on the host: "
-                              "it cannot be captured in a hipGraph")
+            raise L.StifError(_NO_CAPTURE)
         tabs = [self._tab(H, Wd, HH, WW, s) for s in ops.ENSEMBLE_SHIFTS]
-        ry, rx, rh, rw = region
-        outs = [self._empty(B, 3, rh, rw) for _ in tvs]
-        self.last_window_F, self.window_peak_scratch_bytes = None, 0
-        st = self._status
-        if st is not None and self._dec_flags == 0 and not whole:
-            st.zero_()   # fp32 operands: only the windows' bits 1 and 2 are read below
-        per = max(1, self.dec_chunk_px // max(r[2] * r[3] for r in rects))
-
-        def tiles(proj, a, b):
-            for r in rects:
-                views = [o[a:b, :, r[0] - ry:r[0] - ry + r[2], r[1] - rx:r[1] - rx + r[3]] for o in outs]
-                yield from self._ensemble_steps(proj, [t[a:b] for t in tvs], HH, WW, tabs, views, r)
-        self._decode_passes(B, per, True, tiles)
-        # with F the whole grid no index can leave it: nothing to read back (the call may be being captured)
-        if st is not None and not whole and int(st.item()) & 6:
-            raise L.StifError("windowed ensemble decode: a gather left its HRfeat rectangle (the remap rectangle or "
-                              "stif_dec_bounds disagrees with the kernels): the result is wrong")
-        return outs
+        return self._decode_tiles(
+            tvs, B, region, rects,
+            lambda proj, ts, views, r, a, b: self._ensemble_steps(proj, ts, HH, WW, tabs, views, r), True,
+            0 if whole else 6,
+            "windowed ensemble decode: a gather left its HRfeat rectangle (the remap rectangle or stif_dec_bounds "
+            "disagrees with the kernels): the result is wrong")
 
     def decoding_window(self, times=None, scale=None, center=(0.0, 0.0), size=None):
         """The reference's zoom call (decoding_memory, Sakuya_arch_test.py:600-861): the ``size`` (default 4H x 4W)

@@ -350,6 +350,11 @@ class DecTablesDev:
             # the remap rectangle of a window is known on the host: the tables are monotone
             self.hr_y, self.hr_x = tab["hr_y"], tab["hr_x"]
 
+    @property
+    def shifted(self):
+        """These tables carry the remap (hr_y / hr_x) of a shifted query; ``plain`` never does."""
+        return "hr_y" in self._t and bool(self.c.hr_y)
+
     def remap_rect(self, rect):
         """The rectangle (y0, x0, hh, ww) of HR pixels whose HRfeat the flow stage of a shifted query reads for the
         window ``rect``: [hr_y[y0], hr_y[y0 + hh - 1]] x [hr_x[x0], hr_x[x0 + ww - 1]]."""
@@ -478,7 +483,7 @@ class DecTime:
 
 
 def _time_field_call(t, n, image, tables, what):
-    if image is not None or "hr_y" in tables._t and tables.c.hr_y:
+    if image is not None or tables.shifted:
         raise ValueError(f"{what}: a time field has no high-resolution-image and no local-ensemble form")
     if t.n is not None and t.n != n:
         raise ValueError(f"{what}: the time field holds {t.n} items, the call has {n}")
@@ -487,31 +492,36 @@ def _time_field_call(t, n, image, tables, what):
         raise ValueError(f"{what}: a time field over {t.grid} does not broadcast to the {HH} x {WW} grid")
 
 
+def _stage_entry(stage, t, window, blend=None):
+    """(entry name for errors, library function, time argument, trailing arguments) of decoder stage ``stage`` for
+    the time ``t`` (an [n] tensor or a DecTime), a window and a blend (either may be None)."""
+    win = C.byref(window) if window is not None else None
+    if isinstance(t, DecTime):
+        what, targ, tail = f"stif_dec_stage{stage}_tf", C.byref(t.c), (win,)
+    elif blend is not None:
+        what, targ, tail = "stif_dec_stage2_blend_win", _vp(t), (C.byref(blend), win)
+    elif window is not None:
+        what, targ, tail = f"stif_dec_stage{stage}_win", _vp(t), (win,)
+    else:
+        return f"stif_dec_stage{stage}", getattr(L.lib(), f"stif_dec_stage{stage}_ex"), _vp(t), ()
+    return what, getattr(L.lib(), what), targ, tail
+
+
 def dec_stage1(proj, mlp, tables: DecTablesDev, t, hrfeat, flow, image: "DecImageDev" = None, flags=0, status=None,
                window: L.DecWindow = None):
     """window (dec_window): the stage over that rectangle of the tables' grid -- flow [n, hh, ww, 4] (None: HRfeat
     only), hrfeat over the window's F rectangle.  t: the [n] time tensor, or a DecTime (a time per pixel of the
     tables' grid; no image, no shifted tables)."""
     n, h, w, _ = proj.shape
-    trace = None
     if isinstance(t, DecTime):
         _time_field_call(t, n, image, tables, "dec_stage1")
-        HH, WW = _win_shapes(window, tables, n, hrfeat, flow) if window is not None else hrfeat.shape[1:3]
-        if window is None and TRACE is not None:
-            trace = (("dec1",), 2.0 * 62464 * n * HH * WW)
-        _launch("stif_dec_stage1_tf", trace, L.lib().stif_dec_stage1_tf, _vp(proj), _vp(mlp), C.byref(tables.c), None,
-                C.byref(t.c), _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream(),
-                C.byref(window) if window is not None else None)
-        return
-    if window is not None:
-        HH, WW = _win_shapes(window, tables, n, hrfeat, flow)
-        what, fn, tail = "stif_dec_stage1_win", L.lib().stif_dec_stage1_win, (C.byref(window),)
-    else:
-        HH, WW = hrfeat.shape[1:3]
-        what, fn, tail = "stif_dec_stage1", L.lib().stif_dec_stage1_ex, ()
-        if TRACE is not None:   # per HR px: feat_imnet layers 1-3 (36,864 MAC) + flow_imnet HRfeat/1-3 (25,600 MAC)
-            trace = (("dec1",), 2.0 * 62464 * n * HH * WW)
-    _launch(what, trace, fn, _vp(proj), _vp(mlp), C.byref(tables.c), C.byref(image.c) if image else None, _vp(t),
+    HH, WW = _win_shapes(window, tables, n, hrfeat, flow) if window is not None else hrfeat.shape[1:3]
+    trace = None
+    if window is None and TRACE is not None:
+        # per HR px: feat_imnet layers 1-3 (36,864 MAC) + flow_imnet HRfeat/1-3 (25,600 MAC)
+        trace = (("dec1",), 2.0 * 62464 * n * HH * WW)
+    what, fn, targ, tail = _stage_entry(1, t, window)
+    _launch(what, trace, fn, _vp(proj), _vp(mlp), C.byref(tables.c), C.byref(image.c) if image else None, targ,
             _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream(), *tail)
 
 
@@ -550,11 +560,10 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
     blend (dec_blend; needs a window, no image): the local ensemble's epilogue -- w_k rgb is stored, or added to
     what ``out`` holds (blend.accumulate)."""
     n, h, w, _ = proj.shape
-    trace = None
+    trace = win = None
     if blend is not None and (window is None or image is not None):
         raise ValueError("dec_stage2: the blending epilogue is the windowed stage's, without a high-resolution image")
-    tf = isinstance(t, DecTime)
-    if tf:
+    if isinstance(t, DecTime):
         _time_field_call(t, n, image, tables, "dec_stage2")
         if blend is not None:
             raise ValueError("dec_stage2: a time field has no blending (local-ensemble) form")
@@ -564,21 +573,13 @@ def dec_stage2(proj, mlp, hrfeat, flow, tables: DecTablesDev, t, out, image: "De
             raise ValueError(f"dec_stage2: out must be {(n, 3, window.hh, window.ww)} with unit column stride")
         win = L.DecWindow.from_buffer_copy(window)
         win.out_item, win.out_plane, win.out_pitch = out.stride(0), out.stride(1), out.stride(2)
-        what, fn, tail = "stif_dec_stage2_win", L.lib().stif_dec_stage2_win, (C.byref(win),)
-        if tf:
-            what, fn = "stif_dec_stage2_tf", L.lib().stif_dec_stage2_tf
-        if blend is not None:
-            what, fn, tail = "stif_dec_stage2_blend_win", L.lib().stif_dec_stage2_blend_win, (C.byref(blend), C.byref(win))
     else:
         HH, WW = hrfeat.shape[1:3]
-        what, fn, tail = "stif_dec_stage2", L.lib().stif_dec_stage2_ex, ()
-        if tf:
-            what, fn, tail = "stif_dec_stage2_tf", L.lib().stif_dec_stage2_tf, (None,)
         if TRACE is not None:   # per HR px: encode_imnet HRfeat part + layers 1-4 (94,976 MAC)
             trace = (("dec2",), 2.0 * 94976 * n * HH * WW)
+    what, fn, targ, tail = _stage_entry(2, t, win, blend)
     _launch(what, trace, fn, _vp(proj), _vp(mlp), _vp(hrfeat), _vp(flow), C.byref(tables.c),
-            C.byref(image.c) if image else None, C.byref(t.c) if tf else _vp(t), _vp(out), n, h, w, HH, WW, flags,
-            _vp(status), _stream(), *tail)
+            C.byref(image.c) if image else None, targ, _vp(out), n, h, w, HH, WW, flags, _vp(status), _stream(), *tail)
 
 
 class DecPoints:
@@ -611,7 +612,7 @@ class DecPoints:
 
 
 def _points_call(pts, n, tables, what):
-    if "hr_y" in tables._t and tables.c.hr_y:
+    if tables.shifted:
         raise ValueError(f"{what}: a point list has no local-ensemble form")
     if pts.n is not None and pts.n != n:
         raise ValueError(f"{what}: the point list holds {pts.n} items, the call has {n}")
