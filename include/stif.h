@@ -485,6 +485,37 @@ int stif_dec_stage2_pts(const float* proj, const float* mlp, const float* hrfeat
                         const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h, int w,
                         int HH, int WW, int flags, int* status, void* stream);
 
+/* ---- local ensemble at points: point (item i, row y, column x, time t) is bit for bit what the four-shift
+ * sequence above (stif_dec_stage2_blend_win over the whole grid with the per-item time t) leaves at [i][:][y][x].
+ * Per shift k, in the launch order of stif_dec_stage2_blend_win, on one stream, with tab_k the tables of shift k and
+ * plain_k the same without hr_y / hr_x: stif_dec_remap_pts (tab_k) -> stif_dec_stage1_pts (plain_k, the list
+ * {ry, rx, t}, flow = NULL: the compact HRfeat operand [n][npts][64]) -> stif_dec_flow_pts (tab_k) ->
+ * stif_dec_corners_pts (plain_k) -> stif_dec_stage1_pts over the corner list (plain_k, flow = NULL) ->
+ * stif_dec_stage2_blend_pts (tab_k).  One shift's scratch is alive at a time; nothing is read back.
+ * The three entry points return STIF_E_INVALID, with the reason in stif_last_error, for a null pointer, npts < 1,
+ * n * 8 * npts beyond INT_MAX and a negative stride; y / x are clamped and flagged (bit 3) as above. ---- */
+
+/* ry[i][p] = hr_y[y], rx[i][p] = hr_x[x] at point p's clamped row / column, both int32 [n][npts]: the HR pixel whose
+ * HRfeat row the flow stage of the shifted query reads.  {ry, rx, t, npts, npts, t_item, t_point, npts} (t and its
+ * strides the point list's) is the stif_dec_points of the feat-only pass that computes those rows.  Tables without
+ * hr_y / hr_x are STIF_E_INVALID. */
+int stif_dec_remap_pts(const stif_dec_tables* tab, const stif_dec_points* pts, int* ry, int* rx, int n, int HH, int WW,
+                       int* status, void* stream);
+/* flow_imnet alone over the points, with the tables of a shifted query (hr_y / hr_x required, as stif_dec_flow_win;
+ * they are not read): the HRfeat operand of point p of item i is row [i][p] of hrfeat [n][npts][64].  flow:
+ * [n][npts][4], each point's bit-identical to stif_dec_stage1_ex's flow with the same tables at its pixel and time. */
+int stif_dec_flow_pts(const float* proj, const float* mlp, const stif_dec_tables* tab, const stif_dec_points* pts,
+                      const float* hrfeat, float* flow, int n, int h, int w, int HH, int WW, int flags, int* status,
+                      void* stream);
+/* stif_dec_stage2_pts with the local ensemble's blending epilogue (stif_dec_blend, the arithmetic and the launch
+ * order of stif_dec_stage2_blend_win): the weight is taken at the point's clamped row / column of the virtual grid.
+ * The tables of a shifted query are accepted (hr_y / hr_x are never read).  out [n][3][npts], each element written
+ * by one lane (no atomics).  STIF_E_INVALID also for a bad blend: NULL, k outside 0..3, accumulate outside 0 / 1, a
+ * null rel table.  Status bits as stif_dec_stage2_pts. */
+int stif_dec_stage2_blend_pts(const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
+                              const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n, int h, int w,
+                              int HH, int WW, int flags, int* status, void* stream, const stif_dec_blend* blend);
+
 /* ---- evaluation: PSNR / SSIM of decoded frames against ground truth (myutils.py:1151-1174, util.py:105-174) ---- */
 
 /* stif_metric_args.flags */

@@ -163,6 +163,11 @@ EXPORTS = {
                              + [C.c_int] * 3 + [_P, _P]),
     "stif_dec_stage2_pts": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecPointList), _P]
                             + [C.c_int] * 6 + [_P, _P]),
+    "stif_dec_remap_pts": (C.c_int, [C.POINTER(DecTables), C.POINTER(DecPointList), _P, _P] + [C.c_int] * 3 + [_P, _P]),
+    "stif_dec_flow_pts": (C.c_int, [_P, _P, C.POINTER(DecTables), C.POINTER(DecPointList), _P, _P]
+                          + [C.c_int] * 6 + [_P, _P]),
+    "stif_dec_stage2_blend_pts": (C.c_int, [_P, _P, _P, _P, C.POINTER(DecTables), C.POINTER(DecPointList), _P]
+                                  + [C.c_int] * 6 + [_P, _P, C.POINTER(DecBlend)]),
     "stif_dec_blend4": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "stif_upsample_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "stif_resize_frames": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int,

@@ -362,13 +362,14 @@ STIF_DEV float blend_weight(const stif_dec_blend& bl, int gy, int gx) {
 // `r = p0 w0; r += p1 w1` into fma(p0, w0, p1 * w1): its one rounded product is decode 1's, then come the fmas of
 // decodes 0, 2 and 3 -- so launching the decodes in the order 1, 0, 2, 3 reproduces its bits (model.py does).
 // The pixel's lane owns its three output elements: no atomics.
-// PTS: the caller passes the [n][3][npts] output as a one-row grid (py = 0, px = the point, HH = 1, WW = npts).
+// PTS: the caller passes the [n][3][npts] output as a one-row grid (py = 0, px = the point, HH = 1, WW = npts) and,
+// BLEND, the point's clamped row / column of the virtual grid (gy, gx), where its weight is taken.
 template <int FORM, bool REPORT, bool BLEND = false>
 STIF_DEV void store_rgb(float* __restrict__ out, const float* __restrict__ mlp, const float* o4, const f32x4 fv,
                         int item, int py, int px, int HH, int WW, const stif_dec_window& win, int* status,
-                        const stif_dec_blend& bl) {
+                        const stif_dec_blend& bl, int gy = 0, int gx = 0) {
   constexpr bool WIN = FORM == WINDOW;
-  static_assert(WIN || !BLEND, "the blending epilogue is the windowed stages'");
+  static_assert(FORM != GRID || !BLEND, "the blending epilogue is the windowed and the point stages'");
   const size_t plane = WIN ? (size_t)win.out_plane : (size_t)HH * WW;
   float* o = WIN ? out + (size_t)item * win.out_item + (size_t)py * win.out_pitch + px
                  : out + (size_t)item * 3 * plane + (size_t)py * WW + px;
@@ -381,7 +382,7 @@ STIF_DEV void store_rgb(float* __restrict__ out, const float* __restrict__ mlp, 
     if constexpr (!BLEND) o[c * plane] = rgb[c];
   }
   if constexpr (BLEND) {
-    const float wk = blend_weight(bl, win.y0 + py, win.x0 + px);
+    const float wk = WIN ? blend_weight(bl, win.y0 + py, win.x0 + px) : blend_weight(bl, gy, gx);
     if (!bl.accumulate) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) o[c * plane] = __fmul_rn(rgb[c], wk);
@@ -495,6 +496,9 @@ constexpr int S1 = OCC1<MODE, HRIMG> == 4 ? 4 : OCC1<MODE, HRIMG> == 3 ? 6 : SEG
 // FORM PTS (MODE 0 / 1, no HR image): the pixels are the points of tq, a stif_dec_points, each with its own time;
 // HRfeat and flow are stored at the point's running index, the whole-grid layout over the point list; a row /
 // column clamped into the grid is reported as bit 3 of *status (pixel_of).
+// PTS and MODE 2 (the local ensemble's flow stage at the points, tb a shifted query's): hrfeat is the compact
+// [n][npts][64] operand, row [item][pt] the HRfeat of the point's remapped pixel (k_dec_remap and a feat-only pass over
+// the remapped list made it), so hr_y / hr_x are not read here.
 template <int MODE, bool HRIMG, int F16, int FORM, bool TF = false>
 __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<MODE, HRIMG>))) void k_dec1(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      stif_dec_tables tb, stif_dec_image im,
@@ -505,7 +509,7 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
   constexpr int TQ = TQK<FORM, TF>;
   static_assert(!(WIN && MODE == 2 && HRIMG), "the windowed flow-only stage takes no high-resolution image");
   static_assert(!TF || (MODE != 2 && !HRIMG), "a time field has no local-ensemble and no HR-image form");
-  static_assert(FORM != PTS || (MODE != 2 && !HRIMG && !TF), "a point list has no local-ensemble and no HR-image form");
+  static_assert(FORM != PTS || (!HRIMG && !TF), "a point list has no HR-image and no time-field form");
   // two segment buffers of SEG1 tiles + the flow's last layer (plain [4][256], resident)
   constexpr bool OCC3 = S1<MODE, HRIMG> != SEG1;             // 3 or 4 workgroups per CU
   constexpr bool OCC4 = OCC1<MODE, HRIMG> == 4;
@@ -627,7 +631,9 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
     // the query's HRfeat operand: the HR pixel nearest to the shifted query (grid_sample nearest
     // of HRfeat at coord_, Sakuya_arch_test.py:1022-1025)
     Bilin b;
-    if constexpr (WIN) {
+    if constexpr (FORM == PTS) {
+      b.o00 = b.o01 = b.o10 = b.o11 = pix.pt;
+    } else if constexpr (WIN) {
       const int ry = tb.hr_y[py] - win.fy0, rx = tb.hr_x[px] - win.fx0;
       const int y = min(max(ry, 0), win.fh - 1), x = min(max(rx, 0), win.fw - 1);
       if (status != nullptr && (y != ry || x != rx)) atomicOr(status, 4);
@@ -637,7 +643,10 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
     }
     b.w00 = 1.f;
     b.w01 = b.w10 = b.w11 = 0.f;
-    gather64<8>(hr, hrfeat + (size_t)item * (WIN ? (size_t)win.fh * win.fw : (size_t)HH * WW) * 64, 64, 0, b, hf);
+    if constexpr (FORM == PTS)
+      gather64<8>(hr, hrfeat + (size_t)item * tq.npts * 64, 64, 0, b, hf);
+    else
+      gather64<8>(hr, hrfeat + (size_t)item * (WIN ? (size_t)win.fh * win.fw : (size_t)HH * WW) * 64, 64, 0, b, hf);
   }
 
   // ---- flow_imnet layer 0: W[:, :64] . HRfeat + bilinear(P2 at the HR centre) + w_t * t + b
@@ -736,7 +745,7 @@ __global__ __launch_bounds__(NW1 * 64) __attribute__((amdgpu_waves_per_eu(OCC1<M
 // rectangle (bilin_hr) and the RGB goes through win's output addressing.
 // FORM PTS: the pixels are the points of tq (flow at the point's index, the linspace base at its clamped row /
 // column, its own time), hrfeat holds the points' corner rows [n][npts][8][64] (bilin_hr) and the RGB goes to
-// out[item][c][point].
+// out[item][c][point] -- BLEND: blended into it with the weight at the point's clamped row / column (store_rgb).
 template <bool HRIMG, int F16, int FORM, bool BLEND = false, bool TF = false>   // TF: as k_dec1's
 __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DEC2_WPE))) void k_dec2(const float* __restrict__ proj, const float* __restrict__ mlp,
                                                      const float* __restrict__ hrfeat, const float* __restrict__ flow,
@@ -747,7 +756,7 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
   constexpr bool WIN = FORM == WINDOW;
   constexpr int TQ = TQK<FORM, TF>;
   static_assert(!TF || (!HRIMG && !BLEND), "a time field has no HR-image and no blending form");
-  static_assert(FORM != PTS || (!HRIMG && !BLEND && !TF), "a point list has no HR-image and no blending form");
+  static_assert(FORM != PTS || (!HRIMG && !TF), "a point list has no HR-image and no time-field form");
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEG * T];
   const int lane = threadIdx.x & 63, hf = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
@@ -872,7 +881,8 @@ __global__ __launch_bounds__(DEC2_NW * 64) __attribute__((amdgpu_waves_per_eu(DE
 #pragma unroll
   for (int c = 0; c < 3; ++c) o4[c] += __shfl_xor(o4[c], 32);   // the other lane half's 128 features
   if (pix.valid && hf == 0) {
-    if constexpr (FORM == PTS) store_rgb<PTS, F16 != 0>(out, mlp, o4, fv, item, 0, pix.pt, 1, tq.npts, win, status, bl);
+    if constexpr (FORM == PTS)
+      store_rgb<PTS, F16 != 0, BLEND>(out, mlp, o4, fv, item, 0, pix.pt, 1, tq.npts, win, status, bl, pix.ly, pix.lx);
     else store_rgb<FORM, F16 != 0, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
   }
 }
@@ -966,7 +976,7 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
   constexpr bool WIN = FORM == WINDOW;
   constexpr int TQ = TQK<FORM, TF>;
   static_assert(!TF || !BLEND, "a time field has no blending form");
-  static_assert(FORM != PTS || (!BLEND && !TF), "a point list has no blending form");
+  static_assert(FORM != PTS || !TF, "a point list has no time-field form");
   __shared__ __attribute__((aligned(16))) float wbuf[2 * SEGQ * T];
   const int lane = threadIdx.x & 63, q = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1104,7 +1114,8 @@ __global__ __launch_bounds__(DEC2Q_NW * 64) __attribute__((amdgpu_waves_per_eu(4
     o4[c] += __shfl_xor(o4[c], 32);
   }
   if (pix.valid && q == 0) {
-    if constexpr (FORM == PTS) store_rgb<PTS, true>(out, mlp, o4, fv, item, 0, pix.pt, 1, tq.npts, win, status, bl);
+    if constexpr (FORM == PTS)
+      store_rgb<PTS, true, BLEND>(out, mlp, o4, fv, item, 0, pix.pt, 1, tq.npts, win, status, bl, pix.ly, pix.lx);
     else store_rgb<FORM, true, BLEND>(out, mlp, o4, fv, item, py, px, HH, WW, win, status, bl);
   }
 }
@@ -1169,6 +1180,22 @@ __global__ __launch_bounds__(256) void k_dec_corners(const float* __restrict__ f
       cx[p * 8 + k] = (k & 1) ? a.cx1 : a.cx0;
       ct[p * 8 + k] = t;
     }
+  }
+}
+
+// k_dec_remap: the HR pixel whose HRfeat row the flow stage of a shifted query reads for every point (grid_sample
+// nearest of HRfeat at the shifted coordinate: tb.hr_y / hr_x at the point's clamped row / column), as the row /
+// column lists of the feat-only pass that computes those rows.  The tables hold indices of the grid, so the lists need
+// no clamp of their own.
+__global__ __launch_bounds__(256) void k_dec_remap(stif_dec_tables tb, stif_dec_points pts, int* __restrict__ ry,
+                                                   int* __restrict__ rx, long long total, int HH, int WW,
+                                                   int* status) {
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
+    const int item = (int)(p / pts.npts), pt = (int)(p - (long long)item * pts.npts);
+    int y, x;
+    point_yx(pts, item, pt, HH, WW, status, y, x);
+    ry[p] = tb.hr_y[y];
+    rx[p] = tb.hr_x[x];
   }
 }
 
@@ -1294,12 +1321,15 @@ const char* time_field_invalid(const stif_dec_tables* tab, const stif_dec_image*
 }
 
 // the reason a point call is invalid after its generic argument check, or null
-const char* points_invalid(const stif_dec_tables* tab, const stif_dec_points* p, int n, int HH, int WW) {
+// shifted: the entry point takes the tables of a shifted query (the local ensemble's point stages)
+const char* points_invalid(const stif_dec_tables* tab, const stif_dec_points* p, int n, int HH, int WW,
+                           bool shifted = false) {
   if (!p || !p->y || !p->x || !p->t) return "null point list (pts or its y, x or t)";
   if (p->npts < 1) return "npts < 1";
   if (p->y_item < 0 || p->x_item < 0 || p->t_item < 0 || p->t_point < 0) return "negative point stride";
   if (n >= 1 && (long long)n * 8 * p->npts > INT_MAX) return "n * 8 * npts exceeds INT_MAX";
-  if (tab && (tab->hr_y || tab->hr_x)) return "tables with hr_y / hr_x (local ensemble) have no point form";
+  if (!shifted && tab && (tab->hr_y || tab->hr_x))
+    return "tables with hr_y / hr_x (local ensemble) have no point form";
   if (HH < 2 || WW < 2 || (long long)HH * WW > INT_MAX) return "bad virtual grid size";
   return nullptr;
 }
@@ -1327,7 +1357,7 @@ struct Query {
   TimeQ time;
   bool windowed = false;                 // the pixels are win's query rectangle (a point list is never windowed)
   const stif_dec_window* win = nullptr;
-  bool flow_only = false;                // stage 1: the windowed flow-only stage of a shifted query (MODE 2 over F)
+  bool flow_only = false;                // stage 1: the flow-only stage of a shifted query (MODE 2 over F / the points)
   bool blending = false;                 // stage 2: the local ensemble's epilogue, as `blend` says
   const stif_dec_blend* blend = nullptr;
   int form() const { return time.kind == 2 ? PTS : windowed ? WINDOW : GRID; }
@@ -1342,7 +1372,7 @@ const char* pixels_of(const Query& q, const stif_dec_tables* tab, int n, int HH,
                       long long* total) {
   *wn = stif_dec_window{};
   if (q.form() == PTS) {
-    if (const char* why = points_invalid(tab, q.time.pts, n, HH, WW)) return why;
+    if (const char* why = points_invalid(tab, q.time.pts, n, HH, WW, q.flow_only || q.blending)) return why;
     *total = (long long)n * q.time.pts->npts;
   } else if (q.form() == WINDOW) {
     if (const char* why = window_resolve(q.win, HH, WW, wn)) return why;
@@ -1356,10 +1386,11 @@ const char* pixels_of(const Query& q, const stif_dec_tables* tab, int n, int HH,
 
 // The instantiations the entry points can reach; the rest the kernels' static_asserts refuse, or nothing asks for.
 constexpr bool variant_exists(int form, bool blend, bool tf) {
-  return !(tf && form == PTS) && (!blend || (form == WINDOW && !tf));
+  return !(tf && form == PTS) && (!blend || (form != GRID && !tf));
 }
 constexpr bool dec1_exists(int mode, bool hrimg, int form, bool tf) {
-  if (tf || form == PTS) return variant_exists(form, false, tf) && mode != 2 && !hrimg;
+  if (form == PTS) return !tf && !hrimg;   // MODE 2: the local ensemble's flow stage over the compact operand
+  if (tf) return mode != 2 && !hrimg;
   // the whole grid's feat-only pass is the first half of the remapped stage, which takes the image in its second
   return form == WINDOW ? !(mode == 2 && hrimg) : !(mode == 1 && hrimg);
 }
@@ -1371,7 +1402,8 @@ constexpr bool dec2_exists(bool hrimg, bool f16, int form, bool blend, bool tf) 
 // Stage 1.  A null flow is the feat-only pass (MODE 1), which the plain and the flow-only stage do not have.
 // flow_only: flow_imnet over the query rectangle, its HRfeat operand the row of HR pixel (hr_y, hr_x) in the F
 // layout; F need not hold the query rectangle, only the remap rectangle -- which the kernel enforces (clamp + bit 2
-// of *status), since the tables live on the device.
+// of *status), since the tables live on the device.  flow_only over a point list: the operand of point p is row
+// [item][p] of the compact hrfeat; the shifted tables are required as for the window and their remap is not read.
 int dec_stage1(const Query& q, const float* proj, const float* mlp, const stif_dec_tables* tab,
                const stif_dec_image* img, float* hrfeat, float* flow, int n, int h, int w, int HH, int WW, int flags,
                int* status, void* stream) {
@@ -1577,6 +1609,40 @@ extern "C" int stif_dec_corners_pts(const float* flow, const stif_dec_tables* ta
   hipLaunchKernelGGL(k_dec_corners, dim3(blocks), dim3(256), 0, (hipStream_t)stream, flow, *tab, *pts, cy, cx, ct,
                      total, HH, WW, status);
   return stif_check_launch(me);
+}
+
+// ---- the local ensemble at points: remap -> stif_dec_stage1_pts over the remapped list -> flow -> corners and their
+// HRfeat (the plain point entry points) -> blending stage 2, per shift
+extern "C" int stif_dec_remap_pts(const stif_dec_tables* tab, const stif_dec_points* pts, int* ry, int* rx, int n,
+                                  int HH, int WW, int* status, void* stream) {
+  static const char* const me = "stif_dec_remap_pts";
+  if (!tables_ok(tab) || !ry || !rx || n < 1) return window_fail(me, "bad arguments (null pointer or n < 1)");
+  if (!tab->hr_y || !tab->hr_x) return window_fail(me, "the tables carry no hr_y / hr_x remap (local ensemble)");
+  if (const char* why = points_invalid(tab, pts, n, HH, WW, true)) return window_fail(me, why);
+  const long long total = (long long)n * pts->npts;
+  const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_dec_remap, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *tab, *pts, ry, rx, total, HH, WW,
+                     status);
+  return stif_check_launch(me);
+}
+
+extern "C" int stif_dec_flow_pts(const float* proj, const float* mlp, const stif_dec_tables* tab,
+                                 const stif_dec_points* pts, const float* hrfeat, float* flow, int n, int h, int w,
+                                 int HH, int WW, int flags, int* status, void* stream) {
+  Query q{"stif_dec_flow_pts", pts};
+  q.flow_only = true;
+  return dec_stage1(q, proj, mlp, tab, nullptr, const_cast<float*>(hrfeat), flow, n, h, w, HH, WW, flags, status,
+                    stream);
+}
+
+extern "C" int stif_dec_stage2_blend_pts(const float* proj, const float* mlp, const float* hrfeat8, const float* flow,
+                                         const stif_dec_tables* tab, const stif_dec_points* pts, float* out, int n,
+                                         int h, int w, int HH, int WW, int flags, int* status, void* stream,
+                                         const stif_dec_blend* blend) {
+  Query q{"stif_dec_stage2_blend_pts", pts};
+  q.blending = true;
+  q.blend = blend;
+  return dec_stage2(q, proj, mlp, hrfeat8, flow, tab, nullptr, out, n, h, w, HH, WW, flags, status, stream);
 }
 
 extern "C" int stif_dec_bounds(const float* flow, const stif_dec_tables* tab, int* box, int n, int HH, int WW,

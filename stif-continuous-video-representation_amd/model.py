@@ -922,7 +922,7 @@ class LunaTokis(nn.Module):
             self._feat, self.inp = feat, inp
 
     # ------------------------------------------------------------------ point queries
-    def decoding_points(self, y, x, times, scale=None, pairs=None, return_flow=False):
+    def decoding_points(self, y, x, times, scale=None, pairs=None, return_flow=False, ensemble=False):
         """The decode at a set of points: [B, 3, n] float32 on the device, unclamped, in the order given -- point p
         of item b is, bit for bit, ``decoding([t], scale)[0][b, :, y, x]`` with that point's scalar time t.  With
         ``return_flow`` also stage 1's flow [B, 4, n] in HR pixels.
@@ -943,11 +943,25 @@ class LunaTokis(nn.Module):
         read back: the kernels clamp them into the grid and flag it, the flag is read once after the launches
         (IndexError) -- not while the stream is being captured and not with range_check='off', when valid indices
         are the caller's responsibility (they are still clamped).  ``pairs``: as ``decoding_pairs`` -- only those
-        items of the latent, B = len(pairs)."""
+        items of the latent, B = len(pairs).
+
+        ``ensemble=True``: the points of the local ensemble instead -- point p of item b is, bit for bit,
+        ``decoding([t], scale, ensemble=True)[0][b, :, y, x]`` (``decoding_localensemble``'s pixel).  The four
+        shifted decodes run one after the other over the points, each blended into the output by its weight at the
+        point (``_ensemble_points``); a point then costs 36 feat_imnet evaluations, four flow and four encode stages.
+        Every argument form, the index checks and the capture rule are those above; ``return_flow`` is a ValueError
+        (there are four flows and none of them is the flow).  Measured on the C0 latent (six items, 512 x 512 grid,
+        DESIGN.md section 3e'''): 4,096 points per item take 0.738 ms (0.732 .. 0.756) against 7.752 ms
+        (7.677 .. 7.959) of the full ensemble decode followed by an index, 65,536 take 5.822 (5.693 .. 5.975)
+        against 7.865 (7.781 .. 7.950), and the full ensemble decode wins above about 90,000 points per item, a
+        third of the grid (7.198 against 7.873 ms at 81,920, 8.481 against 7.703 at 98,304)."""
+        if ensemble and return_flow:
+            raise ValueError("decoding_points: return_flow has no meaning with ensemble=True (the local ensemble has "
+                             "four flows per point)")
         if pairs is None:
-            return self._call(self._decoding_points, y, x, times, scale, return_flow)
+            return self._call(self._decoding_points, y, x, times, scale, return_flow, ensemble)
         with self._pairs_selected(pairs):
-            return self._call(self._decoding_points, y, x, times, scale, return_flow)
+            return self._call(self._decoding_points, y, x, times, scale, return_flow, ensemble)
 
     def _point_list(self, y, x, times, B, HH, WW):
         """The arguments of ``decoding_points`` as an ``ops.DecPoints`` over B items."""
@@ -980,7 +994,30 @@ class LunaTokis(nn.Module):
         (yi, _), (xi, _), (ti, tp) = (point_strides(s, v.stride()) for s, v in ((ys, yt), (xs, xt), (ts, tt)))
         return ops.DecPoints(yt, xt, tt, yi, xi, ti, tp, n, B)
 
-    def _decoding_points(self, y, x, times, scale=None, return_flow=False):
+    def _ensemble_points(self, proj, mlp, tabs, blends, sub, o, fl, st):
+        """The local ensemble at the points ``sub`` of the items of ``proj`` into ``o`` ([k, 3, m]): per shift, in
+        ops.ENSEMBLE_BLEND_ORDER on one stream -- the remapped pixel of every point (``ops.dec_remap_pts``), feat_imnet
+        of the shifted query there (the flow stage's HRfeat operand), the flow, its eight corner pixels and their
+        HRfeat as in the plain path but with the shifted tables, and stage 2 blending w_k rgb into ``o`` (the first
+        stores, the others accumulate).  One shift's scratch is alive at a time."""
+        k, m = o.shape[0], sub.npts
+        ints = lambda *shape: torch.empty(*shape, device=self.device, dtype=torch.int32)
+        for s in ops.ENSEMBLE_BLEND_ORDER:
+            tab = tabs[s]
+            remapped = ops.dec_remap_pts(tab, sub, k, ints(k, m), ints(k, m), status=st)
+            hrf = self._empty(k, m, 64)
+            ops.dec_stage1_pts(proj, mlp, tab.plain, remapped, hrf, None, flags=fl, status=st)
+            flow = self._empty(k, m, 4)
+            ops.dec_flow_pts(proj, mlp, tab, sub, hrf, flow, flags=fl, status=st)
+            del hrf, remapped
+            corners = ops.dec_corners_pts(flow, tab.plain, sub, ints(k, 8 * m), ints(k, 8 * m), self._empty(k, 8 * m),
+                                          status=st)
+            hrf8 = self._empty(k, 8 * m, 64)
+            ops.dec_stage1_pts(proj, mlp, tab.plain, corners, hrf8, None, flags=fl, status=st)
+            ops.dec_stage2_blend_pts(proj, mlp, hrf8, flow, tab, sub, o, blends[s], flags=fl, status=st)
+            del hrf8, corners, flow
+
+    def _decoding_points(self, y, x, times, scale=None, return_flow=False, ensemble=False):
         if self._feat is None:
             raise RuntimeError("decoding needs gen_feat first")
         _, B, H, Wd, _ = self._feat.shape
@@ -997,12 +1034,24 @@ class LunaTokis(nn.Module):
         # scratch bound of the whole-grid decode; points are decoded independently, so chunking changes no bit
         per, ranges = point_passes(B, n, self.dec_chunk_px)
         whole = len(ranges) == 1
+        if ensemble:
+            tabs = [self._tab(H, Wd, HH, WW, s) for s in ops.ENSEMBLE_SHIFTS]
+            blends = {k: ops.dec_blend(k, tabs, accumulate=i > 0) for i, k in enumerate(ops.ENSEMBLE_BLEND_ORDER)}
 
         def body(proj, a, b):
             k = b - a
             for p0, p1 in ranges:
                 m = p1 - p0
                 sub = pts.sub(a, b, p0, p1)
+                if ensemble:
+                    # the range's buffer lives across its four shifts before it is copied into place
+                    o = out[a:b] if whole else self._empty(k, 3, m)
+                    self._ensemble_points(proj, mlp, tabs, blends, sub, o, fl, st)
+                    if not whole:
+                        out[a:b, :, p0:p1].copy_(o)
+                    del o
+                    yield
+                    continue
                 hrf = self._empty(k, m, 64)
                 flow = flw[a:b] if whole and return_flow else self._empty(k, m, 4)
                 ops.dec_stage1_pts(proj, mlp, tab, sub, hrf, flow, flags=fl, status=st)

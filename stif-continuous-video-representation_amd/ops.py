@@ -666,6 +666,61 @@ def dec_stage2_pts(proj, mlp, hrfeat8, flow, tables: DecTablesDev, pts: DecPoint
             C.byref(tables.c), C.byref(pts.c), _vp(out), n, h, w, HH, WW, flags, _vp(status), _stream())
 
 
+def _shifted_points_call(pts, n, tables, what):
+    if not tables.shifted:
+        raise ValueError(f"{what}: the tables of a shifted query (local ensemble) are required")
+    if pts.n is not None and pts.n != n:
+        raise ValueError(f"{what}: the point list holds {pts.n} items, the call has {n}")
+
+
+def dec_remap_pts(tables: DecTablesDev, pts: DecPoints, n, ry, rx, status=None) -> DecPoints:
+    """The HR pixel whose HRfeat row the flow stage of the shifted query ``tables`` reads for every point of the ``n``
+    items: ry = hr_y[y], rx = hr_x[x] (int32 [n, npts]) at the point's row / column, clamped into the grid (bit 3 of
+    ``status``).  Returns them with the points' times as the point list of the feat-only pass (dec_stage1_pts with
+    ``tables.plain`` and flow=None), whose hrfeat [n, npts, 64] is dec_flow_pts' operand."""
+    _shifted_points_call(pts, n, tables, "dec_remap_pts")
+    for v, name in ((ry, "ry"), (rx, "rx")):
+        _dense(v, (n, pts.npts), torch.int32, f"dec_remap_pts: {name}")
+    HH, WW = tables.shape[2:]
+    _launch("stif_dec_remap_pts", None, L.lib().stif_dec_remap_pts, C.byref(tables.c), C.byref(pts.c), _vp(ry), _vp(rx),
+            n, HH, WW, _vp(status), _stream())
+    m = pts.npts
+    return DecPoints(ry, rx, pts.t, m, m, pts.strides[2], pts.strides[3], m, n, (0, 0, pts.offsets[2]))
+
+
+def dec_flow_pts(proj, mlp, tables: DecTablesDev, pts: DecPoints, hrfeat, flow, flags=0, status=None):
+    """The flow-only stage of a shifted query (``tables`` with the remap) over a point list: flow [n, npts, 4], the
+    HRfeat operand of point p of item i row [i, p] of ``hrfeat`` [n, npts, 64] (dec_remap_pts)."""
+    n, h, w, _ = proj.shape
+    _shifted_points_call(pts, n, tables, "dec_flow_pts")
+    _dense(hrfeat, (n, pts.npts, 64), torch.float32, "dec_flow_pts: hrfeat")
+    if flow is None:
+        raise ValueError("dec_flow_pts: flow is the output")
+    _dense(flow, (n, pts.npts, 4), torch.float32, "dec_flow_pts: flow")
+    HH, WW = tables.shape[2:]
+    _launch("stif_dec_flow_pts", None, L.lib().stif_dec_flow_pts, _vp(proj), _vp(mlp), C.byref(tables.c),
+            C.byref(pts.c), _vp(hrfeat), _vp(flow), n, h, w, HH, WW, flags, _vp(status), _stream())
+
+
+def dec_stage2_blend_pts(proj, mlp, hrfeat8, flow, tables: DecTablesDev, pts: DecPoints, out, blend: L.DecBlend,
+                         flags=0, status=None):
+    """dec_stage2_pts with the local ensemble's epilogue (dec_blend): w_k rgb is stored into out [n, 3, npts], or
+    added to what it holds (blend.accumulate), the weight taken at the point's row / column.  ``tables``: those of
+    the shifted query or their ``plain`` (the remap is not read)."""
+    n, h, w, _ = proj.shape
+    if pts.n is not None and pts.n != n:
+        raise ValueError(f"dec_stage2_blend_pts: the point list holds {pts.n} items, the call has {n}")
+    if not isinstance(blend, L.DecBlend):
+        raise ValueError("dec_stage2_blend_pts: blend must be a dec_blend")
+    _dense(hrfeat8, (n, 8 * pts.npts, 64), torch.float32, "dec_stage2_blend_pts: hrfeat8")
+    _dense(flow, (n, pts.npts, 4), torch.float32, "dec_stage2_blend_pts: flow")
+    _dense(out, (n, 3, pts.npts), torch.float32, "dec_stage2_blend_pts: out")
+    HH, WW = tables.shape[2:]
+    _launch("stif_dec_stage2_blend_pts", None, L.lib().stif_dec_stage2_blend_pts, _vp(proj), _vp(mlp), _vp(hrfeat8),
+            _vp(flow), C.byref(tables.c), C.byref(pts.c), _vp(out), n, h, w, HH, WW, flags, _vp(status), _stream(),
+            C.byref(blend))
+
+
 # ----------------------------------------------------------------------------- video I/O (planar YUV <-> RGB)
 _YUV_MATRIX = {"bt601": L.YUV_BT601, "bt709": L.YUV_BT709}
 

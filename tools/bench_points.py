@@ -4,7 +4,9 @@ are obtained without point queries: the full decode followed by an index, and de
 same pixel count.  Device events around each call, WARM warm-up rounds, then REPS rounds that alternate the three
 (so drift hits them alike); per line the median and the spread (min .. max) over the rounds.
 PARENT=<checkout of another commit with its library built>: the full decode and the window are measured on that
-checkout's package and library, in this process, on its own latent of the same frames."""
+checkout's package and library, in this process, on its own latent of the same frames.
+ENSEMBLE=1: the three ways with the local ensemble -- decoding_points(ensemble=True), the full ensemble decode
+followed by an index, and decoding(window=, ensemble=True) of equal pixel count."""
 import importlib.util
 import os
 import statistics
@@ -20,6 +22,8 @@ PKG = "stif-continuous-video-representation_amd"
 counts = [int(v) for v in os.environ.get("N", "256,4096,65536").split(",")]
 reps, warm = int(os.environ.get("REPS", "7")), int(os.environ.get("WARM", "2"))
 mode = os.environ.get("MFMA", "f16x3")
+ens = os.environ.get("ENSEMBLE", "0") not in ("", "0")
+kw = dict(ensemble=True) if ens else {}
 stif = stif_pkg.load()
 base, base_name = stif, "this tree"
 if os.environ.get("PARENT"):
@@ -61,10 +65,11 @@ def timed(fn):
 
 
 def line(name, ms):
-    print(f"  {name:34s} {statistics.median(ms):9.3f} ms   ({min(ms):.3f} .. {max(ms):.3f})", flush=True)
+    print(f"  {name:{46 if ens else 34}s} {statistics.median(ms):9.3f} ms   ({min(ms):.3f} .. {max(ms):.3f})", flush=True)
 
 
-print(f"C0 latent, {B} items, grid {HH} x {WW}, {mode}; full decode and window on: {base_name}", flush=True)
+print(f"C0 latent, {B} items, grid {HH} x {WW}, {mode}{', local ensemble' if ens else ''}; full decode and window "
+      f"on: {base_name}", flush=True)
 with torch.no_grad():
     for n in counts:
         g = torch.Generator(device=dev).manual_seed(n)
@@ -75,13 +80,14 @@ with torch.no_grad():
         side = int(round(n ** 0.5))
         win = ((HH - side) // 2, (WW - side) // 2, side, n // side)
         def full_index():
-            o = parent.decoding(tq)[0]
+            o = parent.decoding(tq, **kw)[0]
             return torch.stack([o[b][:, yl[b], xl[b]] for b in range(B)])
 
+        e = ", ensemble=True" if ens else ""
         ways = {
-            "decoding_points": lambda: model.decoding_points(y, x, t),
-            "full decode + index": full_index,
-            f"decoding(window={win[2]}x{win[3]})": lambda: parent.decoding(tq, window=win),
+            f"decoding_points({e[2:]})" if ens else "decoding_points": lambda: model.decoding_points(y, x, t, **kw),
+            f"full {'ensemble ' if ens else ''}decode + index": full_index,
+            f"decoding(window={win[2]}x{win[3]}{e})": lambda: parent.decoding(tq, window=win, **kw),
         }
         ms = {k: [] for k in ways}
         for r in range(warm + reps):
