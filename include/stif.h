@@ -104,6 +104,34 @@ int stif_conv2d_nhwc(const stif_conv_args* args, void* stream);
  * in1_mode 0 or 1; C0 and C1 multiples of 32. */
 int stif_conv3x3_wino(const stif_conv_args* args, void* stream);
 
+/* Weight and bias gradient of the 3x3 / stride 1 / 'same' convolution (training):
+ *   gw[co][ci][kh][kw] = sum_{n,y,x} gy[n][y][x][co] * x[n][y + kh - 1][x + kw - 1][ci]  (zero outside the map),
+ *   gb[co] = sum_{n,y,x} gy[n][y][x][co].
+ * x (the forward's input) and gy (the gradient of its output) are NHWC fp32 maps of n items, x_item / gy_item
+ * elements apart (>= 0, multiples of 4; bases 16-B aligned); gw is written in the state dict's OIHW order, gb may
+ * be NULL; both are overwritten.  cin = cout = 64 only (the struct carries both so other shapes can follow).
+ * Exact fp32 products on fp32 MFMA, fp32 accumulation.  No floating-point atomics: a persistent grid of G
+ * workgroups (G a function of n, H, W and the device's CU count) takes the tiles in a static order, each writes
+ * one partial sum to the workspace, and a second launch adds the G partials in index order, so repeated calls on
+ * one device give identical bits.  workspace: at least stif_conv3x3_wgrad_workspace_size bytes, 16-B aligned;
+ * its previous contents do not matter.  STIF_E_INVALID, each with its reason, before any launch: null args, a
+ * null x / gy / gw, n / H / W < 1, other channel counts, a negative or misaligned stride, an item of 2 GB or more
+ * (the limit stif_conv3x3_wino enforces), a workspace that is missing, too small or misaligned.
+ * Zero-initialise the struct, then fill. */
+typedef struct {
+  const float* x;
+  const float* gy;
+  float* gw;               /* [cout][cin][3][3] */
+  float* gb;               /* [cout] or NULL */
+  long long x_item, gy_item;
+  int n, H, W, cin, cout;
+  void* workspace;
+  size_t workspace_bytes;
+} stif_conv_wgrad_args;
+/* 0 for sizes < 1 or unsupported channel counts.  Pure host once the device's CU count is known. */
+size_t stif_conv3x3_wgrad_workspace_size(int n, int H, int W, int cin, int cout);
+int stif_conv3x3_wgrad(const stif_conv_wgrad_args* args, void* stream);
+
 /* out = scale * F.interpolate(in, scale_factor=2, mode='bilinear', align_corners=False) on NHWC
  * maps (PCD_Align's coarse-to-fine step, Sakuya_arch_test.py:86-87); in [n][h1][w1][c],
  * out [n][2h1][2w1][c], items `in_item` / `out_item` floats apart, c % 4 == 0. */
@@ -315,6 +343,21 @@ size_t stif_conv_bias_floats(int cout, int mode);
  * 8 (2 a + (l >> 5)) + e, cout nt * 32 + (l & 31). */
 int stif_pack_conv_weight(const float* w_oihw, const float* b, int cout, int cin, int ks, int mode,
                           float* w_dst, float* b_dst);
+
+/* The Winograd packer on the device, for weights that change every training step: all pointers are device
+ * pointers, nothing is read back and nothing is copied through the host.  mode STIF_PACK_WINO or STIF_PACK_WINO |
+ * STIF_PACK_F16X3, ks 3, cin = cout = 64 (anything else is STIF_E_INVALID); w_dst / b_dst sized by
+ * stif_conv_weight_floats / stif_conv_bias_floats.  The bytes written are those stif_pack_conv_weight writes for
+ * the same weight (the transform is evaluated in double in the same addition order, every product exact).
+ * flags = STIF_PACK_DGRAD: packs the data gradient's weight w'[ci][co][kh][kw] = w[co][ci][2 - kh][2 - kw] with a
+ * zero bias (b may be NULL then), so that stif_conv3x3_wino on grad_output computes grad_input.
+ * status: device word, required with STIF_PACK_F16X3 (may be NULL otherwise): where the host packer returns
+ * STIF_E_RANGE (a U = G g G^T outside |U| <= 65504 / 1024) the kernel ORs STIF_STATUS_PACK_RANGE into *status
+ * (a vector atomic) and the packed bytes are unspecified -- pack and run that layer with STIF_PACK_WINO alone. */
+#define STIF_PACK_DGRAD 1
+#define STIF_STATUS_PACK_RANGE 16
+int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, int mode, int flags,
+                              float* w_dst, float* b_dst, int* status, void* stream);
 
 size_t stif_dec_proj_floats(void);   /* packed fp32 1x1 weight of the LR projection: [25][256][1][8]; the
                                         f16x3 packing: stif_conv_weight_floats(256, 200, 1, STIF_PACK_PLAIN | STIF_PACK_F16X3) */

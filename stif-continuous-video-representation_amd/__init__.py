@@ -15,7 +15,8 @@ Layout:
 (integration/_ext.py at the repo root is the DCNv2 `_ext` shim over ops.dcn_v2_forward)
   parallel.py frame-pair sharding over ranks
   serving.py  option files, define_G / load_network / VideoSRModel (checkpoint drop-in)
-  train.py    Charbonnier loss, the two restart LR schedules, Adam set-up (training drop-ins)
+  train.py    Charbonnier loss, the two restart LR schedules, Adam set-up (training drop-ins); trainable
+              Conv3x3 / ResidualBlock_noBN / make_trunk on the HIP conv forward, data- and weight-gradient kernels
 """
 from . import weights  # noqa: F401
 from . import coords  # noqa: F401

@@ -18,6 +18,8 @@ PACK_F16X3 = 16          # OR'ed into a PACK_WINO* mode (stif.h STIF_PACK_F16X3)
 CONV_F16X3 = 1           # stif_conv_args.flags
 CONV_DYNAMIC = 2         # stif_conv_args.flags: dynamic tile schedule (sched counters)
 DEC_REVOLUTIONS = 2      # stif_pack_dec_proj_ex lr_image bit (stif.h STIF_DEC_REVOLUTIONS)
+PACK_DGRAD = 1           # stif_pack_conv_weight_dev flags: the data gradient's weight (stif.h STIF_PACK_DGRAD)
+STATUS_PACK_RANGE = 16   # status bit of the device packer (stif.h STIF_STATUS_PACK_RANGE)
 
 _P = C.c_void_p
 _PA = _P * MAXG
@@ -51,6 +53,15 @@ class DcnSepArgs(C.Structure):
         ("fea_item", C.c_longlong), ("in_item", C.c_longlong), ("out_item", C.c_longlong),
         ("ngroups", C.c_int), ("nitems", C.c_int), ("H", C.c_int), ("W", C.c_int), ("epi", C.c_int),
         ("flags", C.c_int), ("status", _P),
+    ]
+
+
+class ConvWgradArgs(C.Structure):
+    """stif_conv_wgrad_args: x / gy NHWC maps with element strides between items, gw OIHW, gb or NULL."""
+    _fields_ = [
+        ("x", _P), ("gy", _P), ("gw", _P), ("gb", _P), ("x_item", C.c_longlong), ("gy_item", C.c_longlong),
+        ("n", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cin", C.c_int), ("cout", C.c_int),
+        ("workspace", _P), ("workspace_bytes", C.c_size_t),
     ]
 
 
@@ -126,6 +137,9 @@ EXPORTS = {
     "stif_metric_float": (C.c_int, [C.POINTER(MetricArgs), C.c_int, _P, _P, C.c_size_t, _P]),
     "stif_conv2d_nhwc": (C.c_int, [C.POINTER(ConvArgs), _P]),
     "stif_conv3x3_wino": (C.c_int, [C.POINTER(ConvArgs), _P]),
+    "stif_conv3x3_wgrad_workspace_size": (C.c_size_t, [C.c_int] * 5),
+    "stif_conv3x3_wgrad": (C.c_int, [C.POINTER(ConvWgradArgs), _P]),
+    "stif_pack_conv_weight_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "stif_upsample2x_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,
                                        C.c_longlong, _P]),
     "stif_conv_first": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

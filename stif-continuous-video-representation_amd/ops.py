@@ -189,6 +189,65 @@ def conv2d(groups, *, epi=L.EPI_NONE, in1_mode=0, in1_scale=1.0, stride=None, st
         _launch("stif_conv2d_nhwc", trace, L.lib().stif_conv2d_nhwc, C.byref(a), _stream())
 
 
+def pack_conv_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mode: int = L.PACK_WINO, dgrad: bool = False,
+                  status: Optional[torch.Tensor] = None) -> PackedConv:
+    """The Winograd packing of a 64 -> 64 3x3 layer on the device (stif_pack_conv_weight_dev): ``weight`` [64,64,3,3]
+    and ``bias`` [64] are device tensors and nothing passes through the host.  ``dgrad``: the data gradient's weight
+    (transposed and rotated, zero bias; ``bias`` may be None).  With ``PACK_F16X3`` a weight outside the split-fp16
+    range sets ``STATUS_PACK_RANGE`` in the int32 device word ``status`` (required then) instead of raising."""
+    if not (weight.is_cuda and weight.dtype == torch.float32):
+        raise ValueError("pack_conv_dev: expected a float32 CUDA weight")
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
+        raise ValueError("pack_conv_dev: expected a float32 CUDA bias")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"pack_conv_dev: weight shape {tuple(weight.shape)} is not [cout, cin, k, k]")
+    weight = weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    cout, cin, ks, _ = weight.shape
+    lib = L.lib()
+    wd = torch.empty(lib.stif_conv_weight_floats(cout, cin, ks, mode), dtype=torch.float32, device=weight.device)
+    bd = torch.empty(lib.stif_conv_bias_floats(cout, mode), dtype=torch.float32, device=weight.device)
+    _launch("stif_pack_conv_weight_dev", None, lib.stif_pack_conv_weight_dev, _vp(weight), _vp(bias), cout, cin, ks,
+            mode, L.PACK_DGRAD if dgrad else 0, _vp(wd), _vp(bd), _vp(status), _stream())
+    return PackedConv(wd, bd, cin if dgrad else cout, cout if dgrad else cin, ks, mode)
+
+
+# stif_conv3x3_wgrad's workspace (the workgroups' partial sums): one buffer per (device, stream), grown on demand;
+# launches on one stream run in issue order, launches on different streams never share one
+_WGRAD_WS = {}
+
+
+def conv3x3_wgrad(x: torch.Tensor, gy: torch.Tensor):
+    """Weight and bias gradient of the 3x3 / stride-1 / 64 -> 64 'same' conv: NHWC ``x`` (the forward's input) and
+    ``gy`` (the gradient of its output), [n, H, W, 64] fp32 with any item stride, pixels contiguous -- as ops.conv2d
+    reads its inputs.  Returns (gw [64, 64, 3, 3] in the state dict's OIHW order, gb [64]); repeated calls give
+    identical bits (no atomics)."""
+    if x.dim() != 4 or x.shape != gy.shape or x.shape[3] != 64:
+        raise ValueError(f"conv3x3_wgrad: x {tuple(x.shape)} and gy {tuple(gy.shape)} must both be [n, H, W, 64]")
+    x_item = _item_stride([x], "conv3x3_wgrad x")
+    gy_item = _item_stride([gy], "conv3x3_wgrad gy")
+    n, H, W, _ = x.shape
+    lib = L.lib()
+    nbytes = lib.stif_conv3x3_wgrad_workspace_size(n, H, W, 64, 64)
+    s = torch.cuda.current_stream(x.device)
+    key = (s.device.index, s.cuda_stream)
+    ws = _WGRAD_WS.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _WGRAD_WS[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
+    gw = torch.empty(64, 64, 3, 3, dtype=torch.float32, device=x.device)
+    gb = torch.empty(64, dtype=torch.float32, device=x.device)
+    a = L.ConvWgradArgs()
+    a.x, a.gy, a.gw, a.gb = _vp(x), _vp(gy), _vp(gw), _vp(gb)
+    a.x_item, a.gy_item = x_item, gy_item
+    a.n, a.H, a.W, a.cin, a.cout = n, H, W, 64, 64
+    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
+    trace = None
+    if TRACE is not None:
+        trace = (("wgrad",), 2.0 * 64 * 64 * 9 * n * H * W, 4.0 * 2 * 64 * n * H * W)
+    _launch("stif_conv3x3_wgrad", trace, lib.stif_conv3x3_wgrad, C.byref(a), s.cuda_stream)
+    return gw, gb
+
+
 def upsample2x(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0):
     """out = scale * bilinear x2 upsample (align_corners=False) of NHWC x [n, h, w, c] (items may be
     strided; pixels contiguous) into out [n, 2h, 2w, c]."""

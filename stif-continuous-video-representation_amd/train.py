@@ -13,8 +13,19 @@ Both schedules are recurrences on the group's current lr (each step scales the p
 reference evaluates them, so a resumed optimizer continues the same sequence; ``tests/test_train.py`` checks
 them step for step against sequences recorded from the reference's own classes (tests/golden/make_golden.py
 sched).  ``optimize_step`` is VideoSRBaseModel.optimize_parameters (VideoSR_base_model.py:113-134) for a
-module and one target.  The HIP forward (``LunaTokis``) is inference-only; training runs a torch module whose
-DCN_sep layers call the ``_ext`` drop-in (integration/_ext.py: stif_dcn_v2_forward / _backward).
+module and one target.  The whole-model HIP forward (``LunaTokis``) is inference-only.  Two of the model's
+operators train on the engine's own kernels: the DCN_sep layers of a torch module through the ``_ext`` drop-in
+(integration/_ext.py: stif_dcn_v2_forward / _backward), and the 3x3 / 64 -> 64 convolutions of the residual
+trunks through the modules below.
+
+* ``Conv3x3``, ``ResidualBlock_noBN``, ``make_trunk`` -- module_util.py:34-52 with ``nn.Conv2d``'s parameter
+  names and shapes (reference checkpoints load), forward and backward on the HIP kernels: the forward and the
+  data gradient are stif_conv3x3_wino (the data gradient with the transposed, rotated weight), the weight /
+  bias gradient is stif_conv3x3_wgrad, and the weights are re-packed on the device every step
+  (stif_pack_conv_weight_dev).  ``mfma="f16x3"`` runs the two Winograd convs on split-fp16 operands; the weight
+  gradient always uses exact fp32 products.  The f16x3 operand range is reported through one device status word
+  per device: ``module.range_status()`` reads and clears it (one sync).  A step that ends with a non-zero
+  status used an operand outside the split range somewhere and must be redone with ``mfma="f32"``.
 """
 from __future__ import annotations
 
@@ -24,6 +35,9 @@ from collections import Counter, defaultdict
 import torch
 from torch import nn
 from torch.optim.lr_scheduler import LRScheduler
+
+from . import _lib as L
+from . import ops
 
 
 class CharbonnierLoss(nn.Module):
@@ -137,3 +151,176 @@ def optimize_step(net: nn.Module, opt, criterion, inputs, gt, weight: float = 1.
     loss.backward()
     opt.step()
     return float(loss.detach())
+
+
+# ---- the residual trunks' 3x3 convolutions, trainable on the HIP kernels ----
+
+_EPI = {None: L.EPI_NONE, "relu": L.EPI_RELU, "lrelu": L.EPI_LRELU}
+_PACK = {"f16x3": L.PACK_WINO | L.PACK_F16X3, "f32": L.PACK_WINO}
+_STATUS = {}   # device index -> the int32 status word every module on that device shares
+
+
+def _status_word(device) -> torch.Tensor:
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    s = _STATUS.get(idx)
+    if s is None:
+        s = _STATUS[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+    return s
+
+
+def range_status(device=None) -> int:
+    """Read and clear the f16x3 range status of ``device`` (default: the current one); one synchronisation.
+    Bit 0: a Winograd conv (forward or data gradient) produced a non-finite value -- an activation or gradient
+    outside the split-fp16 range; ``STATUS_PACK_RANGE`` (16): a weight outside it (the convs store a plain 1, so a
+    later conv's report may replace the packer's bit: test for non-zero).  Non-zero: redo the step with
+    ``mfma="f32"``."""
+    s = _status_word(torch.device("cuda") if device is None else torch.device(device))
+    bits = int(s.item())
+    s.zero_()
+    return bits
+
+
+def _nhwc(t: torch.Tensor, what: str) -> torch.Tensor:
+    """The NHWC buffer of a logical NCHW tensor: a ``channels_last`` tensor is used in place (its memory is
+    NHWC), anything else is converted once."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
+                           "(move the module and its input to the GPU)")
+    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 64:
+        raise RuntimeError(f"{what}: expected a float32 [n, 64, H, W] tensor, got {t.dtype} {tuple(t.shape)}")
+    v = t.detach().permute(0, 2, 3, 1)
+    return v if v.is_contiguous() else v.contiguous()
+
+
+def _wino(x, weight, bias, mode, epi=L.EPI_NONE, res=None, dgrad=False):
+    """stif_conv3x3_wino of NHWC ``x`` with ``weight`` packed on the device for this call (``dgrad``: the data
+    gradient's packing, so ``x`` is a grad_output and the result a grad_input); returns a new NHWC tensor."""
+    status = _status_word(x.device)
+    lay = ops.pack_conv_dev(weight, bias, mode, dgrad=dgrad, status=status)
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    ops.conv2d([dict(layer=lay, in0=x, out=out, res=res)], epi=epi, status=status)
+    return out
+
+
+class _Conv3x3Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, mode):
+        xh = _nhwc(x, "Conv3x3")
+        out = _wino(xh, weight, bias, mode, _EPI[act])
+        ctx.act, ctx.mode = act, mode
+        ctx.save_for_backward(xh, weight, out if act else None)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xh, weight, out = ctx.saved_tensors
+        g = _nhwc(grad_out, "Conv3x3 backward")
+        # the activation's derivative from its output: both activations keep the sign of their argument
+        if ctx.act == "relu":
+            g = g * (out > 0)
+        elif ctx.act == "lrelu":
+            g = torch.where(out > 0, g, g * 0.1)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        gx = gw = gb = None
+        if need_w or need_b:
+            gw, gb = ops.conv3x3_wgrad(xh, g)
+        if need_x:
+            gx = _wino(g, weight, None, ctx.mode, dgrad=True).permute(0, 3, 1, 2)
+        return gx, gw if need_w else None, gb if need_b else None, None, None
+
+
+class _ResBlockFn(torch.autograd.Function):
+    """identity + conv2(relu(conv1(x))) as one node: the residual rides in conv2's epilogue, and the identity
+    path's gradient in the epilogue of conv1's data gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, mode):
+        xh = _nhwc(x, "ResidualBlock_noBN")
+        t = _wino(xh, w1, b1, mode, L.EPI_RELU)
+        out = _wino(t, w2, b2, mode, L.EPI_RES, res=xh)
+        ctx.mode = mode
+        ctx.save_for_backward(xh, t, w1, w2)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xh, t, w1, w2 = ctx.saved_tensors
+        g = _nhwc(grad_out, "ResidualBlock_noBN backward")
+        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
+        gx = gw1 = gb1 = gw2 = gb2 = None
+        if need_w2 or need_b2:
+            gw2, gb2 = ops.conv3x3_wgrad(t, g)
+        if need_x or need_w1 or need_b1:
+            gt = _wino(g, w2, None, ctx.mode, dgrad=True) * (t > 0)
+            if need_w1 or need_b1:
+                gw1, gb1 = ops.conv3x3_wgrad(xh, gt)
+            if need_x:
+                gx = _wino(gt, w1, None, ctx.mode, L.EPI_RES, res=g, dgrad=True).permute(0, 3, 1, 2)
+        return (gx, gw1 if need_w1 else None, gb1 if need_b1 else None, gw2 if need_w2 else None,
+                gb2 if need_b2 else None, None)
+
+
+def _check_choice(nf, act, mfma):
+    if nf != 64:
+        raise ValueError(f"the HIP conv backward covers 64 -> 64 channels only, got nf = {nf}")
+    if act not in _EPI:
+        raise ValueError(f"act must be None, 'relu' or 'lrelu', got {act!r}")
+    if mfma not in _PACK:
+        raise ValueError(f"mfma must be 'f16x3' or 'f32', got {mfma!r}")
+
+
+class Conv3x3(nn.Module):
+    """nn.Conv2d(64, 64, 3, 1, 1) with an optional fused ReLU / LeakyReLU(0.1), forward and backward on the HIP
+    kernels.  ``weight`` [64, 64, 3, 3] and ``bias`` [64] carry nn.Conv2d's names, shapes and default
+    initialisation.  Input and output are logical NCHW; the output is ``channels_last``, and a ``channels_last``
+    input is read in place."""
+
+    def __init__(self, nf: int = 64, act=None, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(nf, act, mfma)
+        self.act, self.mfma = act, mfma
+        self.weight = nn.Parameter(torch.empty(nf, nf, 3, 3))
+        self.bias = nn.Parameter(torch.empty(nf))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(nf * 9)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x):
+        return _Conv3x3Fn.apply(x, self.weight, self.bias, self.act, _PACK[self.mfma])
+
+    def range_status(self) -> int:
+        return range_status(self.weight.device)
+
+    def extra_repr(self):
+        return f"64, 64, kernel_size=(3, 3), padding=1, act={self.act}, mfma={self.mfma}"
+
+
+class ResidualBlock_noBN(nn.Module):
+    """module_util.py:34-52: identity + conv2(relu(conv1(x))), submodules ``conv1`` / ``conv2`` as in the
+    reference (kaiming-normal weights scaled by 0.1, zero biases), one autograd node on the HIP kernels."""
+
+    def __init__(self, nf: int = 64, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(nf, None, mfma)
+        self.mfma = mfma
+        self.conv1 = Conv3x3(nf, "relu", mfma)
+        self.conv2 = Conv3x3(nf, None, mfma)
+        with torch.no_grad():
+            for m in (self.conv1, self.conv2):
+                nn.init.kaiming_normal_(m.weight, a=0, mode="fan_in")
+                m.weight.mul_(0.1)
+                m.bias.zero_()
+
+    def forward(self, x):
+        return _ResBlockFn.apply(x, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
+                                 _PACK[self.mfma])
+
+    def range_status(self) -> int:
+        return range_status(self.conv1.weight.device)
+
+
+def make_trunk(n_blocks: int, nf: int = 64, mfma: str = "f16x3") -> nn.Sequential:
+    """module_util.make_layer of ``n_blocks`` ResidualBlock_noBN (keys ``0.conv1.weight``, ...): the
+    ``recon_trunk.*`` / ``feature_extraction.*`` slices of a LunaTokis state dict load with ``strict=True``.
+    ``trunk[0].range_status()`` (or ``train.range_status()``) reports the f16x3 range for the whole trunk."""
+    return nn.Sequential(*[ResidualBlock_noBN(nf, mfma) for _ in range(n_blocks)])
