@@ -132,6 +132,36 @@ typedef struct {
 size_t stif_conv3x3_wgrad_workspace_size(int n, int H, int W, int cin, int cout);
 int stif_conv3x3_wgrad(const stif_conv_wgrad_args* args, void* stream);
 
+/* The same for the 3x3 / stride 2 / pad 1 convolution (the pyramid's fea_L*_conv1), same struct: H, W are the size
+ * of x (the forward's input), gy is [n][Ho][Wo][64] with Ho = (H + 1) / 2, Wo = (W + 1) / 2, and
+ *   gw[co][ci][kh][kw] = sum_{n,oy,ox} gy[n][oy][ox][co] * x[n][2 oy + kh - 1][2 ox + kw - 1][ci]  (zero outside).
+ * Same partial-sum scheme, determinism contract, workspace rules and rejections as stif_conv3x3_wgrad. */
+size_t stif_conv3x3s2_wgrad_workspace_size(int n, int H, int W, int cin, int cout);
+int stif_conv3x3s2_wgrad(const stif_conv_wgrad_args* args, void* stream);
+
+/* Data gradient of the 3x3 / stride 2 / pad 1 / 64 -> 64 convolution (a transposed conv):
+ *   gx[n][y][x][ci] = sum over (kh, kw, co) with y + 1 - kh and x + 1 - kw even and (oy, ox) = ((y + 1 - kh) / 2,
+ *   (x + 1 - kw) / 2) inside [0, Ho) x [0, Wo) of gy[n][oy][ox][co] * w[co][ci][kh][kw].
+ * gy [n][Ho][Wo][64] and gx [n][H][W][64] are NHWC fp32 maps, gy_item / gx_item elements apart (>= 0, multiples of 4;
+ * bases 16-B aligned); H, W (the forward input's size) are given because Ho does not determine them.  w_oihw is the
+ * state dict's weight on the device (transposed by the kernel's own loads: the workspace size is 0 and workspace may
+ * be NULL).  gx is overwritten in full, each element by one lane; exact fp32 products on fp32 MFMA, split by the
+ * parity of the gx pixel so that no multiply-add is spent on an inserted zero.  STIF_E_INVALID before any launch:
+ * a null gy / w_oihw / gx, n / H / W < 1, a negative or misaligned stride, an item of 2 GB or more. */
+size_t stif_conv3x3s2_dgrad_workspace_size(int n, int H, int W);
+int stif_conv3x3s2_dgrad(const float* gy, const float* w_oihw, float* gx, long long gy_item, long long gx_item,
+                         int n, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Weight and bias gradient of conv_first (3 -> 64, 3x3 'same'): x_nchw the RGB frames [n,3,h,w] as stif_conv_first
+ * reads them, gy NHWC [n][h][w][64] (items gy_item elements apart, >= 0, a multiple of 4; base 16-B aligned),
+ * gw [64][3][3][3], gb [64] or NULL.  Two launches -- per-workgroup partials into the workspace, then a reduce in
+ * index order -- so repeated calls on one device give identical bits; the workspace (at least
+ * stif_conv_first_wgrad_workspace_size bytes, 16-B aligned) may hold anything.  The gradient with respect to the
+ * frames is not computed.  STIF_E_INVALID before any launch as for stif_conv3x3_wgrad. */
+size_t stif_conv_first_wgrad_workspace_size(int n, int h, int w);
+int stif_conv_first_wgrad(const float* x_nchw, const float* gy, float* gw, float* gb, long long gy_item,
+                          int n, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+
 /* out = scale * F.interpolate(in, scale_factor=2, mode='bilinear', align_corners=False) on NHWC
  * maps (PCD_Align's coarse-to-fine step, Sakuya_arch_test.py:86-87); in [n][h1][w1][c],
  * out [n][2h1][2w1][c], items `in_item` / `out_item` floats apart, c % 4 == 0. */
@@ -358,6 +388,12 @@ int stif_pack_conv_weight(const float* w_oihw, const float* b, int cout, int cin
 #define STIF_STATUS_PACK_RANGE 16
 int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, int mode, int flags,
                               float* w_dst, float* b_dst, int* status, void* stream);
+/* The fp32 STIF_PACK_PLAIN packing of a 64 -> 64 3x3 layer on the device (anything else is STIF_E_INVALID): byte
+ * for byte what stif_pack_conv_weight(..., STIF_PACK_PLAIN) writes, sized by stif_conv_weight_floats /
+ * stif_conv_bias_floats; b may be NULL (a zero bias).  With it the training forward of a stride-2 conv is
+ * stif_conv2d_nhwc with no host packing and no synchronisation. */
+int stif_pack_conv_plain_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, float* w_dst,
+                             float* b_dst, void* stream);
 
 size_t stif_dec_proj_floats(void);   /* packed fp32 1x1 weight of the LR projection: [25][256][1][8]; the
                                         f16x3 packing: stif_conv_weight_floats(256, 200, 1, STIF_PACK_PLAIN | STIF_PACK_F16X3) */

@@ -140,6 +140,14 @@ EXPORTS = {
     "stif_conv3x3_wgrad_workspace_size": (C.c_size_t, [C.c_int] * 5),
     "stif_conv3x3_wgrad": (C.c_int, [C.POINTER(ConvWgradArgs), _P]),
     "stif_pack_conv_weight_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "stif_conv3x3s2_wgrad_workspace_size": (C.c_size_t, [C.c_int] * 5),
+    "stif_conv3x3s2_wgrad": (C.c_int, [C.POINTER(ConvWgradArgs), _P]),
+    "stif_conv3x3s2_dgrad_workspace_size": (C.c_size_t, [C.c_int] * 3),
+    "stif_conv3x3s2_dgrad": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, _P,
+                                       C.c_size_t, _P]),
+    "stif_conv_first_wgrad_workspace_size": (C.c_size_t, [C.c_int] * 3),
+    "stif_conv_first_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "stif_pack_conv_plain_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "stif_upsample2x_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,
                                        C.c_longlong, _P]),
     "stif_conv_first": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

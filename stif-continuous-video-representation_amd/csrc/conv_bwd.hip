@@ -2,7 +2,11 @@
 // module_util.py:34-52): the weight / bias gradient kernel and the Winograd weight packer on the device.  The data
 // gradient needs no kernel of its own: it is stif_conv3x3_wino with the weight packed by
 // stif_pack_conv_weight_dev(..., STIF_PACK_DGRAD) (transposed and rotated), DESIGN.md section 3j.
+// And the backward of the frame encoder's other three convs: the weight gradient of the
+// stride-2 convs (the same kernel, a template on the stride), their data gradient (a transposed conv, split by output
+// parity), the weight gradient of conv_first (3 -> 64), and the STIF_PACK_PLAIN packer on the device.
 #include <algorithm>
+#include <cstdio>
 
 #include "abi_util.h"
 #include "stif.h"
@@ -24,15 +28,24 @@ namespace {
 #define STIF_WGRAD_TH 2
 #define STIF_WGRAD_WG_PER_CU 2
 #endif
-constexpr int TH = STIF_WGRAD_TH, TW = 32;
-constexpr int XH = TH + 2, XW = TW + 2;
+// The tile of stride S (1: 'same', 2: the pyramid's down-sampling convs, pad 1): TH x TW output (gy) pixels and the
+// S (TH - 1) + 3 rows x S (TW - 1) + 3 columns of x they read.  Stride 2 halves TW so that both tiles stay at
+// ~50 KB (42,240 + 8,192 B) and two workgroups still share a CU.
+template <int S>
+struct WgradTile {
+  static constexpr int TH = S == 1 ? STIF_WGRAD_TH : 2, TW = S == 1 ? 32 : 16;
+  static constexpr int XH = S * (TH - 1) + 3, XW = S * (TW - 1) + 3;
+};
 constexpr int WG_PER_CU = STIF_WGRAD_WG_PER_CU;
 constexpr int GW_FLOATS = 64 * 64 * 9;
 constexpr int PART = GW_FLOATS + 64;   // one workgroup's partial: [tap 9][co 64][ci 64] then the 64 bias sums
 
+// x is [H][W][64] per item, gy [Ho][Wo][64]; the tiles walk gy
+template <int S>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG_PER_CU)))
 void k_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ ws, long long x_item,
-             long long gy_item, int H, int W, int tiles_x, int tiles_per_item, int ntiles) {
+             long long gy_item, int H, int W, int Ho, int Wo, int tiles_x, int tiles_per_item, int ntiles) {
+  constexpr int TH = WgradTile<S>::TH, TW = WgradTile<S>::TW, XH = WgradTile<S>::XH, XW = WgradTile<S>::XW;
   __shared__ __attribute__((aligned(16))) float s_x[XH * XW * 64];
   __shared__ __attribute__((aligned(16))) float s_gy[TH * TW * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -55,7 +68,7 @@ void k_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* _
       const int i = tid + k * 256;
       if (i < XH * XW * 16) {
         const int c4 = i & 15, p = i >> 4, py = p / XW, px = p - py * XW;
-        const int yy = y0 + py - 1, xx = x0 + px - 1;
+        const int yy = S * y0 + py - 1, xx = S * x0 + px - 1;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = ld4(xi + ((size_t)yy * W + xx) * 64 + c4 * 4);
         st4(s_x + p * 64 + c4 * 4, v);
@@ -67,13 +80,14 @@ void k_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* _
       const int c4 = i & 15, p = i >> 4, py = p / TW, px = p - py * TW;
       const int yy = y0 + py, xx = x0 + px;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (yy < H && xx < W) v = ld4(gi + ((size_t)yy * W + xx) * 64 + c4 * 4);
+      if (yy < Ho && xx < Wo) v = ld4(gi + ((size_t)yy * Wo + xx) * 64 + c4 * 4);
       st4(s_gy + p * 64 + c4 * 4, v);
     }
     __syncthreads();
-    // k step (r, xs): pixels (r, 2 xs + hf) of the tile; tap (kh, kw) reads x tile pixel (r + kh, 2 xs + hf + kw)
+    // k step (r, xs): gy pixels (r, 2 xs + hf) of the tile; tap (kh, kw) reads x tile pixel
+    // (S r + kh, S (2 xs + hf) + kw)
     const float* ap = s_gy + hf * 64 + cot * 32 + l32;
-    const float* bp = s_x + hf * 64 + cit * 32 + l32;
+    const float* bp = s_x + S * hf * 64 + cit * 32 + l32;
 #pragma unroll
     for (int r = 0; r < TH; ++r) {
 #pragma unroll 2
@@ -84,7 +98,7 @@ void k_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* _
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
           for (int kw = 0; kw < 3; ++kw)
-            acc[kh * 3 + kw] = mfma32(a, bp[((r + kh) * XW + 2 * xs + kw) * 64], acc[kh * 3 + kw]);
+            acc[kh * 3 + kw] = mfma32(a, bp[((S * r + kh) * XW + S * 2 * xs + kw) * 64], acc[kh * 3 + kw]);
       }
     }
   }
@@ -115,9 +129,62 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
   }
 }
 
-long long wgrad_tiles(int n, int H, int W) { return (long long)n * ((H + TH - 1) / TH) * ((W + TW - 1) / TW); }
+// tiles over the gy map of an x of H x W (stride 2: Ho = (H + 1) / 2, Wo = (W + 1) / 2)
+template <int S>
+long long wgrad_tiles(int n, int H, int W) {
+  constexpr int TH = WgradTile<S>::TH, TW = WgradTile<S>::TW;
+  const int Ho = (H + S - 1) / S, Wo = (W + S - 1) / S;
+  return (long long)n * ((Ho + TH - 1) / TH) * ((Wo + TW - 1) / TW);
+}
 // workgroups launched = partials reduced: a function of the shape and the device's CU count alone
 int wgrad_grid(long long tiles) { return (int)std::min<long long>(tiles, (long long)WG_PER_CU * stif_num_cus()); }
+
+template <int S>
+size_t wgrad_workspace_size(int n, int H, int W, int cin, int cout) {
+  if (n < 1 || H < 1 || W < 1 || cin != 64 || cout != 64) return 0;
+  const long long tiles = wgrad_tiles<S>(n, H, W);
+  if (tiles > 0x7fffffffLL) return 0;
+  return (size_t)wgrad_grid(tiles) * PART * sizeof(float);
+}
+
+bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// the entry point of stride S; `fn` prefixes every message
+template <int S>
+int wgrad_entry(const char* fn, const stif_conv_wgrad_args* pa, void* stream) {
+  constexpr int TH = WgradTile<S>::TH, TW = WgradTile<S>::TW;
+  char msg[160];
+  auto fail = [&](const char* why) {
+    snprintf(msg, sizeof msg, "%s: %s", fn, why);
+    return stif_fail(STIF_E_INVALID, msg);
+  };
+  if (!pa) return fail("null args");
+  const stif_conv_wgrad_args& a = *pa;
+  if (!a.x || !a.gy || !a.gw) return fail("null pointer (x, gy, gw)");
+  if (a.n < 1 || a.H < 1 || a.W < 1) return fail("n, H, W must be >= 1");
+  if (a.cin != 64 || a.cout != 64) return fail("unsupported channel counts (64 -> 64 only)");
+  if (a.x_item < 0 || a.gy_item < 0) return fail("negative item stride");
+  if ((long long)a.H * a.W * 64 * 4 >= 0x7fffffffLL) return fail("item larger than 2 GB (buffer addressing)");
+  if (misaligned16(a.x) || misaligned16(a.gy) || a.x_item % 4 || a.gy_item % 4)
+    return fail("x / gy and their item strides must be 16-byte aligned");
+  const long long tiles = wgrad_tiles<S>(a.n, a.H, a.W);
+  if (tiles > 0x7fffffffLL) return fail("too many tiles");
+  const int G = wgrad_grid(tiles);
+  if (!a.workspace || a.workspace_bytes < (size_t)G * PART * sizeof(float))
+    return fail(S == 1 ? "workspace too small (stif_conv3x3_wgrad_workspace_size)"
+                       : "workspace too small (stif_conv3x3s2_wgrad_workspace_size)");
+  if (misaligned16(a.workspace)) return fail("workspace not 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int Ho = (a.H + S - 1) / S, Wo = (a.W + S - 1) / S;
+  const int tiles_x = (Wo + TW - 1) / TW, tiles_per_item = tiles_x * ((Ho + TH - 1) / TH);
+  float* ws = static_cast<float*>(a.workspace);
+  hipLaunchKernelGGL(k_wgrad<S>, dim3(G), dim3(256), 0, st, a.x, a.gy, ws, a.x_item, a.gy_item, a.H, a.W, Ho, Wo,
+                     tiles_x, tiles_per_item, (int)tiles);
+  if (int rc = stif_check_launch(fn)) return rc;
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3((PART + 255) / 256), dim3(256), 0, st, ws, G, a.gw, a.gb);
+  snprintf(msg, sizeof msg, "%s (reduce)", fn);
+  return stif_check_launch(msg);
+}
 
 // ---- Winograd weight packing on the device: the bytes of pack.cpp's pack_wino / pack_wino_f16x3 ----
 
@@ -177,44 +244,292 @@ __global__ __launch_bounds__(256) void k_pack_wino(const float* __restrict__ w, 
   if (ci == 0) b_dst[co] = (dgrad || b == nullptr) ? 0.f : b[co];
 }
 
-bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+// ---- the direct-conv (STIF_PACK_PLAIN) packing on the device: the bytes of pack.cpp's plain loop, 64 -> 64 3x3 ----
+// [chunk 8][tap 9][nt 2][lane 64][4]: one thread per destination element (a pure permutation)
+__global__ __launch_bounds__(256) void k_pack_plain(const float* __restrict__ w, const float* __restrict__ b,
+                                                    float* __restrict__ w_dst, float* __restrict__ b_dst) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;   // < 8 * 9 * 2 * 64 * 4 = 36864 = 144 blocks
+  const int e = idx & 3, l = (idx >> 2) & 63, nt = (idx >> 8) & 1, ct = idx >> 9, c = ct / 9, t = ct - c * 9;
+  const int co = nt * 32 + (l & 31), ci = c * 8 + 4 * (l >> 5) + e;
+  w_dst[idx] = w[(co * 64 + ci) * 9 + t];
+  if (idx < 64) b_dst[idx] = b == nullptr ? 0.f : b[idx];
+}
+
+// ---- stride-2 data gradient: gx = the transposed conv of gy, split by the parity of the gx pixel ----
+//
+// gx pixel (2 i + py, 2 j + px) takes tap (1, 1) of gy pixel (i, j) for (py, px) = (0, 0); taps (1, 0) / (1, 2) of
+// (i, j + 1) / (i, j) for (0, 1); taps (0, 1) / (2, 1) of (i + 1, j) / (i, j) for (1, 0); and taps (0, 0), (0, 2),
+// (2, 0), (2, 2) of (i + 1, j + 1), (i + 1, j), (i, j + 1), (i, j) for (1, 1): nine tap-GEMMs per gy pixel, the
+// forward's multiply-adds, none on an inserted zero.  A workgroup stages DG_TH x DG_TW gy pixels with one halo row
+// and column (zeros outside the map) in LDS, pixel-major with a 65-float pitch so that the 32 lanes of an A read
+// (32 consecutive pixels, one cout) fall on 32 banks.  Wave w owns row w of the tile: 32 gy pixels x 4 phases x 2
+// cin tiles = 128 accumulator registers.  The contraction runs over cout on fp32 MFMA, D[pixel 32][ci 32] +=
+// A[pixel][co pair] * B[co pair][ci]; the raw OIHW weight streams through LDS in chunks of DG_CO couts
+// ([tap][co][ci], transposed by the copy; 516-float tap pitch keeps the transposing writes to two per bank),
+// double-buffered: the next chunk is fetched into registers before the current one is consumed.
+constexpr int DG_TH = 4, DG_TW = 32, DG_GH = DG_TH + 1, DG_GW = DG_TW + 1, DG_PX = 65;
+constexpr int DG_CO = 8, DG_TAP = DG_CO * 64 + 4, DG_CHUNK = DG_CO * 64 * 9, DG_LD = DG_CHUNK / 256;
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+void k_dgrad_s2(const float* __restrict__ gy, const float* __restrict__ w, float* __restrict__ gx, long long gy_item,
+                long long gx_item, int H, int W, int Ho, int Wo, int tiles_x, int tiles_per_item) {
+  __shared__ float s_gy[DG_GH * DG_GW * DG_PX];
+  __shared__ float s_w[2][9 * DG_TAP];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, hf = lane >> 5;
+  const int t = blockIdx.x, n = t / tiles_per_item, rem = t - n * tiles_per_item, ty = rem / tiles_x;
+  const int i0 = ty * DG_TH, j0 = (rem - ty * tiles_x) * DG_TW;
+  const float* gi = gy + (size_t)n * gy_item;
+#pragma unroll
+  for (int k = 0; k < (DG_GH * DG_GW * 16 + 255) / 256; ++k) {
+    const int i = tid + k * 256;
+    if (i < DG_GH * DG_GW * 16) {
+      const int c4 = i & 15, p = i >> 4, py = p / DG_GW, px = p - py * DG_GW;
+      const int yy = i0 + py, xx = j0 + px;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (yy < Ho && xx < Wo) v = ld4(gi + ((size_t)yy * Wo + xx) * 64 + c4 * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s_gy[p * DG_PX + c4 * 4 + e] = v[e];
+    }
+  }
+  float wr[DG_LD];   // the next weight chunk: DG_CO couts of w[co][ci][tap], contiguous in OIHW
+#pragma unroll
+  for (int k = 0; k < DG_LD; ++k) wr[k] = w[tid + k * 256];
+#pragma unroll
+  for (int k = 0; k < DG_LD; ++k) {
+    const int e = tid + k * 256, q = e / 9;
+    s_w[0][(e - q * 9) * DG_TAP + q] = wr[k];
+  }
+  __syncthreads();
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int ph = 0; ph < 4; ++ph)
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[ph][ct][r] = 0.f;
+
+  const float* ap = s_gy + (wave * DG_GW + l32) * DG_PX + hf;
+#pragma unroll 1
+  for (int c = 0; c < 64 / DG_CO; ++c) {
+    if (c + 1 < 64 / DG_CO) {
+#pragma unroll
+      for (int k = 0; k < DG_LD; ++k) wr[k] = w[(c + 1) * DG_CHUNK + tid + k * 256];
+    }
+    const float* wb = s_w[c & 1] + hf * 64 + l32;
+#pragma unroll
+    for (int kk = 0; kk < DG_CO / 2; ++kk) {
+      const int co = c * DG_CO + 2 * kk;
+      const float a00 = ap[co], a01 = ap[DG_PX + co], a10 = ap[DG_GW * DG_PX + co], a11 = ap[(DG_GW + 1) * DG_PX + co];
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        const float* bp = wb + 2 * kk * 64 + ct * 32;
+        acc[0][ct] = mfma32(a00, bp[4 * DG_TAP], acc[0][ct]);
+        acc[1][ct] = mfma32(a01, bp[3 * DG_TAP], acc[1][ct]);
+        acc[2][ct] = mfma32(a10, bp[1 * DG_TAP], acc[2][ct]);
+        acc[3][ct] = mfma32(a11, bp[0 * DG_TAP], acc[3][ct]);
+        acc[1][ct] = mfma32(a00, bp[5 * DG_TAP], acc[1][ct]);
+        acc[2][ct] = mfma32(a00, bp[7 * DG_TAP], acc[2][ct]);
+        acc[3][ct] = mfma32(a10, bp[2 * DG_TAP], acc[3][ct]);
+        acc[3][ct] = mfma32(a01, bp[6 * DG_TAP], acc[3][ct]);
+        acc[3][ct] = mfma32(a00, bp[8 * DG_TAP], acc[3][ct]);
+      }
+    }
+    if (c + 1 < 64 / DG_CO) {   // the other buffer was last read before the previous barrier
+#pragma unroll
+      for (int k = 0; k < DG_LD; ++k) {
+        const int e = tid + k * 256, q = e / 9;
+        s_w[(c + 1) & 1][(e - q * 9) * DG_TAP + q] = wr[k];
+      }
+    }
+    __syncthreads();
+  }
+
+  // D[pixel = mfma_row][ci = l32]: rows / columns of gx past H / W (H = 2 Ho - 1) are not stored
+  float* go = gx + (size_t)n * gx_item;
+  const int i = i0 + wave;
+#pragma unroll
+  for (int ph = 0; ph < 4; ++ph) {
+    const int y = 2 * i + (ph >> 1);
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int xx = 2 * (j0 + mfma_row(r, lane)) + (ph & 1);
+        if (y < H && xx < W) go[((size_t)y * W + xx) * 64 + ct * 32 + l32] = acc[ph][ct][r];
+      }
+  }
+}
+
+// ---- conv_first (3 -> 64) weight gradient: gw[co][c][kh][kw] = sum gy[n][y][x][co] * x[n][c][y+kh-1][x+kw-1] ----
+//
+// Per pixel the 27 input taps and a constant one form the row operand (row 27 yields gb), the 64 gy channels the
+// column operand: D[row 32][co 32] += A[row][pixel pair] * B[pixel pair][co] on fp32 MFMA, operands straight from
+// global memory (gy is read once, 256 B per pixel -- the kernel's cost; the frames are 12 B per pixel and cached).
+// A wave takes runs of CF_WAVE_PX consecutive pixels of the flat [n][h][w] order, a workgroup CF_WG_PX, statically
+// (chunks b, b + G, ...); the four waves' accumulators are added in wave order and written as one [28][64] partial.
+constexpr int CF_PART = 28 * 64, CF_WAVE_PX = 128, CF_WG_PX = 4 * CF_WAVE_PX, CF_WG_PER_CU = 4;
+
+__global__ __launch_bounds__(256) void k_cf_wgrad(const float* __restrict__ x, const float* __restrict__ gy,
+                                                  float* __restrict__ ws, long long gy_item, int h, int w,
+                                                  long long total, int nchunks) {
+  __shared__ float s_part[4][32 * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, hf = lane >> 5;
+  const int c = l32 / 9, kh = (l32 - c * 9) / 3, kw = l32 - c * 9 - kh * 3;   // row l32 < 27: tap (c, kh, kw)
+  const long long hw = (long long)h * w;
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
+  for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    long long p = (long long)ch * CF_WG_PX + wave * CF_WAVE_PX + hf;   // this lane's pixel of each pair
+    if (p - hf >= total) continue;
+    long long img = p / hw;
+    int y = (int)((p - img * hw) / w), xq = (int)(p - img * hw - (long long)y * w);
+#pragma unroll 8
+    for (int ks = 0; ks < CF_WAVE_PX / 2; ++ks) {
+      float a = 0.f, b0 = 0.f, b1 = 0.f;
+      if (p < total) {
+        const float* g = gy + (size_t)img * gy_item + ((size_t)y * w + xq) * 64 + l32;
+        b0 = g[0];
+        b1 = g[32];
+        const int yy = y + kh - 1, xx = xq + kw - 1;
+        if (l32 == 27) a = 1.f;
+        else if (l32 < 27 && yy >= 0 && yy < h && xx >= 0 && xx < w) a = x[(((size_t)img * 3 + c) * h + yy) * w + xx];
+      }
+      acc0 = mfma32(a, b0, acc0);
+      acc1 = mfma32(a, b1, acc1);
+      // two pixels on, without a branch so that the loads of the unrolled steps are issued together: a step of 2
+      // wraps a row at most twice (w = 1), and each row wrap an image at most once
+      p += 2;
+      xq += 2;
+#pragma unroll
+      for (int rep = 0; rep < 2; ++rep) {
+        const int wx = xq >= w ? 1 : 0;
+        xq -= wx * w;
+        y += wx;
+        const int wy = y >= h ? 1 : 0;
+        y -= wy * h;
+        img += wy;
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    s_part[wave][mfma_row(r, lane) * 64 + l32] = acc0[r];
+    s_part[wave][mfma_row(r, lane) * 64 + 32 + l32] = acc1[r];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < CF_PART; idx += 256)
+    ws[(size_t)blockIdx.x * CF_PART + idx] = ((s_part[0][idx] + s_part[1][idx]) + s_part[2][idx]) + s_part[3][idx];
+}
+
+// gw [64][27] / gb = the G partials ([row 28][co 64]) summed in a fixed order: 16 threads per element, thread s adds
+// the partials s, s + 16, s + 32, ... in index order, then one thread adds the 16 sums in slice order.  The order is
+// a function of G alone; one thread per element (G dependent loads each) took longer than the partials kernel.
+__global__ __launch_bounds__(256) void k_cf_wgrad_reduce(const float* __restrict__ ws, int G, float* __restrict__ gw,
+                                                         float* __restrict__ gb) {
+  __shared__ float s_sum[16][16];
+  const int e = threadIdx.x & 15, sl = threadIdx.x >> 4, idx = blockIdx.x * 16 + e;   // CF_PART = 112 blocks x 16
+  float s = 0.f;
+#pragma unroll 8
+  for (int g = sl; g < G; g += 16) s += ws[(size_t)g * CF_PART + idx];
+  s_sum[sl][e] = s;
+  __syncthreads();
+  if (sl != 0) return;
+  float t = s_sum[0][e];
+#pragma unroll
+  for (int k = 1; k < 16; ++k) t += s_sum[k][e];
+  const int row = idx >> 6, co = idx & 63;
+  if (row < 27) gw[co * 27 + row] = t;
+  else if (gb != nullptr) gb[co] = t;
+}
+
+long long cf_chunks(int n, int h, int w) { return ((long long)n * h * w + CF_WG_PX - 1) / CF_WG_PX; }
+int cf_grid(long long chunks) { return (int)std::min<long long>(chunks, (long long)CF_WG_PER_CU * stif_num_cus()); }
+
+int fail_as(const char* fn, const char* why) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", fn, why);
+  return stif_fail(STIF_E_INVALID, msg);
+}
 
 }  // namespace
 
 extern "C" size_t stif_conv3x3_wgrad_workspace_size(int n, int H, int W, int cin, int cout) {
-  if (n < 1 || H < 1 || W < 1 || cin != 64 || cout != 64) return 0;
-  const long long tiles = wgrad_tiles(n, H, W);
-  if (tiles > 0x7fffffffLL) return 0;
-  return (size_t)wgrad_grid(tiles) * PART * sizeof(float);
+  return wgrad_workspace_size<1>(n, H, W, cin, cout);
 }
 
 extern "C" int stif_conv3x3_wgrad(const stif_conv_wgrad_args* pa, void* stream) {
-  if (!pa) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: null args");
-  const stif_conv_wgrad_args& a = *pa;
-  if (!a.x || !a.gy || !a.gw) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: null pointer (x, gy, gw)");
-  if (a.n < 1 || a.H < 1 || a.W < 1) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: n, H, W must be >= 1");
-  if (a.cin != 64 || a.cout != 64)
-    return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: unsupported channel counts (64 -> 64 only)");
-  if (a.x_item < 0 || a.gy_item < 0) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: negative item stride");
-  if ((long long)a.H * a.W * 64 * 4 >= 0x7fffffffLL)
-    return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: item larger than 2 GB (buffer addressing)");
-  if (misaligned16(a.x) || misaligned16(a.gy) || a.x_item % 4 || a.gy_item % 4)
-    return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: x / gy and their item strides must be 16-byte aligned");
-  const long long tiles = wgrad_tiles(a.n, a.H, a.W);
-  if (tiles > 0x7fffffffLL) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: too many tiles");
-  const int G = wgrad_grid(tiles);
-  if (!a.workspace || a.workspace_bytes < (size_t)G * PART * sizeof(float))
-    return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: workspace too small (stif_conv3x3_wgrad_workspace_size)");
-  if (misaligned16(a.workspace))
-    return stif_fail(STIF_E_INVALID, "stif_conv3x3_wgrad: workspace not 16-byte aligned");
+  return wgrad_entry<1>("stif_conv3x3_wgrad", pa, stream);
+}
+
+extern "C" size_t stif_conv3x3s2_wgrad_workspace_size(int n, int H, int W, int cin, int cout) {
+  return wgrad_workspace_size<2>(n, H, W, cin, cout);
+}
+
+extern "C" int stif_conv3x3s2_wgrad(const stif_conv_wgrad_args* pa, void* stream) {
+  return wgrad_entry<2>("stif_conv3x3s2_wgrad", pa, stream);
+}
+
+extern "C" size_t stif_conv3x3s2_dgrad_workspace_size(int, int, int) { return 0; }   // the weight is transposed in flight
+
+extern "C" int stif_conv3x3s2_dgrad(const float* gy, const float* w_oihw, float* gx, long long gy_item,
+                                    long long gx_item, int n, int H, int W, void*, size_t, void* stream) {
+  const char* fn = "stif_conv3x3s2_dgrad";
+  if (!gy || !w_oihw || !gx) return fail_as(fn, "null pointer (gy, w_oihw, gx)");
+  if (n < 1 || H < 1 || W < 1) return fail_as(fn, "n, H, W must be >= 1");
+  if (gy_item < 0 || gx_item < 0) return fail_as(fn, "negative item stride");
+  if ((long long)H * W * 64 * 4 >= 0x7fffffffLL) return fail_as(fn, "item larger than 2 GB (buffer addressing)");
+  if (misaligned16(gy) || misaligned16(gx) || gy_item % 4 || gx_item % 4)
+    return fail_as(fn, "gy / gx and their item strides must be 16-byte aligned");
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const int tiles_x = (Wo + DG_TW - 1) / DG_TW, tiles_per_item = tiles_x * ((Ho + DG_TH - 1) / DG_TH);
+  const long long tiles = (long long)n * tiles_per_item;
+  if (tiles > 0x7fffffffLL) return fail_as(fn, "too many tiles");
+  hipLaunchKernelGGL(k_dgrad_s2, dim3((unsigned)tiles), dim3(256), 0, static_cast<hipStream_t>(stream), gy, w_oihw, gx,
+                     gy_item, gx_item, H, W, Ho, Wo, tiles_x, tiles_per_item);
+  return stif_check_launch(fn);
+}
+
+extern "C" size_t stif_conv_first_wgrad_workspace_size(int n, int h, int w) {
+  if (n < 1 || h < 1 || w < 1) return 0;
+  const long long chunks = cf_chunks(n, h, w);
+  if (chunks > 0x7fffffffLL) return 0;
+  return (size_t)cf_grid(chunks) * CF_PART * sizeof(float);
+}
+
+extern "C" int stif_conv_first_wgrad(const float* x_nchw, const float* gy, float* gw, float* gb, long long gy_item,
+                                     int n, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "stif_conv_first_wgrad";
+  if (!x_nchw || !gy || !gw) return fail_as(fn, "null pointer (x, gy, gw)");
+  if (n < 1 || h < 1 || w < 1) return fail_as(fn, "n, H, W must be >= 1");
+  if (gy_item < 0) return fail_as(fn, "negative item stride");
+  if ((long long)h * w * 64 * 4 >= 0x7fffffffLL) return fail_as(fn, "item larger than 2 GB (buffer addressing)");
+  if (misaligned16(gy) || gy_item % 4) return fail_as(fn, "gy and its item stride must be 16-byte aligned");
+  const long long chunks = cf_chunks(n, h, w);
+  if (chunks > 0x7fffffffLL) return fail_as(fn, "too many tiles");
+  const int G = cf_grid(chunks);
+  if (!workspace || workspace_bytes < (size_t)G * CF_PART * sizeof(float))
+    return fail_as(fn, "workspace too small (stif_conv_first_wgrad_workspace_size)");
+  if (misaligned16(workspace)) return fail_as(fn, "workspace not 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int tiles_x = (a.W + TW - 1) / TW, tiles_per_item = tiles_x * ((a.H + TH - 1) / TH);
-  float* ws = static_cast<float*>(a.workspace);
-  hipLaunchKernelGGL(k_wgrad, dim3(G), dim3(256), 0, st, a.x, a.gy, ws, a.x_item, a.gy_item, a.H, a.W, tiles_x,
-                     tiles_per_item, (int)tiles);
-  if (int rc = stif_check_launch("stif_conv3x3_wgrad")) return rc;
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3((PART + 255) / 256), dim3(256), 0, st, ws, G, a.gw, a.gb);
-  return stif_check_launch("stif_conv3x3_wgrad (reduce)");
+  float* ws = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(k_cf_wgrad, dim3(G), dim3(256), 0, st, x_nchw, gy, ws, gy_item, h, w, (long long)n * h * w,
+                     (int)chunks);
+  if (int rc = stif_check_launch(fn)) return rc;
+  hipLaunchKernelGGL(k_cf_wgrad_reduce, dim3(CF_PART / 16), dim3(256), 0, st, ws, G, gw, gb);
+  return stif_check_launch("stif_conv_first_wgrad (reduce)");
+}
+
+extern "C" int stif_pack_conv_plain_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, float* w_dst,
+                                        float* b_dst, void* stream) {
+  const char* fn = "stif_pack_conv_plain_dev";
+  if (!w_oihw || !w_dst || !b_dst) return fail_as(fn, "null pointer (w_oihw, w_dst, b_dst)");
+  if (ks != 3) return fail_as(fn, "the device pack needs a 3x3 kernel");
+  if (cin != 64 || cout != 64) return fail_as(fn, "unsupported channel counts (64 -> 64 only)");
+  hipLaunchKernelGGL(k_pack_plain, dim3(64 * 64 * 9 / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, b,
+                     w_dst, b_dst);
+  return stif_check_launch(fn);
 }
 
 extern "C" int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, int mode,

@@ -248,6 +248,109 @@ def conv3x3_wgrad(x: torch.Tensor, gy: torch.Tensor):
     return gw, gb
 
 
+def _wgrad_workspace(device, nbytes: int):
+    """The (device, stream) partial-sum buffer conv3x3_wgrad uses, grown to ``nbytes``: the three weight-gradient
+    reductions share it (each finishes its reduce before the next launch on the stream starts)."""
+    s = torch.cuda.current_stream(device)
+    key = (s.device.index, s.cuda_stream)
+    ws = _WGRAD_WS.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _WGRAD_WS[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=device)
+    return ws, s.cuda_stream
+
+
+def conv3x3s2_wgrad(x: torch.Tensor, gy: torch.Tensor):
+    """Weight and bias gradient of the 3x3 / stride-2 / pad-1 / 64 -> 64 conv: NHWC ``x`` [n, H, W, 64] (the forward's
+    input) and ``gy`` [n, (H + 1) // 2, (W + 1) // 2, 64], conventions and determinism of conv3x3_wgrad.  Returns
+    (gw [64, 64, 3, 3] OIHW, gb [64])."""
+    if x.dim() != 4 or gy.dim() != 4 or x.shape[3] != 64:
+        raise ValueError(f"conv3x3s2_wgrad: x {tuple(x.shape)} and gy {tuple(gy.shape)} must be [n, H, W, 64] maps")
+    n, H, W, _ = x.shape
+    if tuple(gy.shape) != (n, (H + 1) // 2, (W + 1) // 2, 64):
+        raise ValueError(f"conv3x3s2_wgrad: gy {tuple(gy.shape)} is not the stride-2 output of x {tuple(x.shape)}")
+    x_item = _item_stride([x], "conv3x3s2_wgrad x")
+    gy_item = _item_stride([gy], "conv3x3s2_wgrad gy")
+    lib = L.lib()
+    ws, stream = _wgrad_workspace(x.device, lib.stif_conv3x3s2_wgrad_workspace_size(n, H, W, 64, 64))
+    gw = torch.empty(64, 64, 3, 3, dtype=torch.float32, device=x.device)
+    gb = torch.empty(64, dtype=torch.float32, device=x.device)
+    a = L.ConvWgradArgs()
+    a.x, a.gy, a.gw, a.gb = _vp(x), _vp(gy), _vp(gw), _vp(gb)
+    a.x_item, a.gy_item = x_item, gy_item
+    a.n, a.H, a.W, a.cin, a.cout = n, H, W, 64, 64
+    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
+    trace = None
+    if TRACE is not None:
+        px = n * gy.shape[1] * gy.shape[2]
+        trace = (("wgrad_s2",), 2.0 * 64 * 64 * 9 * px, 4.0 * 64 * (n * H * W + px))
+    _launch("stif_conv3x3s2_wgrad", trace, lib.stif_conv3x3s2_wgrad, C.byref(a), stream)
+    return gw, gb
+
+
+def conv3x3s2_dgrad(gy: torch.Tensor, weight: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Data gradient of the 3x3 / stride-2 / pad-1 / 64 -> 64 conv: NHWC ``gy`` [n, (H + 1) // 2, (W + 1) // 2, 64]
+    (any item stride) and the state dict's ``weight`` [64, 64, 3, 3] on the device; returns gx [n, H, W, 64]."""
+    if gy.dim() != 4 or tuple(gy.shape[1:]) != ((H + 1) // 2, (W + 1) // 2, 64):
+        raise ValueError(f"conv3x3s2_dgrad: gy {tuple(gy.shape)} is not the stride-2 output of a {H} x {W} map")
+    gy_item = _item_stride([gy], "conv3x3s2_dgrad gy")
+    if not (weight.is_cuda and weight.dtype == torch.float32) or tuple(weight.shape) != (64, 64, 3, 3):
+        raise ValueError("conv3x3s2_dgrad: expected a float32 CUDA weight [64, 64, 3, 3]")
+    weight = weight.detach().contiguous()
+    n = gy.shape[0]
+    gx = torch.empty(n, H, W, 64, dtype=torch.float32, device=gy.device)
+    trace = None
+    if TRACE is not None:
+        px = n * gy.shape[1] * gy.shape[2]
+        trace = (("dgrad_s2",), 2.0 * 64 * 64 * 9 * px, 4.0 * 64 * (n * H * W + px))
+    _launch("stif_conv3x3s2_dgrad", trace, L.lib().stif_conv3x3s2_dgrad, _vp(gy), _vp(weight), _vp(gx), gy_item,
+            H * W * 64, n, H, W, None, 0, torch.cuda.current_stream(gy.device).cuda_stream)
+    return gx
+
+
+def conv_first_wgrad(x_nchw: torch.Tensor, gy: torch.Tensor):
+    """Weight and bias gradient of conv_first (3 -> 64, 3x3 'same'): the contiguous NCHW frames ``x_nchw`` [n, 3, h, w]
+    as ops.conv_first reads them and NHWC ``gy`` [n, h, w, 64] (any item stride).  Returns (gw [64, 3, 3, 3], gb [64]);
+    repeated calls give identical bits."""
+    if x_nchw.dim() != 4 or x_nchw.shape[1] != 3 or gy.dim() != 4:
+        raise ValueError(f"conv_first_wgrad: x {tuple(x_nchw.shape)} must be [n, 3, h, w] and gy [n, h, w, 64]")
+    n, _, h, w = x_nchw.shape
+    if tuple(gy.shape) != (n, h, w, 64):
+        raise ValueError(f"conv_first_wgrad: gy {tuple(gy.shape)} != {(n, h, w, 64)}")
+    gy_item = _item_stride([gy], "conv_first_wgrad gy")
+    if not (x_nchw.is_cuda and x_nchw.dtype == torch.float32 and x_nchw.is_contiguous()):
+        raise ValueError("conv_first_wgrad: expected contiguous float32 CUDA frames")
+    lib = L.lib()
+    ws, stream = _wgrad_workspace(gy.device, lib.stif_conv_first_wgrad_workspace_size(n, h, w))
+    gw = torch.empty(64, 3, 3, 3, dtype=torch.float32, device=gy.device)
+    gb = torch.empty(64, dtype=torch.float32, device=gy.device)
+    trace = None
+    if TRACE is not None:
+        trace = (("cf_wgrad",), 2.0 * 64 * 28 * n * h * w, 4.0 * (64 + 3) * n * h * w)
+    _launch("stif_conv_first_wgrad", trace, lib.stif_conv_first_wgrad, _vp(x_nchw), _vp(gy), _vp(gw), _vp(gb), gy_item,
+            n, h, w, _vp(ws), ws.numel() * 4, stream)
+    return gw, gb
+
+
+def pack_conv_plain_dev(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> PackedConv:
+    """The fp32 direct-conv (PACK_PLAIN) packing of a 64 -> 64 3x3 layer on the device (stif_pack_conv_plain_dev):
+    the bytes ops.pack_conv writes, with nothing passing through the host -- the layer ops.conv2d(stride=2) reads."""
+    if not (weight.is_cuda and weight.dtype == torch.float32):
+        raise ValueError("pack_conv_plain_dev: expected a float32 CUDA weight")
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
+        raise ValueError("pack_conv_plain_dev: expected a float32 CUDA bias")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise ValueError(f"pack_conv_plain_dev: weight shape {tuple(weight.shape)} is not [cout, cin, k, k]")
+    weight = weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    cout, cin, ks, _ = weight.shape
+    lib = L.lib()
+    wd = torch.empty(lib.stif_conv_weight_floats(cout, cin, ks, L.PACK_PLAIN), dtype=torch.float32, device=weight.device)
+    bd = torch.empty(lib.stif_conv_bias_floats(cout, L.PACK_PLAIN), dtype=torch.float32, device=weight.device)
+    _launch("stif_pack_conv_plain_dev", None, lib.stif_pack_conv_plain_dev, _vp(weight), _vp(bias), cout, cin, ks,
+            _vp(wd), _vp(bd), _stream())
+    return PackedConv(wd, bd, cout, cin, ks, L.PACK_PLAIN)
+
+
 def upsample2x(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0):
     """out = scale * bilinear x2 upsample (align_corners=False) of NHWC x [n, h, w, c] (items may be
     strided; pixels contiguous) into out [n, 2h, 2w, c]."""

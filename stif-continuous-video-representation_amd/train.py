@@ -26,6 +26,11 @@ trunks through the modules below.
   gradient always uses exact fp32 products.  The f16x3 operand range is reported through one device status word
   per device: ``module.range_status()`` reads and clears it (one sync).  A step that ends with a non-zero
   status used an operand outside the split range somewhere and must be redone with ``mfma="f32"``.
+* ``ConvDown``, ``ConvFirst``, ``FrameFeatures`` -- the per-frame encoder (Sakuya_arch_test.py:282-287, :318-325)
+  with the reference's parameter names: the stride-2 pyramid convs (forward stif_conv2d_nhwc with the weight packed
+  on the device, backward stif_conv3x3s2_wgrad / stif_conv3x3s2_dgrad) and conv_first (stif_conv_first, backward
+  stif_conv_first_wgrad), all fp32, around the trunk and two ``Conv3x3``.  The gradient with respect to the input
+  frames is not built.
 """
 from __future__ import annotations
 
@@ -324,3 +329,136 @@ def make_trunk(n_blocks: int, nf: int = 64, mfma: str = "f16x3") -> nn.Sequentia
     ``recon_trunk.*`` / ``feature_extraction.*`` slices of a LunaTokis state dict load with ``strict=True``.
     ``trunk[0].range_status()`` (or ``train.range_status()``) reports the f16x3 range for the whole trunk."""
     return nn.Sequential(*[ResidualBlock_noBN(nf, mfma) for _ in range(n_blocks)])
+
+
+# ---- the per-frame encoder: conv_first, the stride-2 pyramid convs, FrameFeatures ----
+
+_DOWN_EPI = {None: L.EPI_NONE, "lrelu": L.EPI_LRELU}   # the epilogues the stride-2 forward kernel has
+
+
+class _ConvDownFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        xh = _nhwc(x, "ConvDown")
+        n, H, W, _ = xh.shape
+        out = torch.empty(n, (H + 1) // 2, (W + 1) // 2, 64, dtype=torch.float32, device=xh.device)
+        ops.conv2d([dict(layer=ops.pack_conv_plain_dev(weight, bias), in0=xh, out=out)], epi=_DOWN_EPI[act], stride=2)
+        ctx.act = act
+        ctx.save_for_backward(xh, weight, out if act else None)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xh, weight, out = ctx.saved_tensors
+        g = _nhwc(grad_out, "ConvDown backward")
+        if ctx.act == "lrelu":
+            g = torch.where(out > 0, g, g * 0.1)
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        gx = gw = gb = None
+        if need_w or need_b:
+            gw, gb = ops.conv3x3s2_wgrad(xh, g)
+        if need_x:
+            gx = ops.conv3x3s2_dgrad(g, weight, xh.shape[1], xh.shape[2]).permute(0, 3, 1, 2)
+        return gx, gw if need_w else None, gb if need_b else None, None
+
+
+class ConvDown(nn.Module):
+    """nn.Conv2d(64, 64, 3, 2, 1) with an optional fused LeakyReLU(0.1) (the pyramid's fea_L*_conv1), forward and
+    backward on the HIP kernels in fp32: the forward is stif_conv2d_nhwc with the weight packed on the device, the
+    backward stif_conv3x3s2_wgrad and stif_conv3x3s2_dgrad.  ``weight`` / ``bias`` as nn.Conv2d's; logical NCHW in
+    and out, ``channels_last`` used in place."""
+
+    def __init__(self, nf: int = 64, act="lrelu"):
+        super().__init__()
+        if nf != 64:
+            raise ValueError(f"the HIP conv backward covers 64 -> 64 channels only, got nf = {nf}")
+        if act not in _DOWN_EPI:
+            raise ValueError(f"act must be None or 'lrelu' (the stride-2 forward kernel's epilogues), got {act!r}")
+        self.act = act
+        self.weight = nn.Parameter(torch.empty(nf, nf, 3, 3))
+        self.bias = nn.Parameter(torch.empty(nf))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(nf * 9)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x):
+        return _ConvDownFn.apply(x, self.weight, self.bias, self.act)
+
+    def extra_repr(self):
+        return f"64, 64, kernel_size=(3, 3), stride=2, padding=1, act={self.act}"
+
+
+class _ConvFirstFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, frames, weight, bias):
+        n, _, H, W = frames.shape
+        out = torch.empty(n, H, W, 64, dtype=torch.float32, device=frames.device)
+        ops.conv_first(frames, weight.detach().contiguous(), bias.detach().contiguous(), out)
+        ctx.save_for_backward(frames, out)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        frames, out = ctx.saved_tensors
+        g = _nhwc(grad_out, "ConvFirst backward")
+        g = torch.where(out > 0, g, g * 0.1)
+        need_w, need_b = ctx.needs_input_grad[1:3]
+        gw = gb = None
+        if need_w or need_b:
+            gw, gb = ops.conv_first_wgrad(frames, g)
+        return None, gw if need_w else None, gb if need_b else None
+
+
+class ConvFirst(nn.Module):
+    """nn.Conv2d(3, 64, 3, 1, 1) + LeakyReLU(0.1) (Sakuya_arch_test.py:282, :318): forward on stif_conv_first,
+    weight / bias gradient on stif_conv_first_wgrad.  The gradient with respect to the frames is not built: an
+    input that requires grad is refused."""
+
+    def __init__(self):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(64, 3, 3, 3))
+        self.bias = nn.Parameter(torch.empty(64))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(27)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, frames):
+        if frames.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("ConvFirst: the gradient with respect to the input frames is not built "
+                                      "(pass frames that do not require grad)")
+        if not frames.is_cuda:
+            raise RuntimeError(f"ConvFirst: the HIP convolution kernels need a CUDA tensor, got one on {frames.device} "
+                               "(move the module and its input to the GPU)")
+        if frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 3:
+            raise RuntimeError(f"ConvFirst: expected a float32 [n, 3, H, W] tensor, got {frames.dtype} "
+                               f"{tuple(frames.shape)}")
+        return _ConvFirstFn.apply(frames.detach().contiguous(), self.weight, self.bias)
+
+    def extra_repr(self):
+        return "3, 64, kernel_size=(3, 3), padding=1, act=lrelu"
+
+
+class FrameFeatures(nn.Module):
+    """The reference's per-frame encoder (Sakuya_arch_test.py:282-287, :318-325) with its parameter names, so the
+    ``conv_first.*``, ``feature_extraction.*`` and ``fea_L*_conv*`` slices of a LunaTokis state dict load with
+    ``strict=True``: frames [n, 3, H, W] -> (L1, L2, L3), every conv forward and backward on the HIP kernels.
+    ``mfma`` selects the operand mode of the Winograd convs; conv_first and the stride-2 convs are fp32."""
+
+    def __init__(self, front_RBs: int = 5, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, "lrelu", mfma)
+        self.conv_first = ConvFirst()
+        self.feature_extraction = make_trunk(front_RBs, 64, mfma)
+        self.fea_L2_conv1 = ConvDown(64, "lrelu")
+        self.fea_L2_conv2 = Conv3x3(64, "lrelu", mfma)
+        self.fea_L3_conv1 = ConvDown(64, "lrelu")
+        self.fea_L3_conv2 = Conv3x3(64, "lrelu", mfma)
+
+    def forward(self, frames):
+        L1 = self.feature_extraction(self.conv_first(frames))
+        L2 = self.fea_L2_conv2(self.fea_L2_conv1(L1))
+        L3 = self.fea_L3_conv2(self.fea_L3_conv1(L2))
+        return L1, L2, L3
+
+    def range_status(self) -> int:
+        return range_status(self.conv_first.weight.device)
