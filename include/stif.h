@@ -162,6 +162,45 @@ size_t stif_conv_first_wgrad_workspace_size(int n, int h, int w);
 int stif_conv_first_wgrad(const float* x_nchw, const float* gy, float* gw, float* gb, long long gy_item,
                           int n, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The weight and bias gradient of stif_conv3x3_wgrad in 64 x 64 channel blocks, for the 3x3 'same' convs of PCD_Align
+ * whose input or output is wider than 64 channels (training):
+ *   gw[co][64 i + ci][kh][kw] = sum_{n,y,x} gy[n][y][x][co] * x[i][n][y + kh - 1][x + kw - 1][ci],  co < cout,
+ *   gb[co] = sum_{n,y,x} gy[n][y][x][co].
+ * x[0], x[1]: the halves of the forward's concatenated input (nx = 2; the concatenation is never built), NHWC
+ * 64-channel maps; gy: NHWC with a pixel pitch of gy_channels floats of which the first cout count (the rest is never read).
+ * Supported (nx, gy_channels, cout): (2, 64, 64) the 128 -> 64 concatenation convs, (1, 256, 216) conv_offset_mask
+ * with its gradient in the zero-padded 256-channel map the Winograd conv writes, (1, 64, 64) = stif_conv3x3_wgrad.
+ * One launch computes every block (cout slice, x map) as stif_conv3x3_wgrad's walk over the same tiles with the same
+ * grid, one partial per workgroup and block, and a second adds each block's partials in index order: no
+ * floating-point atomics, identical bits for repeated calls, and every 64 x 64 block of gw equals
+ * stif_conv3x3_wgrad's result for the same two 64-channel maps.  workspace: at least
+ * stif_conv3x3_wgrad_cat_workspace_size bytes (blocks x stif_conv3x3_wgrad_workspace_size), 16-B aligned.
+ * STIF_E_INVALID, each with its reason, before any launch: null args, a null x[0] / gy / gw, nx = 2 with a null x[1],
+ * n / H / W < 1, other channel counts, a negative or misaligned stride or base, an item of 2 GB or more (H W
+ * gy_channels floats), a workspace that is missing, too small or misaligned.  Zero-initialise the struct, then fill. */
+typedef struct {
+  const float* x[2];       /* the halves of the forward's concatenated input, NHWC [n][H][W][64] each */
+  const float* gy;         /* NHWC [n][H][W][gy_channels] */
+  float* gw;               /* [cout][64 * nx][3][3], OIHW as the state dict has it */
+  float* gb;               /* [cout] or NULL */
+  long long x_item[2], gy_item;
+  int n, H, W;
+  int nx;                  /* 1 or 2 */
+  int gy_channels, cout;   /* (64, 64) or (256, 216): the pixel pitch of gy and the channels that count */
+  void* workspace;
+  size_t workspace_bytes;
+} stif_conv_wgrad_cat_args;
+/* 0 for sizes < 1 or unsupported channel counts. */
+size_t stif_conv3x3_wgrad_cat_workspace_size(int n, int H, int W, int nx, int gy_channels, int cout);
+int stif_conv3x3_wgrad_cat(const stif_conv_wgrad_cat_args* args, void* stream);
+
+/* The adjoint of stif_upsample2x_nhwc: gx = the transpose of scale * F.interpolate(scale_factor=2, bilinear,
+ * align_corners=False) applied to gy [n][2 h1][2 w1][c]; gx [n][h1][w1][c], c % 4 == 0, items gy_item / gx_item floats
+ * apart (>= 0, multiples of 4; bases 16-B aligned).  Gather form: every gx element is written once, by one lane, from a
+ * 4 x 4 window of gy in a fixed addition order (no atomics); h1 = 1 and w1 = 1 are served. */
+int stif_upsample2x_bwd_nhwc(const float* gy, float* gx, int n, int h1, int w1, int c, float scale,
+                             long long gy_item, long long gx_item, void* stream);
+
 /* out = scale * F.interpolate(in, scale_factor=2, mode='bilinear', align_corners=False) on NHWC
  * maps (PCD_Align's coarse-to-fine step, Sakuya_arch_test.py:86-87); in [n][h1][w1][c],
  * out [n][2h1][2w1][c], items `in_item` / `out_item` floats apart, c % 4 == 0. */
@@ -394,6 +433,17 @@ int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, int cout, int
  * stif_conv2d_nhwc with no host packing and no synchronisation. */
 int stif_pack_conv_plain_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, float* w_dst,
                              float* b_dst, void* stream);
+/* stif_pack_conv_weight_dev for one 64 x 64 block of a larger 3x3 weight: rows [co0, co0 + 64) and columns
+ * [ci0, ci0 + 64) of the OIHW weight [cout][cin][3][3], cout 64 or 216, cin 64 or 128, co0 / ci0 multiples of 64
+ * inside it (anything else is STIF_E_INVALID before the launch); rows at or past cout read as zeros, and so does
+ * their bias.  Writes one 64 -> 64 pack (stif_conv_weight_floats(64, 64, 3, mode) floats) at w_dst and 64 biases
+ * (b[co0 ..], zeros with STIF_PACK_DGRAD) at b_dst; modes, flags and status as stif_pack_conv_weight_dev.  A Winograd
+ * pack is [cout slice][cin chunk]..., so block packs laid end to end are the packs of wider layers: the two column
+ * blocks of a [64][128] weight are its pack, the four row blocks of a [216][64] weight are its pack (216 rows padded
+ * to 256), the four STIF_PACK_DGRAD row blocks of [216][64] are the data gradient's 256 -> 64 weight, and the
+ * STIF_PACK_DGRAD pack of one column block of [64][128] is the data gradient's weight for that input half. */
+int stif_pack_conv_block_dev(const float* w_oihw, const float* b, int cout, int cin, int co0, int ci0, int mode,
+                             int flags, float* w_dst, float* b_dst, int* status, void* stream);
 
 size_t stif_dec_proj_floats(void);   /* packed fp32 1x1 weight of the LR projection: [25][256][1][8]; the
                                         f16x3 packing: stif_conv_weight_floats(256, 200, 1, STIF_PACK_PLAIN | STIF_PACK_F16X3) */

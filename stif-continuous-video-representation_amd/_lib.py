@@ -65,6 +65,16 @@ class ConvWgradArgs(C.Structure):
     ]
 
 
+class ConvWgradCatArgs(C.Structure):
+    """stif_conv_wgrad_cat_args: the weight gradient in 64 x 64 channel blocks -- one or two 64-channel x maps, gy with
+    a pixel pitch of gy_channels floats of which the first cout count, gw [cout][64 nx][3][3]."""
+    _fields_ = [
+        ("x", _P * 2), ("gy", _P), ("gw", _P), ("gb", _P), ("x_item", C.c_longlong * 2), ("gy_item", C.c_longlong),
+        ("n", C.c_int), ("H", C.c_int), ("W", C.c_int), ("nx", C.c_int), ("gy_channels", C.c_int), ("cout", C.c_int),
+        ("workspace", _P), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class DecTables(C.Structure):
     _fields_ = [(n, _P) for n in ("near_y", "rel_y", "by0", "by1", "wy0", "wy1", "lin_y",
                                   "near_x", "rel_x", "bx0", "bx1", "wx0", "wx1", "lin_x", "hr_y", "hr_x")]
@@ -148,6 +158,11 @@ EXPORTS = {
     "stif_conv_first_wgrad_workspace_size": (C.c_size_t, [C.c_int] * 3),
     "stif_conv_first_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "stif_pack_conv_plain_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "stif_conv3x3_wgrad_cat_workspace_size": (C.c_size_t, [C.c_int] * 6),
+    "stif_conv3x3_wgrad_cat": (C.c_int, [C.POINTER(ConvWgradCatArgs), _P]),
+    "stif_upsample2x_bwd_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,
+                                           C.c_longlong, _P]),
+    "stif_pack_conv_block_dev": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P, _P, _P]),
     "stif_upsample2x_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,
                                        C.c_longlong, _P]),
     "stif_conv_first": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -5,6 +5,9 @@
 // And the backward of the frame encoder's other three convs: the weight gradient of the
 // stride-2 convs (the same kernel, a template on the stride), their data gradient (a transposed conv, split by output
 // parity), the weight gradient of conv_first (3 -> 64), and the STIF_PACK_PLAIN packer on the device.
+// And what PCD_Align's backward lacked: the weight gradient in 64 x 64 channel blocks (the
+// 128 -> 64 concatenation convs, the 64 -> 216 offset / mask conv), the adjoint of the x2 bilinear upsample, and the
+// Winograd packer for a 64 x 64 block of a wider weight.
 #include <algorithm>
 #include <cstdio>
 
@@ -113,6 +116,114 @@ void k_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* _
   if (cit == 0 && hf == 0) part[GW_FLOATS + cot * 32 + l32] = bsum + other;
 }
 
+// The weight gradient in 64 x 64 channel blocks, a sibling of k_wgrad<1> -- a shared template
+// cost k_wgrad two VGPRs.  blockIdx.y = slice * nx + xi is the block of cout slice `slice` (gy channels co0 = 64 slice
+// .. of a pixel pitch of gc floats; channels at or past cout are zeros in LDS and never loaded) against the input map
+// x[xi].  Every block is k_wgrad<1>'s walk: the same tiles, grid, staging and k order, one partial per workgroup and
+// block (block-major in the workspace), so its sums are the bits stif_conv3x3_wgrad computes for the same two
+// 64-channel maps.  The x tile is staged once per block (four times for the 216 form): the loop is MFMA-paced.
+struct WgradCat {
+  const float* x[2];
+  long long x_item[2];
+  int nx, gc, cout;
+};
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG_PER_CU)))
+void k_wgrad_cat(WgradCat c, const float* __restrict__ gy, float* __restrict__ ws, long long gy_item, int H, int W,
+                 int tiles_x, int tiles_per_item, int ntiles) {
+  constexpr int S = 1;   // S, Ho, Wo are kept so that the body below reads line for line as k_wgrad's
+  const int blk = blockIdx.y, slice = blk / c.nx, xi_ = blk - slice * c.nx, co0 = slice * 64, GC = c.gc, cv = c.cout;
+  const float* __restrict__ x = xi_ ? c.x[1] : c.x[0];
+  const long long x_item = xi_ ? c.x_item[1] : c.x_item[0];
+  const int Ho = H, Wo = W;
+  constexpr int TH = WgradTile<S>::TH, TW = WgradTile<S>::TW, XH = WgradTile<S>::XH, XW = WgradTile<S>::XW;
+  __shared__ __attribute__((aligned(16))) float s_x[XH * XW * 64];
+  __shared__ __attribute__((aligned(16))) float s_gy[TH * TW * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cot = wave >> 1, cit = wave & 1, l32 = lane & 31, hf = lane >> 5;
+  f32x16 acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  float bsum = 0.f;   // sum of this lane's gy values: cout cot * 32 + l32, pixels of parity hf
+
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int n = t / tiles_per_item, rem = t - n * tiles_per_item, ty = rem / tiles_x, tx = rem - ty * tiles_x;
+    const int y0 = ty * TH, x0 = tx * TW;
+    const float* xi = x + (size_t)n * x_item;
+    const float* gi = gy + (size_t)n * gy_item;
+    __syncthreads();   // the previous tile's reads are done
+#pragma unroll
+    for (int k = 0; k < (XH * XW * 16 + 255) / 256; ++k) {
+      const int i = tid + k * 256;
+      if (i < XH * XW * 16) {
+        const int c4 = i & 15, p = i >> 4, py = p / XW, px = p - py * XW;
+        const int yy = S * y0 + py - 1, xx = S * x0 + px - 1;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = ld4(xi + ((size_t)yy * W + xx) * 64 + c4 * 4);
+        st4(s_x + p * 64 + c4 * 4, v);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < TH * TW * 16 / 256; ++k) {
+      const int i = tid + k * 256;
+      const int c4 = i & 15, p = i >> 4, py = p / TW, px = p - py * TW;
+      const int yy = y0 + py, xx = x0 + px;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (yy < Ho && xx < Wo && co0 + c4 * 4 < cv) v = ld4(gi + ((size_t)yy * Wo + xx) * GC + co0 + c4 * 4);
+      st4(s_gy + p * 64 + c4 * 4, v);
+    }
+    __syncthreads();
+    // k step (r, xs): gy pixels (r, 2 xs + hf) of the tile; tap (kh, kw) reads x tile pixel
+    // (S r + kh, S (2 xs + hf) + kw)
+    const float* ap = s_gy + hf * 64 + cot * 32 + l32;
+    const float* bp = s_x + S * hf * 64 + cit * 32 + l32;
+#pragma unroll
+    for (int r = 0; r < TH; ++r) {
+#pragma unroll 2
+      for (int xs = 0; xs < TW / 2; ++xs) {
+        const float a = ap[(r * TW + 2 * xs) * 64];
+        bsum += a;
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw)
+            acc[kh * 3 + kw] = mfma32(a, bp[((S * r + kh) * XW + S * 2 * xs + kw) * 64], acc[kh * 3 + kw]);
+      }
+    }
+  }
+
+  float* part = ws + ((size_t)blk * gridDim.x + blockIdx.x) * PART;
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      part[t * 4096 + (cot * 32 + mfma_row(r, lane)) * 64 + cit * 32 + l32] = acc[t][r];
+  const float other = __shfl_xor(bsum, 32);
+  if (cit == 0 && hf == 0) part[GW_FLOATS + cot * 32 + l32] = bsum + other;
+}
+
+// gw / gb of every block = its G partials summed in index order; gw stored OIHW with rows of 64 nx input channels,
+// rows at or past cout skipped, gb from the blocks of x[0]
+__global__ __launch_bounds__(256) void k_wgrad_cat_reduce(const float* __restrict__ ws, int G, float* __restrict__ gw,
+                                                          float* __restrict__ gb, int nx, int cout) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= PART) return;
+  const int blk = blockIdx.y, slice = blk / nx, xi = blk - slice * nx;
+  const float* p = ws + (size_t)blk * G * PART;
+  float s = 0.f;
+#pragma unroll 8
+  for (int g = 0; g < G; ++g) s += p[(size_t)g * PART + idx];
+  if (idx < GW_FLOATS) {
+    const int tap = idx >> 12, co = slice * 64 + ((idx >> 6) & 63), ci = xi * 64 + (idx & 63);
+    if (co < cout) gw[((size_t)co * 64 * nx + ci) * 9 + tap] = s;
+  } else if (gb != nullptr && xi == 0) {
+    const int co = slice * 64 + idx - GW_FLOATS;
+    if (co < cout) gb[co] = s;
+  }
+}
+
 // gw / gb = the G partials summed in index order; gw stored OIHW
 __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ ws, int G, float* __restrict__ gw,
                                                       float* __restrict__ gb) {
@@ -203,17 +314,20 @@ __device__ void wino_u_dev(const float* g, double u[4][4]) {
     for (int b = 0; b < 4; ++b) u[a][b] = t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2];
 }
 
-// one thread per (packed cout, packed cin) of the 64 -> 64 weight; dgrad: the data gradient's weight
-// w'[ci][co][kh][kw] = w[co][ci][2 - kh][2 - kw] with a zero bias
+// one thread per (packed cout, packed cin) of a 64 -> 64 pack: the block of rows co0.. and columns ci0.. of the OIHW
+// weight [cout][cin][3][3] (the whole weight for cout = cin = 64), rows at or past cout reading as zeros; dgrad:
+// the data gradient's weight of that block, w'[ci][co][kh][kw] = w[co0 + co][ci0 + ci][2 - kh][2 - kw], and a zero
+// bias
 __global__ __launch_bounds__(256) void k_pack_wino(const float* __restrict__ w, const float* __restrict__ b,
                                                    float* __restrict__ w_dst, float* __restrict__ b_dst, int* status,
-                                                   int f16, int dgrad) {
+                                                   int f16, int dgrad, int cout, int cin, int co0, int ci0) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int co = idx >> 6, ci = idx & 63;
-  const float* src = w + (size_t)(dgrad ? ci * 64 + co : co * 64 + ci) * 9;
+  const int row = co0 + (dgrad ? ci : co), col = ci0 + (dgrad ? co : ci);
+  const float* src = w + ((size_t)row * cin + col) * 9;
   float g[9];
 #pragma unroll
-  for (int q = 0; q < 9; ++q) g[q] = src[dgrad ? 8 - q : q];
+  for (int q = 0; q < 9; ++q) g[q] = row < cout ? src[dgrad ? 8 - q : q] : 0.f;
   double u[4][4];
   wino_u_dev(g, u);
   const int nt = co >> 5, l = (co & 31) + 32 * ((ci >> 2) & 1);
@@ -241,7 +355,37 @@ __global__ __launch_bounds__(256) void k_pack_wino(const float* __restrict__ w, 
       }
     if (bad) atomicOr(status, STIF_STATUS_PACK_RANGE);
   }
-  if (ci == 0) b_dst[co] = (dgrad || b == nullptr) ? 0.f : b[co];
+  if (ci == 0) b_dst[co] = (dgrad || b == nullptr || co0 + co >= cout) ? 0.f : b[co0 + co];
+}
+
+// ---- the adjoint of the x2 bilinear upsample (align_corners = False), gather form ----
+//
+// Along an axis output 2 i is 0.25 x[i - 1] + 0.75 x[i] and output 2 i + 1 is 0.75 x[i] + 0.25 x[i + 1], with the
+// neighbour clamped into the map at the two borders.  So x[i] receives 0.25, 0.75, 0.75, 0.25 of g[2 i - 1 .. 2 i + 2],
+// and the clamped border's extra 0.25 g[0] (i = 0) and 0.25 g[2 n - 1] (i = n - 1) are exactly the out-of-range taps
+// with their index clamped into [0, 2 n): one rule for every pixel, n = 1 included.  One thread owns four channels of
+// one gx pixel: 16 float4 loads of gy (4 x 4 window, columns first), a fixed addition order, no atomics.
+// grid (x blocks over w1 * c / 4, gx row, item)
+__global__ __launch_bounds__(256) void k_up2_bwd(const float* __restrict__ gy, float* __restrict__ gx, int h1, int w1,
+                                                 int c, float scale, long long gy_item, long long gx_item) {
+  const int c4n = c >> 2, i = blockIdx.y, item = blockIdx.z;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= w1 * c4n) return;
+  const int j = t / c4n, q = t - j * c4n, H = 2 * h1, W = 2 * w1;
+  const float* src = gy + (size_t)item * gy_item + q * 4;
+  int cols[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) cols[b] = min(max(2 * j - 1 + b, 0), W - 1);
+  f32x4 r[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const float* row = src + (size_t)min(max(2 * i - 1 + a, 0), H - 1) * W * c;
+    const f32x4 v0 = ld4(row + (size_t)cols[0] * c), v1 = ld4(row + (size_t)cols[1] * c);
+    const f32x4 v2 = ld4(row + (size_t)cols[2] * c), v3 = ld4(row + (size_t)cols[3] * c);
+    r[a] = 0.25f * (v0 + v3) + 0.75f * (v1 + v2);
+  }
+  const f32x4 v = (0.25f * (r[0] + r[3]) + 0.75f * (r[1] + r[2])) * scale;
+  st4(gx + (size_t)item * gx_item + ((size_t)i * w1 + j) * c + q * 4, v);
 }
 
 // ---- the direct-conv (STIF_PACK_PLAIN) packing on the device: the bytes of pack.cpp's plain loop, 64 -> 64 3x3 ----
@@ -453,6 +597,13 @@ int fail_as(const char* fn, const char* why) {
   return stif_fail(STIF_E_INVALID, msg);
 }
 
+// the (cout slice, x map) blocks of a supported (nx, gy_channels, cout), 0 for anything else
+int wgrad_cat_blocks(int nx, int gy_channels, int cout) {
+  if (gy_channels == 64 && cout == 64 && (nx == 1 || nx == 2)) return nx;
+  if (gy_channels == 256 && cout == 216 && nx == 1) return 4;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" size_t stif_conv3x3_wgrad_workspace_size(int n, int H, int W, int cin, int cout) {
@@ -469,6 +620,64 @@ extern "C" size_t stif_conv3x3s2_wgrad_workspace_size(int n, int H, int W, int c
 
 extern "C" int stif_conv3x3s2_wgrad(const stif_conv_wgrad_args* pa, void* stream) {
   return wgrad_entry<2>("stif_conv3x3s2_wgrad", pa, stream);
+}
+
+extern "C" size_t stif_conv3x3_wgrad_cat_workspace_size(int n, int H, int W, int nx, int gy_channels, int cout) {
+  return (size_t)wgrad_cat_blocks(nx, gy_channels, cout) * wgrad_workspace_size<1>(n, H, W, 64, 64);
+}
+
+extern "C" int stif_conv3x3_wgrad_cat(const stif_conv_wgrad_cat_args* pa, void* stream) {
+  const char* fn = "stif_conv3x3_wgrad_cat";
+  constexpr int TH = WgradTile<1>::TH, TW = WgradTile<1>::TW;
+  if (!pa) return fail_as(fn, "null args");
+  const stif_conv_wgrad_cat_args& a = *pa;
+  if (!a.x[0] || !a.gy || !a.gw) return fail_as(fn, "null pointer (x[0], gy, gw)");
+  if (a.n < 1 || a.H < 1 || a.W < 1) return fail_as(fn, "n, H, W must be >= 1");
+  const int blocks = wgrad_cat_blocks(a.nx, a.gy_channels, a.cout);
+  if (!blocks) return fail_as(fn, "unsupported channel counts (nx, gy_channels, cout: 2/64/64, 1/256/216, 1/64/64)");
+  const bool two = a.nx == 2;
+  if (two && !a.x[1]) return fail_as(fn, "null pointer (x[1] with nx = 2)");
+  if (a.x_item[0] < 0 || (two && a.x_item[1] < 0) || a.gy_item < 0) return fail_as(fn, "negative item stride");
+  if ((long long)a.H * a.W * a.gy_channels * 4 >= 0x7fffffffLL)
+    return fail_as(fn, "item larger than 2 GB (buffer addressing)");
+  if (misaligned16(a.x[0]) || (two && misaligned16(a.x[1])) || misaligned16(a.gy) || a.x_item[0] % 4 ||
+      (two && a.x_item[1] % 4) || a.gy_item % 4)
+    return fail_as(fn, "x / gy and their item strides must be 16-byte aligned");
+  const long long tiles = wgrad_tiles<1>(a.n, a.H, a.W);
+  if (tiles > 0x7fffffffLL) return fail_as(fn, "too many tiles");
+  const int G = wgrad_grid(tiles);
+  if (!a.workspace || a.workspace_bytes < (size_t)blocks * G * PART * sizeof(float))
+    return fail_as(fn, "workspace too small (stif_conv3x3_wgrad_cat_workspace_size)");
+  if (misaligned16(a.workspace)) return fail_as(fn, "workspace not 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int tiles_x = (a.W + TW - 1) / TW, tiles_per_item = tiles_x * ((a.H + TH - 1) / TH);
+  float* ws = static_cast<float*>(a.workspace);
+  WgradCat c{{a.x[0], two ? a.x[1] : a.x[0]}, {a.x_item[0], two ? a.x_item[1] : a.x_item[0]}, a.nx, a.gy_channels,
+             a.cout};
+  hipLaunchKernelGGL(k_wgrad_cat, dim3(G, blocks), dim3(256), 0, st, c, a.gy, ws, a.gy_item, a.H, a.W, tiles_x,
+                     tiles_per_item, (int)tiles);
+  if (int rc = stif_check_launch(fn)) return rc;
+  hipLaunchKernelGGL(k_wgrad_cat_reduce, dim3((PART + 255) / 256, blocks), dim3(256), 0, st, ws, G, a.gw, a.gb, a.nx,
+                     a.cout);
+  return stif_check_launch("stif_conv3x3_wgrad_cat (reduce)");
+}
+
+extern "C" int stif_upsample2x_bwd_nhwc(const float* gy, float* gx, int n, int h1, int w1, int c, float scale,
+                                        long long gy_item, long long gx_item, void* stream) {
+  const char* fn = "stif_upsample2x_bwd_nhwc";
+  if (!gy || !gx) return fail_as(fn, "null pointer (gy, gx)");
+  if (n < 1 || h1 < 1 || w1 < 1) return fail_as(fn, "n, h1, w1 must be >= 1");
+  if (c < 4 || c % 4) return fail_as(fn, "c must be a positive multiple of 4");
+  if (gy_item < 0 || gx_item < 0) return fail_as(fn, "negative item stride");
+  if (misaligned16(gy) || misaligned16(gx) || gy_item % 4 || gx_item % 4)
+    return fail_as(fn, "gy / gx and their item strides must be 16-byte aligned");
+  if (n > 1 && gx_item < (long long)h1 * w1 * c) return fail_as(fn, "gx items overlap (gx_item < h1 * w1 * c)");
+  if (h1 > 65535 || n > 65535 || (long long)w1 * (c / 4) > 0x7fffffffLL - 255)
+    return fail_as(fn, "image too large for the row grid");
+  const dim3 grid((unsigned)((w1 * (c / 4) + 255) / 256), (unsigned)h1, (unsigned)n);
+  hipLaunchKernelGGL(k_up2_bwd, grid, dim3(256), 0, static_cast<hipStream_t>(stream), gy, gx, h1, w1, c, scale,
+                     gy_item, gx_item);
+  return stif_check_launch(fn);
 }
 
 extern "C" size_t stif_conv3x3s2_dgrad_workspace_size(int, int, int) { return 0; }   // the weight is transposed in flight
@@ -548,6 +757,25 @@ extern "C" int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, in
   if (f16 && !status)
     return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: STIF_PACK_F16X3 needs a status word (range report)");
   hipLaunchKernelGGL(k_pack_wino, dim3(16), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, b, w_dst, b_dst,
-                     status, f16 ? 1 : 0, dgrad ? 1 : 0);
+                     status, f16 ? 1 : 0, dgrad ? 1 : 0, 64, 64, 0, 0);
   return stif_check_launch("stif_pack_conv_weight_dev");
+}
+
+extern "C" int stif_pack_conv_block_dev(const float* w_oihw, const float* b, int cout, int cin, int co0, int ci0,
+                                        int mode, int flags, float* w_dst, float* b_dst, int* status, void* stream) {
+  const char* fn = "stif_pack_conv_block_dev";
+  if (!w_oihw || !w_dst || !b_dst) return fail_as(fn, "null pointer (w_oihw, w_dst, b_dst)");
+  if (mode != STIF_PACK_WINO && mode != (STIF_PACK_WINO | STIF_PACK_F16X3))
+    return fail_as(fn, "unsupported mode (STIF_PACK_WINO [| STIF_PACK_F16X3] only)");
+  if ((cout != 64 && cout != 216) || (cin != 64 && cin != 128))
+    return fail_as(fn, "unsupported channel counts (cout 64 or 216, cin 64 or 128)");
+  if (co0 < 0 || co0 % 64 || co0 >= cout || ci0 < 0 || ci0 % 64 || ci0 >= cin)
+    return fail_as(fn, "co0 / ci0 must be multiples of 64 inside the weight");
+  if (flags & ~STIF_PACK_DGRAD) return fail_as(fn, "unknown flags");
+  const bool dgrad = (flags & STIF_PACK_DGRAD) != 0, f16 = (mode & STIF_PACK_F16X3) != 0;
+  if (!b && !dgrad) return fail_as(fn, "null bias (allowed with STIF_PACK_DGRAD only)");
+  if (f16 && !status) return fail_as(fn, "STIF_PACK_F16X3 needs a status word (range report)");
+  hipLaunchKernelGGL(k_pack_wino, dim3(16), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, b, w_dst, b_dst,
+                     status, f16 ? 1 : 0, dgrad ? 1 : 0, cout, cin, co0, ci0);
+  return stif_check_launch(fn);
 }

@@ -363,6 +363,97 @@ def upsample2x(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0):
             float(scale), x.stride(0) if n > 1 else h * w * c, out.stride(0) if n > 1 else 4 * h * w * c, _stream())
 
 
+def upsample2x_bwd(gy: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """The adjoint of upsample2x: NHWC ``gy`` [n, 2h, 2w, c] (items may be strided; pixels contiguous, c % 4 == 0)
+    -> a new gx [n, h, w, c], the transpose of scale * bilinear x2 (align_corners=False).  A gather: no atomics."""
+    if gy.dim() != 4 or gy.shape[1] % 2 or gy.shape[2] % 2 or gy.shape[3] % 4 or 0 in gy.shape:
+        raise ValueError(f"upsample2x_bwd: gy {tuple(gy.shape)} must be [n, 2h, 2w, c] with c % 4 == 0")
+    gy_item = _item_stride([gy], "upsample2x_bwd gy")
+    n, H, W, c = gy.shape
+    gx = torch.empty(n, H // 2, W // 2, c, dtype=torch.float32, device=gy.device)
+    trace = (("up2_bwd",), 0.0, 4.0 * 1.25 * c * n * H * W) if TRACE is not None else None
+    _launch("stif_upsample2x_bwd_nhwc", trace, L.lib().stif_upsample2x_bwd_nhwc, _vp(gy), _vp(gx), n, H // 2, W // 2, c,
+            float(scale), gy_item if n > 1 else H * W * c, (H // 2) * (W // 2) * c,
+            torch.cuda.current_stream(gy.device).cuda_stream)
+    return gx
+
+
+def conv3x3_wgrad_cat(xs, gy: torch.Tensor, cout: int):
+    """Weight and bias gradient of a 3x3 'same' conv in 64 x 64 channel blocks (stif_conv3x3_wgrad_cat).  ``xs``: the
+    one or two NHWC 64-channel maps whose concatenation was the forward's input (never built); ``gy``: [n, H, W, 64] with
+    ``cout`` = 64, or the 256-channel map of the 64 -> 216 offset / mask conv with ``cout`` = 216 (channels 216.. are
+    never read).  Returns (gw [cout, 64 len(xs), 3, 3] OIHW, gb [cout]).  Every 64 x 64 block of gw has the bits
+    conv3x3_wgrad returns for the same two maps; repeated calls give identical bits."""
+    xs = list(xs)
+    if len(xs) not in (1, 2) or gy.dim() != 4 or any(x.dim() != 4 or x.shape[3] != 64 or x.shape[:3] != gy.shape[:3]
+                                                      for x in xs):
+        raise ValueError(f"conv3x3_wgrad_cat: one or two x maps [n, H, W, 64] and a gy over the same pixels, got "
+                         f"{[tuple(x.shape) for x in xs]} and {tuple(gy.shape)}")
+    n, H, W, gc = gy.shape
+    nx = len(xs)
+    if (nx, gc, cout) not in ((2, 64, 64), (1, 256, 216), (1, 64, 64)):
+        raise ValueError(f"conv3x3_wgrad_cat: unsupported channel counts (nx, gy channels, cout) = {(nx, gc, cout)}")
+    lib = L.lib()
+    a = L.ConvWgradCatArgs()
+    for i, x in enumerate(xs):
+        a.x[i], a.x_item[i] = _vp(x), _item_stride([x], "conv3x3_wgrad_cat x")
+    gy_item = _item_stride([gy], "conv3x3_wgrad_cat gy")
+    ws, stream = _wgrad_workspace(gy.device, lib.stif_conv3x3_wgrad_cat_workspace_size(n, H, W, nx, gc, cout))
+    gw = torch.empty(cout, 64 * nx, 3, 3, dtype=torch.float32, device=gy.device)
+    gb = torch.empty(cout, dtype=torch.float32, device=gy.device)
+    a.gy, a.gw, a.gb, a.gy_item = _vp(gy), _vp(gw), _vp(gb), gy_item
+    a.n, a.H, a.W, a.nx, a.gy_channels, a.cout = n, H, W, nx, gc, cout
+    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
+    trace = None
+    if TRACE is not None:
+        blocks = nx * ((cout + 63) // 64)
+        trace = (("wgrad_cat", nx, cout), 2.0 * cout * 64 * nx * 9 * n * H * W, 4.0 * (64 * blocks + cout) * n * H * W)
+    _launch("stif_conv3x3_wgrad_cat", trace, lib.stif_conv3x3_wgrad_cat, C.byref(a), stream)
+    return gw, gb
+
+
+def pack_conv_blocks_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mode: int = L.PACK_WINO,
+                         dgrad: bool = False, half: Optional[int] = None,
+                         status: Optional[torch.Tensor] = None) -> PackedConv:
+    """The Winograd packing on the device of PCD_Align's wider 3x3 layers, as 64 x 64 block packs
+    (stif_pack_conv_block_dev) laid end to end in one buffer:
+
+    * ``weight`` [64, 128]: the 128 -> 64 layer (the bytes of ops.pack_conv), its two column blocks;
+    * ``weight`` [216, 64]: the 64 -> 216 layer with its rows zero-padded to 256 (the bytes of ops.pack_conv; the
+      PackedConv says cout = 256, which is what stif_conv3x3_wino writes), its four row blocks;
+    * ``weight`` [216, 64], ``dgrad``: the data gradient's 256 -> 64 layer, the four DGRAD row blocks;
+    * ``weight`` [64, 128], ``dgrad``, ``half`` = 0 or 1: the data gradient's 64 -> 64 layer of that input half.
+
+    ``bias`` may be None with ``dgrad`` (the bias is zero then); ``status`` as ops.pack_conv_dev."""
+    if not (weight.is_cuda and weight.dtype == torch.float32):
+        raise ValueError("pack_conv_blocks_dev: expected a float32 CUDA weight")
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
+        raise ValueError("pack_conv_blocks_dev: expected a float32 CUDA bias")
+    shape = tuple(weight.shape)
+    if shape == (64, 128, 3, 3) and not dgrad and half is None:
+        blocks, cout, cin = [(0, 0), (0, 64)], 64, 128
+    elif shape == (216, 64, 3, 3) and half is None:
+        blocks = [(64 * s, 0) for s in range(4)]
+        cout, cin = (64, 256) if dgrad else (256, 64)
+    elif shape == (64, 128, 3, 3) and dgrad and half in (0, 1):
+        blocks, cout, cin = [(0, 64 * half)], 64, 64
+    else:
+        raise ValueError(f"pack_conv_blocks_dev: no block form for weight {shape}, dgrad={dgrad}, half={half}")
+    weight = weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    lib = L.lib()
+    per = lib.stif_conv_weight_floats(64, 64, 3, mode)
+    wd = torch.empty(per * len(blocks), dtype=torch.float32, device=weight.device)
+    bd = torch.empty(lib.stif_conv_bias_floats(cout, mode), dtype=torch.float32, device=weight.device)
+    for i, (co0, ci0) in enumerate(blocks):
+        # the blocks of one cout slice share its 64 biases; a row block has its own
+        bi = bd[co0:co0 + 64] if cout == 256 else bd
+        _launch("stif_pack_conv_block_dev", None, lib.stif_pack_conv_block_dev, _vp(weight), _vp(bias), shape[0],
+                shape[1], co0, ci0, mode, L.PACK_DGRAD if dgrad else 0, _vp(wd[i * per:]), _vp(bi), _vp(status),
+                _stream())
+    return PackedConv(wd, bd, cout, cin, 3, mode)
+
+
 def conv_first(x_nchw: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor):
     n, c, h, wd = x_nchw.shape
     assert c == 3 and x_nchw.is_contiguous() and out.is_contiguous()
@@ -473,8 +564,9 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride
     wo = (w + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
     out = torch.empty(b, co, ho, wo, device=input.device, dtype=torch.float32)
     ws, nbytes = _dcn_v2_workspace(L.lib().stif_dcn_v2_workspace_size, dims, out.device)
-    L.check(L.lib().stif_dcn_v2_forward(*[_vp(t) for t in ts], _vp(out), *dims, _vp(ws), nbytes, _stream()),
-            "dcn_v2_forward")
+    trace = (("dcn_v2_fwd",), 2.0 * co * dims[1] * kernel_h * kernel_w * b * ho * wo) if TRACE is not None else None
+    _launch("dcn_v2_forward", trace, L.lib().stif_dcn_v2_forward, *[_vp(t) for t in ts], _vp(out), *dims, _vp(ws),
+            nbytes, _stream())
     return out
 
 
@@ -488,8 +580,12 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, ke
     input, weight, bias, offset, mask, _ = ts
     grads = [torch.empty_like(t) for t in (input, offset, mask, weight, bias)]
     ws, nbytes = _dcn_v2_workspace(L.lib().stif_dcn_v2_backward_workspace_size, dims, input.device)
-    L.check(L.lib().stif_dcn_v2_backward(*[_vp(t) for t in ts], *[_vp(g) for g in grads], *dims, _vp(ws), nbytes,
-                                         _stream()), "dcn_v2_backward")
+    trace = None
+    if TRACE is not None:   # the column GEMM and the weight-gradient GEMM
+        gb, _, gh, gw_ = grad_output.shape
+        trace = (("dcn_v2_bwd",), 4.0 * weight.numel() * gb * gh * gw_)
+    _launch("dcn_v2_backward", trace, L.lib().stif_dcn_v2_backward, *[_vp(t) for t in ts], *[_vp(g) for g in grads],
+            *dims, _vp(ws), nbytes, _stream())
     return tuple(grads)
 
 

@@ -31,6 +31,13 @@ trunks through the modules below.
   on the device, backward stif_conv3x3s2_wgrad / stif_conv3x3s2_dgrad) and conv_first (stif_conv_first, backward
   stif_conv_first_wgrad), all fp32, around the trunk and two ``Conv3x3``.  The gradient with respect to the input
   frames is not built.
+* ``Upsample2x``, ``Conv3x3Cat``, ``DCN_sep``, ``PCD_Align`` -- the alignment module that consumes the encoder's three
+  levels (Sakuya_arch_test.py:20-130, dcn_v2.py:110-140) with the reference's parameter names: the 128 -> 64 convs run
+  on their two inputs without a concatenation (stif_conv3x3_wino with two inputs; backward stif_conv3x3_wgrad_cat,
+  the weight gradient in 64 x 64 channel blocks, and one 64 -> 64 data-gradient conv per input), the x2 upsample has
+  its adjoint kernel (stif_upsample2x_bwd_nhwc), and DCN_sep's 64 -> 216 offset / mask conv trains through the same
+  block kernels on a zero-padded 256-channel map (weights packed by stif_pack_conv_block_dev).  The deformable conv
+  itself goes through the NCHW entry points stif_dcn_v2_forward / _backward with torch layout conversions around them.
 """
 from __future__ import annotations
 
@@ -185,13 +192,15 @@ def range_status(device=None) -> int:
     return bits
 
 
-def _nhwc(t: torch.Tensor, what: str) -> torch.Tensor:
+def _nhwc(t: torch.Tensor, what: str, channels=64) -> torch.Tensor:
     """The NHWC buffer of a logical NCHW tensor: a ``channels_last`` tensor is used in place (its memory is
-    NHWC), anything else is converted once."""
+    NHWC), anything else is converted once.  ``channels`` None: any positive multiple of 4."""
     if not t.is_cuda:
         raise RuntimeError(f"{what}: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
                            "(move the module and its input to the GPU)")
-    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 64:
+    if channels is None and (t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] % 4 or t.shape[1] < 4):
+        raise RuntimeError(f"{what}: expected a float32 [n, 4k, H, W] tensor, got {t.dtype} {tuple(t.shape)}")
+    if channels is not None and (t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != channels):
         raise RuntimeError(f"{what}: expected a float32 [n, 64, H, W] tensor, got {t.dtype} {tuple(t.shape)}")
     v = t.detach().permute(0, 2, 3, 1)
     return v if v.is_contiguous() else v.contiguous()
@@ -462,3 +471,255 @@ class FrameFeatures(nn.Module):
 
     def range_status(self) -> int:
         return range_status(self.conv_first.weight.device)
+
+
+# ---- PCD_Align: the concatenation convs, the x2 upsample, DCN_sep (Sakuya_arch_test.py:20-130, dcn_v2.py:110-140) ----
+
+class _Upsample2xFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale):
+        xh = _nhwc(x, "Upsample2x", None)
+        n, h, w, c = xh.shape
+        out = torch.empty(n, 2 * h, 2 * w, c, dtype=torch.float32, device=xh.device)
+        ops.upsample2x(xh, out, scale)
+        ctx.scale = scale
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return ops.upsample2x_bwd(_nhwc(grad_out, "Upsample2x backward", None), ctx.scale).permute(0, 3, 1, 2), None
+
+
+class Upsample2x(nn.Module):
+    """``scale`` * F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False) as one autograd node:
+    forward stif_upsample2x_nhwc, backward its adjoint stif_upsample2x_bwd_nhwc.  Logical NCHW in and out
+    (``channels_last`` memory), channels a multiple of 4."""
+
+    def __init__(self, scale: float = 1.0):
+        super().__init__()
+        self.scale = float(scale)
+
+    def forward(self, x):
+        return _Upsample2xFn.apply(x, self.scale)
+
+    def extra_repr(self):
+        return f"scale={self.scale}"
+
+
+class _Conv3x3CatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, weight, bias, act, mode):
+        ah, bh = _nhwc(a, "Conv3x3Cat"), _nhwc(b, "Conv3x3Cat")
+        if ah.shape != bh.shape:
+            raise RuntimeError(f"Conv3x3Cat: the two inputs differ in shape, {tuple(a.shape)} and {tuple(b.shape)}")
+        status = _status_word(ah.device)
+        lay = ops.pack_conv_blocks_dev(weight, bias, mode, status=status)
+        out = torch.empty(ah.shape, dtype=torch.float32, device=ah.device)
+        ops.conv2d([dict(layer=lay, in0=ah, in1=bh, out=out)], epi=_EPI[act], in1_mode=1, status=status)
+        ctx.act, ctx.mode = act, mode
+        ctx.save_for_backward(ah, bh, weight, out if act else None)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ah, bh, weight, out = ctx.saved_tensors
+        g = _nhwc(grad_out, "Conv3x3Cat backward")
+        if ctx.act == "relu":
+            g = g * (out > 0)
+        elif ctx.act == "lrelu":
+            g = torch.where(out > 0, g, g * 0.1)
+        need_a, need_b, need_w, need_bias = ctx.needs_input_grad[:4]
+        gw = gb = None
+        if need_w or need_bias:
+            gw, gb = ops.conv3x3_wgrad_cat([ah, bh], g, 64)
+        gin = [None, None]
+        status = _status_word(g.device)
+        for half, need in enumerate((need_a, need_b)):
+            if need:
+                lay = ops.pack_conv_blocks_dev(weight, None, ctx.mode, dgrad=True, half=half, status=status)
+                gx = torch.empty(g.shape, dtype=torch.float32, device=g.device)
+                ops.conv2d([dict(layer=lay, in0=g, out=gx)], status=status)
+                gin[half] = gx.permute(0, 3, 1, 2)
+        return gin[0], gin[1], gw if need_w else None, gb if need_bias else None, None, None
+
+
+class Conv3x3Cat(nn.Module):
+    """nn.Conv2d(128, 64, 3, 1, 1) applied to torch.cat([a, b], 1) with an optional fused ReLU / LeakyReLU(0.1),
+    without the concatenation: the forward is one stif_conv3x3_wino launch with two inputs, the backward
+    stif_conv3x3_wgrad_cat and one 64 -> 64 Winograd data-gradient conv per input that needs one.  ``weight``
+    [64, 128, 3, 3] and ``bias`` [64] as nn.Conv2d's (names, shapes, default initialisation)."""
+
+    def __init__(self, act=None, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, act, mfma)
+        self.act, self.mfma = act, mfma
+        self.weight = nn.Parameter(torch.empty(64, 128, 3, 3))
+        self.bias = nn.Parameter(torch.empty(64))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(128 * 9)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, a, b):
+        return _Conv3x3CatFn.apply(a, b, self.weight, self.bias, self.act, _PACK[self.mfma])
+
+    def range_status(self) -> int:
+        return range_status(self.weight.device)
+
+    def extra_repr(self):
+        return f"128, 64, kernel_size=(3, 3), padding=1, act={self.act}, mfma={self.mfma}"
+
+
+_DCN_GEOM = (3, 3, 1, 1, 1, 1, 1, 1, 8)   # kernel, stride, pad, dilation (h, w each), deformable groups
+
+
+class _DCNSepFn(torch.autograd.Function):
+    """DCN_sep as one node.  The offset / mask conv writes the zero-padded 256-channel map om (channels 0..143 the
+    reference's cat(o1, o2), 144..215 the mask logits, 216..255 zeros); the deformable conv itself goes through the
+    NCHW entry points stif_dcn_v2_forward / _backward, with torch layout conversions around them."""
+
+    @staticmethod
+    def forward(ctx, inp, fea, weight, bias, om_weight, om_bias, act, mode):
+        feah = _nhwc(fea, "DCN_sep")
+        x = _nhwc(inp, "DCN_sep").permute(0, 3, 1, 2).contiguous()
+        if x.shape != fea.shape:
+            raise RuntimeError(f"DCN_sep: input {tuple(inp.shape)} and fea {tuple(fea.shape)} differ in shape")
+        status = _status_word(feah.device)
+        n, H, W, _ = feah.shape
+        om = torch.empty(n, H, W, 256, dtype=torch.float32, device=feah.device)
+        ops.conv2d([dict(layer=ops.pack_conv_blocks_dev(om_weight, om_bias, mode, status=status), in0=feah, out=om)],
+                   status=status)
+        offset = om[..., :144].permute(0, 3, 1, 2).contiguous()
+        mask = torch.sigmoid(om[..., 144:216]).permute(0, 3, 1, 2).contiguous()
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        out = ops.dcn_v2_forward(x, w, b, offset, mask, *_DCN_GEOM)
+        if act == "lrelu":
+            out = torch.where(out > 0, out, out * 0.1)
+        ctx.act, ctx.mode = act, mode
+        ctx.save_for_backward(x, feah, w, b, om_weight, offset, mask, out if act else None)
+        return out.contiguous(memory_format=torch.channels_last)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, feah, w, b, om_weight, offset, mask, out = ctx.saved_tensors
+        if not grad_out.is_cuda:
+            raise RuntimeError("DCN_sep backward: the HIP kernels need a CUDA tensor")
+        g = grad_out.detach()
+        if ctx.act == "lrelu":
+            g = torch.where(out > 0, g, g * 0.1)
+        g_in, g_off, g_mask, g_w, g_b = ops.dcn_v2_backward(x, w, b, offset, mask, g.contiguous(), *_DCN_GEOM)
+        need_in, need_fea, need_w, need_b, need_omw, need_omb = ctx.needs_input_grad[:6]
+        g_fea = g_omw = g_omb = None
+        if need_fea or need_omw or need_omb:
+            n, H, W, _ = feah.shape
+            # [grad_offset | grad_mask * m (1 - m) | 0]: the pad channels are zeros because the data gradient's
+            # Winograd conv multiplies them
+            g_om = torch.zeros(n, H, W, 256, dtype=torch.float32, device=feah.device)
+            g_om[..., :144] = g_off.permute(0, 2, 3, 1)
+            g_om[..., 144:216] = (g_mask * mask * (1.0 - mask)).permute(0, 2, 3, 1)
+            if need_omw or need_omb:
+                g_omw, g_omb = ops.conv3x3_wgrad_cat([feah], g_om, 216)
+            if need_fea:
+                status = _status_word(feah.device)
+                lay = ops.pack_conv_blocks_dev(om_weight, None, ctx.mode, dgrad=True, status=status)
+                gf = torch.empty(feah.shape, dtype=torch.float32, device=feah.device)
+                ops.conv2d([dict(layer=lay, in0=g_om, out=gf)], status=status)
+                g_fea = gf.permute(0, 3, 1, 2)
+        return (g_in if need_in else None, g_fea, g_w if need_w else None, g_b if need_b else None,
+                g_omw if need_omw else None, g_omb if need_omb else None, None, None)
+
+
+class _ConvParams(nn.Module):
+    """The parameters of an nn.Conv2d (``weight``, ``bias``) under its names, with no forward of its own."""
+
+    def __init__(self, cout, cin):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(cout, cin, 3, 3))
+        self.bias = nn.Parameter(torch.zeros(cout))
+
+
+class DCN_sep(nn.Module):
+    """dcn_v2.py:110-140 for 64 -> 64 channels, 3x3, 8 deformable groups, trainable on the engine: ``forward(input,
+    fea)`` = the modulated deformable conv of ``input`` with offsets and masks from ``conv_offset_mask(fea)``,
+    optionally followed by LeakyReLU(0.1).  Parameters under the reference's names -- ``weight``, ``bias``,
+    ``conv_offset_mask.weight`` [216, 64, 3, 3], ``conv_offset_mask.bias`` -- with its initialisation (uniform
+    weight, zero bias, zeroed offset conv).  The offset / mask conv and its data gradient are stif_conv3x3_wino, its
+    weight gradient stif_conv3x3_wgrad_cat, the deformable conv stif_dcn_v2_forward / stif_dcn_v2_backward."""
+
+    def __init__(self, act=None, mfma: str = "f16x3"):
+        super().__init__()
+        if act not in (None, "lrelu"):
+            raise ValueError(f"act must be None or 'lrelu', got {act!r}")
+        _check_choice(64, None, mfma)
+        self.act, self.mfma = act, mfma
+        self.weight = nn.Parameter(torch.empty(64, 64, 3, 3))
+        self.bias = nn.Parameter(torch.zeros(64))
+        stdv = 1.0 / math.sqrt(64 * 9)
+        nn.init.uniform_(self.weight, -stdv, stdv)
+        self.conv_offset_mask = _ConvParams(216, 64)
+
+    def forward(self, input, fea):
+        return _DCNSepFn.apply(input, fea, self.weight, self.bias, self.conv_offset_mask.weight,
+                               self.conv_offset_mask.bias, self.act, _PACK[self.mfma])
+
+    def range_status(self) -> int:
+        return range_status(self.weight.device)
+
+    def extra_repr(self):
+        return f"64, 64, kernel_size=(3, 3), padding=1, deformable_groups=8, act={self.act}, mfma={self.mfma}"
+
+
+class PCD_Align(nn.Module):
+    """Sakuya_arch_test.py:20-130 with the reference's submodule names and registration order, so the ``pcd_align.*``
+    slice of a LunaTokis state dict (and ``ConvBLSTM.forward_net.pcd_h.pcd_align.*`` / ``...pcd_c.pcd_align.*``) loads
+    with ``strict=True``: ``forward(fea1, fea2)`` takes two lists [L1, L2, L3] of logical-NCHW 64-channel maps and
+    returns [B, 128, H, W], every conv, upsample and deformable conv forward and backward on the HIP kernels."""
+
+    def __init__(self, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, None, mfma)
+        for s in ("_1", "_2"):
+            self.add_module("L3_offset_conv1" + s, Conv3x3Cat("lrelu", mfma))
+            self.add_module("L3_offset_conv2" + s, Conv3x3(64, "lrelu", mfma))
+            self.add_module("L3_dcnpack" + s, DCN_sep("lrelu", mfma))
+            for lv in ("L2", "L1"):
+                self.add_module(f"{lv}_offset_conv1" + s, Conv3x3Cat("lrelu", mfma))
+                self.add_module(f"{lv}_offset_conv2" + s, Conv3x3Cat("lrelu", mfma))
+                self.add_module(f"{lv}_offset_conv3" + s, Conv3x3(64, "lrelu", mfma))
+                self.add_module(f"{lv}_dcnpack" + s, DCN_sep(None, mfma))
+                self.add_module(f"{lv}_fea_conv" + s, Conv3x3Cat("lrelu" if lv == "L2" else None, mfma))
+        self.up_offset = Upsample2x(2.0)     # F.interpolate(offset) * 2
+        self.up_fea = Upsample2x(1.0)
+
+    def _branch(self, s, fa, fb):
+        m = lambda name: getattr(self, name + s)
+        L3_off = m("L3_offset_conv2")(m("L3_offset_conv1")(fa[2], fb[2]))
+        L3_fea = m("L3_dcnpack")(fa[2], L3_off)
+        L2_off = m("L2_offset_conv1")(fa[1], fb[1])
+        L2_off = m("L2_offset_conv3")(m("L2_offset_conv2")(L2_off, self.up_offset(L3_off)))
+        L2_fea = m("L2_fea_conv")(m("L2_dcnpack")(fa[1], L2_off), self.up_fea(L3_fea))
+        L1_off = m("L1_offset_conv1")(fa[0], fb[0])
+        L1_off = m("L1_offset_conv3")(m("L1_offset_conv2")(L1_off, self.up_offset(L2_off)))
+        return m("L1_fea_conv")(m("L1_dcnpack")(fa[0], L1_off), self.up_fea(L2_fea))
+
+    def forward(self, fea1, fea2):
+        fea1, fea2 = list(fea1), list(fea2)
+        if len(fea1) != 3 or len(fea2) != 3:
+            raise ValueError("PCD_Align: fea1 and fea2 are lists [L1, L2, L3]")
+        if fea1[0].dim() != 4:
+            raise ValueError(f"PCD_Align: expected [B, 64, H, W] maps, got {tuple(fea1[0].shape)}")
+        B, _, H, W = fea1[0].shape
+        if H % 4 or W % 4:
+            raise ValueError(f"PCD_Align: H and W must be multiples of 4 (three pyramid levels), got {H} x {W}")
+        for lv in range(3):
+            want = (B, 64, H >> lv, W >> lv)
+            if tuple(fea1[lv].shape) != want or tuple(fea2[lv].shape) != want:
+                raise ValueError(f"PCD_Align: level L{lv + 1} must be {want}, got {tuple(fea1[lv].shape)} and "
+                                 f"{tuple(fea2[lv].shape)}")
+        for t in fea1 + fea2:     # a CPU tensor is refused before any launch
+            if not t.is_cuda:
+                raise RuntimeError(f"PCD_Align: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
+                                   "(move the module and its input to the GPU)")
+        return torch.cat([self._branch("_1", fea1, fea2), self._branch("_2", fea2, fea1)], dim=1)
+
+    def range_status(self) -> int:
+        return range_status(self.L3_dcnpack_1.weight.device)
