@@ -232,6 +232,57 @@ typedef struct {
 
 int stif_dcn_nhwc(const stif_dcn_args* args, void* stream);
 
+/* Backward of stif_dcn_nhwc (one group, fp32) at the same shape, NHWC throughout (training; the formulas are
+ * modulated_deformable_col2im / _col2im_coord and dcn_v2_cuda_backward's weight / bias gradient).  With
+ *   gy = gout, or with epi = STIF_EPI_LRELU gout * (out > 0 ? 1 : 0.1)   (the activation's derivative from its output),
+ *   colg[p][c][k] = sum_co w[co][c][k] * gy[p][co],
+ *   g_in   += colg * m * bilinear weight at the four corners of every sample (corners outside the frame get nothing),
+ *   g_w[co][c][k] = sum_p gy[p][co] * m * sample(p, c, k),   g_b[co] = sum_p gy[p][co],
+ * and g_om in the layout of the offset / mask conv's 256-channel output map, so that it is that conv's output
+ * gradient as it stands: channel g*18 + 2k (+1) = grad_offset h (w) of group g, tap k; channel 144 + g*9 + k =
+ * grad_mask * m * (1 - m) with m read from offmask (the sigmoid's derivative); channels 216..255 zeros.
+ * All pointers are device pointers, bases 16-B aligned, items *_item floats apart (>= 0, multiples of 4; the items of
+ * g_in / g_om must not overlap); nothing is read back and nothing is allocated.  A NULL output is not computed: the
+ * weight kernel runs only with g_w, the data kernel only with g_in or g_om.  Every output asked for is overwritten
+ * in full; g_in is cleared on `stream` first.  g_om, g_w and g_b are written without floating-point atomics, each
+ * element by one lane (g_w / g_b through per-workgroup partials in the workspace, added in index order as
+ * stif_conv3x3_wgrad does), so repeated calls on one device give identical bits for these three.  g_in is a sum of
+ * fp32 atomic adds -- as in the reference and the drop-in -- whose order varies: its last bits may differ from run to
+ * run.  workspace (needed with g_w only): at least stif_dcn_bwd_workspace_size bytes, which equals
+ * stif_conv3x3_wgrad_workspace_size(n, H, W, 64, 64), 16-B aligned; its previous contents do not matter.
+ * STIF_E_INVALID, each with its reason, before any launch: null args, a null in / offmask / w / gout, an unknown epi,
+ * epi LRELU with a null out, all of g_in / g_om / g_w null, g_b without g_w, n / H / W < 1, a negative or misaligned
+ * stride or base, overlapping g_in / g_om items, an item of 2 GB or more (H W 256 floats), and with g_w a workspace
+ * that is missing, too small or misaligned.  Zero-initialise the struct, then fill. */
+typedef struct {
+  const float* in;       /* the forward's input, NHWC [n][H][W][64] */
+  const float* offmask;  /* what stif_dcn_nhwc read: NHWC [n][H][W][216] = [group 8][tap 9][dy, dx, m], m after the sigmoid */
+  const float* w;        /* the state dict's weight [64][64][3][3] on the device (no host packing, no sync) */
+  const float* gout;     /* gradient of the forward's output, NHWC [n][H][W][64] */
+  const float* out;      /* the forward's output, NHWC; read only with epi = STIF_EPI_LRELU */
+  float* g_in;           /* NHWC [n][H][W][64], or NULL: not computed */
+  float* g_om;           /* NHWC [n][H][W][256], or NULL: not computed */
+  float* g_w;            /* [64][64][3][3] OIHW, or NULL: neither g_w nor g_b computed */
+  float* g_b;            /* [64] or NULL */
+  long long in_item, om_item, gout_item, out_item, gin_item, gom_item;
+  int n, H, W;
+  int epi;               /* STIF_EPI_NONE, or STIF_EPI_LRELU: gout is first multiplied by 0.1 where out <= 0 */
+  void* workspace;
+  size_t workspace_bytes;
+} stif_dcn_bwd_args;
+/* 0 for sizes < 1. */
+size_t stif_dcn_bwd_workspace_size(int n, int H, int W);
+int stif_dcn_bwd_nhwc(const stif_dcn_bwd_args* args, void* stream);
+
+/* The offset / mask conv's output as the deformable conv reads it: om NHWC [n][H][W][256] in the reference's row order
+ * (channel g*18 + 2k (+1) the h (w) offset of group g, tap k; 144 + g*9 + k the mask logit; 216..255 never read) ->
+ * offmask NHWC [n][H][W][216] = [group][tap][dy, dx, sigmoid(logit)].  Offsets are copied bit for bit; the sigmoid is
+ * 1 / (1 + expf(-x)).  Items om_item / offmask_item floats apart (>= 0, multiples of 4; bases 16-B aligned; offmask
+ * items must not overlap).  STIF_E_INVALID before the launch: a null om / offmask, n / H / W < 1, a negative or
+ * misaligned stride or base, overlapping offmask items, an item of 2 GB or more (H W 256 floats). */
+int stif_dcn_offmask_nhwc(const float* om, float* offmask, long long om_item, long long offmask_item, int n, int H,
+                          int W, void* stream);
+
 /* Fused DCN_sep (dcn_v2.py:127-140) in one launch: conv_offset_mask (64 -> 216, 3x3) + chunk / cat /
  * sigmoid + the modulated deformable conv (64 -> 64, 3x3, 8 groups) -- the offset/mask map never leaves
  * the registers (split-fp16 MFMA only, flags = STIF_CONV_F16X3).  fea: the offset branch's feature

@@ -75,6 +75,19 @@ class ConvWgradCatArgs(C.Structure):
     ]
 
 
+class DcnBwdArgs(C.Structure):
+    """stif_dcn_bwd_args: the backward of stif_dcn_nhwc -- NHWC maps with element strides between items, the OIHW weight
+    as the state dict has it, any of g_in / g_om / g_w (with g_b) NULL for 'not computed'."""
+    _fields_ = [
+        ("inp", _P), ("offmask", _P), ("w", _P), ("gout", _P), ("out", _P),
+        ("g_in", _P), ("g_om", _P), ("g_w", _P), ("g_b", _P),
+        ("in_item", C.c_longlong), ("om_item", C.c_longlong), ("gout_item", C.c_longlong), ("out_item", C.c_longlong),
+        ("gin_item", C.c_longlong), ("gom_item", C.c_longlong),
+        ("n", C.c_int), ("H", C.c_int), ("W", C.c_int), ("epi", C.c_int),
+        ("workspace", _P), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class DecTables(C.Structure):
     _fields_ = [(n, _P) for n in ("near_y", "rel_y", "by0", "by1", "wy0", "wy1", "lin_y",
                                   "near_x", "rel_x", "bx0", "bx1", "wx0", "wx1", "lin_x", "hr_y", "hr_x")]
@@ -168,6 +181,9 @@ EXPORTS = {
     "stif_conv_first": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "stif_dcn_nhwc": (C.c_int, [C.POINTER(DcnArgs), _P]),
     "stif_dcn_sep_nhwc": (C.c_int, [C.POINTER(DcnSepArgs), _P]),
+    "stif_dcn_bwd_workspace_size": (C.c_size_t, [C.c_int] * 3),
+    "stif_dcn_bwd_nhwc": (C.c_int, [C.POINTER(DcnBwdArgs), _P]),
+    "stif_dcn_offmask_nhwc": (C.c_int, [_P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, _P]),
     "stif_dcn_v2_workspace_size": (C.c_size_t, [C.c_int] * 14),
     "stif_dcn_v2_forward": (C.c_int, [_P] * 6 + [C.c_int] * 14 + [_P, C.c_size_t, _P]),
     "stif_dcn_v2_backward_workspace_size": (C.c_size_t, [C.c_int] * 14),

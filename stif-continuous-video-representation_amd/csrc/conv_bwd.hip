@@ -14,6 +14,7 @@
 #include "abi_util.h"
 #include "stif.h"
 #include "stif_common.h"
+#include "wgrad_part.h"
 
 namespace {
 
@@ -40,8 +41,7 @@ struct WgradTile {
   static constexpr int XH = S * (TH - 1) + 3, XW = S * (TW - 1) + 3;
 };
 constexpr int WG_PER_CU = STIF_WGRAD_WG_PER_CU;
-constexpr int GW_FLOATS = 64 * 64 * 9;
-constexpr int PART = GW_FLOATS + 64;   // one workgroup's partial: [tap 9][co 64][ci 64] then the 64 bias sums
+// GW_FLOATS, PART (one workgroup's partial) and k_wgrad_reduce: wgrad_part.h
 
 // x is [H][W][64] per item, gy [Ho][Wo][64]; the tiles walk gy
 template <int S>
@@ -221,22 +221,6 @@ __global__ __launch_bounds__(256) void k_wgrad_cat_reduce(const float* __restric
   } else if (gb != nullptr && xi == 0) {
     const int co = slice * 64 + idx - GW_FLOATS;
     if (co < cout) gb[co] = s;
-  }
-}
-
-// gw / gb = the G partials summed in index order; gw stored OIHW
-__global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ ws, int G, float* __restrict__ gw,
-                                                      float* __restrict__ gb) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= PART) return;
-  float s = 0.f;
-#pragma unroll 8
-  for (int g = 0; g < G; ++g) s += ws[(size_t)g * PART + idx];
-  if (idx < GW_FLOATS) {
-    const int tap = idx >> 12, co = (idx >> 6) & 63, ci = idx & 63;
-    gw[(co * 64 + ci) * 9 + tap] = s;
-  } else if (gb != nullptr) {
-    gb[idx - GW_FLOATS] = s;
   }
 }
 

@@ -491,6 +491,84 @@ def dcn(groups, *, epi=L.EPI_NONE, status=None):
     _launch("stif_dcn_nhwc", trace, L.lib().stif_dcn_nhwc, C.byref(a), _stream())
 
 
+def dcn_offmask(om: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The offset / mask conv's NHWC map ``om`` [n, H, W, 256] (reference row order: offsets 0..143, mask logits
+    144..215, pad channels never read) as the offmask ops.dcn reads, [n, H, W, 216] = [group][tap][dy, dx,
+    sigmoid(logit)] (stif_dcn_offmask_nhwc): offsets bit for bit, one pass.  Items may be strided, pixels contiguous."""
+    if om.dim() != 4 or om.shape[3] != 256 or 0 in om.shape:
+        raise ValueError(f"dcn_offmask: om {tuple(om.shape)} must be [n, H, W, 256]")
+    n, H, W, _ = om.shape
+    if out is None:
+        out = torch.empty(n, H, W, 216, dtype=torch.float32, device=om.device)
+    elif tuple(out.shape) != (n, H, W, 216):
+        raise ValueError(f"dcn_offmask: out shape {tuple(out.shape)} != {(n, H, W, 216)}")
+    om_item = _item_stride([om], "dcn_offmask om")
+    out_item = _item_stride([out], "dcn_offmask out")
+    trace = (("dcn_offmask",), 0.0, 4.0 * 2 * 216 * n * H * W) if TRACE is not None else None
+    _launch("stif_dcn_offmask_nhwc", trace, L.lib().stif_dcn_offmask_nhwc, _vp(om), _vp(out),
+            om_item if n > 1 else H * W * 256, out_item if n > 1 else H * W * 216, n, H, W,
+            torch.cuda.current_stream(om.device).cuda_stream)
+    return out
+
+
+def dcn_bwd(inp: torch.Tensor, offmask: torch.Tensor, weight: torch.Tensor, gout: torch.Tensor, *,
+            out: Optional[torch.Tensor] = None, epi=L.EPI_NONE, need=(True, True, True)):
+    """Backward of ops.dcn (fp32, one group) on NHWC maps (stif_dcn_bwd_nhwc): ``inp`` / ``gout`` [n, H, W, 64],
+    ``offmask`` [n, H, W, 216] as the forward read it, ``weight`` the state dict's [64, 64, 3, 3] on the device,
+    ``out`` the forward's output (needed with ``epi`` = EPI_LRELU only: the activation's derivative).  ``need`` =
+    (g_in, g_om, g_w): what to compute.  Returns (g_in [n, H, W, 64], g_om [n, H, W, 256], g_w [64, 64, 3, 3],
+    g_b [64]) with None for what was not asked for (g_b comes with g_w).  g_om is the gradient of the offset / mask
+    conv's 256-channel output: grad_offset in channels 0..143, grad_mask * m (1 - m) in 144..215, zeros in the pad
+    channels.  g_om, g_w and g_b have identical bits on repeated calls; g_in is an fp32 atomic sum."""
+    need_in, need_om, need_w = (bool(v) for v in need)
+    if inp.dim() != 4 or inp.shape[3] != 64 or 0 in inp.shape or gout.shape != inp.shape:
+        raise ValueError(f"dcn_bwd: inp {tuple(inp.shape)} and gout {tuple(gout.shape)} must both be [n, H, W, 64]")
+    n, H, W, _ = inp.shape
+    if tuple(offmask.shape) != (n, H, W, 216):
+        raise ValueError(f"dcn_bwd: offmask shape {tuple(offmask.shape)} != {(n, H, W, 216)}")
+    if tuple(weight.shape) != (64, 64, 3, 3) or not (weight.is_cuda and weight.dtype == torch.float32):
+        raise ValueError("dcn_bwd: expected a float32 CUDA weight [64, 64, 3, 3]")
+    if epi not in (L.EPI_NONE, L.EPI_LRELU):
+        raise ValueError("dcn_bwd: epi must be EPI_NONE or EPI_LRELU")
+    if epi == L.EPI_LRELU and (out is None or out.shape != inp.shape):
+        raise ValueError("dcn_bwd: EPI_LRELU needs the forward's output [n, H, W, 64]")
+    if not (need_in or need_om or need_w):
+        raise ValueError("dcn_bwd: nothing to compute")
+    weight = weight.detach().contiguous()
+    dev = inp.device
+    a = L.DcnBwdArgs()
+    def item(t, what):   # checks dtype, device and pixel contiguity; the stride of a size-1 dim addresses nothing
+        stride = _item_stride([t], "dcn_bwd " + what)
+        return stride if n > 1 else H * W * t.shape[3]
+
+    a.inp, a.in_item = _vp(inp), item(inp, "inp")
+    a.offmask, a.om_item = _vp(offmask), item(offmask, "offmask")
+    a.gout, a.gout_item = _vp(gout), item(gout, "gout")
+    a.w = _vp(weight)
+    if epi == L.EPI_LRELU:
+        a.out, a.out_item = _vp(out), item(out, "out")
+    g_in = g_om = g_w = g_b = None
+    if need_in:
+        g_in = torch.empty(n, H, W, 64, dtype=torch.float32, device=dev)
+        a.g_in, a.gin_item = _vp(g_in), H * W * 64
+    if need_om:
+        g_om = torch.empty(n, H, W, 256, dtype=torch.float32, device=dev)
+        a.g_om, a.gom_item = _vp(g_om), H * W * 256
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if need_w:
+        g_w = torch.empty(64, 64, 3, 3, dtype=torch.float32, device=dev)
+        g_b = torch.empty(64, dtype=torch.float32, device=dev)
+        ws, stream = _wgrad_workspace(dev, L.lib().stif_dcn_bwd_workspace_size(n, H, W))
+        a.g_w, a.g_b, a.workspace, a.workspace_bytes = _vp(g_w), _vp(g_b), _vp(ws), ws.numel() * 4
+    a.n, a.H, a.W, a.epi = n, H, W, epi
+    trace = None
+    if TRACE is not None:   # the column-gradient GEMM (data kernel) and the weight-gradient GEMM
+        flops = 2.0 * 64 * 576 * n * H * W * ((need_in or need_om) + need_w)
+        trace = (("dcn_bwd", epi, need_in, need_om, need_w), flops, 4.0 * (64 * 3 + 216 + 256) * n * H * W)
+    _launch("stif_dcn_bwd_nhwc", trace, L.lib().stif_dcn_bwd_nhwc, C.byref(a), stream)
+    return g_in, g_om, g_w, g_b
+
+
 def dcn_sep_fusable(om_layer: PackedConv, layer: PackedConv) -> bool:
     """Both layers of a DCN_sep packed for the fused kernel (stif_dcn_sep_nhwc)."""
     return om_layer.mode == (L.PACK_DCNSEP | L.PACK_F16X3) and layer.mode == (L.PACK_DCNPAIR | L.PACK_F16X3)

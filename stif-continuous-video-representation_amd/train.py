@@ -37,7 +37,8 @@ trunks through the modules below.
   the weight gradient in 64 x 64 channel blocks, and one 64 -> 64 data-gradient conv per input), the x2 upsample has
   its adjoint kernel (stif_upsample2x_bwd_nhwc), and DCN_sep's 64 -> 216 offset / mask conv trains through the same
   block kernels on a zero-padded 256-channel map (weights packed by stif_pack_conv_block_dev).  The deformable conv
-  itself goes through the NCHW entry points stif_dcn_v2_forward / _backward with torch layout conversions around them.
+  itself stays in NHWC: stif_dcn_offmask_nhwc, the fused forward stif_dcn_nhwc (fp32) and its backward
+  stif_dcn_bwd_nhwc, which writes the offset / mask conv's output gradient in place of any torch assembly.
 """
 from __future__ import annotations
 
@@ -569,62 +570,51 @@ class Conv3x3Cat(nn.Module):
         return f"128, 64, kernel_size=(3, 3), padding=1, act={self.act}, mfma={self.mfma}"
 
 
-_DCN_GEOM = (3, 3, 1, 1, 1, 1, 1, 1, 8)   # kernel, stride, pad, dilation (h, w each), deformable groups
-
-
 class _DCNSepFn(torch.autograd.Function):
-    """DCN_sep as one node.  The offset / mask conv writes the zero-padded 256-channel map om (channels 0..143 the
-    reference's cat(o1, o2), 144..215 the mask logits, 216..255 zeros); the deformable conv itself goes through the
-    NCHW entry points stif_dcn_v2_forward / _backward, with torch layout conversions around them."""
+    """DCN_sep as one node that never leaves NHWC.  The offset / mask conv writes the zero-padded 256-channel map om
+    (channels 0..143 the reference's cat(o1, o2), 144..215 the mask logits, 216..255 zeros); stif_dcn_offmask_nhwc
+    turns it into the offmask the fused deformable conv stif_dcn_nhwc reads; the backward is one stif_dcn_bwd_nhwc
+    call, whose g_om is the offset / mask conv's output gradient as it stands."""
 
     @staticmethod
     def forward(ctx, inp, fea, weight, bias, om_weight, om_bias, act, mode):
-        feah = _nhwc(fea, "DCN_sep")
-        x = _nhwc(inp, "DCN_sep").permute(0, 3, 1, 2).contiguous()
-        if x.shape != fea.shape:
+        feah, xh = _nhwc(fea, "DCN_sep"), _nhwc(inp, "DCN_sep")
+        if xh.shape != feah.shape:
             raise RuntimeError(f"DCN_sep: input {tuple(inp.shape)} and fea {tuple(fea.shape)} differ in shape")
         status = _status_word(feah.device)
         n, H, W, _ = feah.shape
         om = torch.empty(n, H, W, 256, dtype=torch.float32, device=feah.device)
         ops.conv2d([dict(layer=ops.pack_conv_blocks_dev(om_weight, om_bias, mode, status=status), in0=feah, out=om)],
                    status=status)
-        offset = om[..., :144].permute(0, 3, 1, 2).contiguous()
-        mask = torch.sigmoid(om[..., 144:216]).permute(0, 3, 1, 2).contiguous()
-        w, b = weight.detach().contiguous(), bias.detach().contiguous()
-        out = ops.dcn_v2_forward(x, w, b, offset, mask, *_DCN_GEOM)
-        if act == "lrelu":
-            out = torch.where(out > 0, out, out * 0.1)
+        offmask = ops.dcn_offmask(om)
+        out = torch.empty(n, H, W, 64, dtype=torch.float32, device=feah.device)
+        ops.dcn([dict(layer=ops.pack_conv_plain_dev(weight, bias), inp=xh, offmask=offmask, out=out)], epi=_EPI[act])
         ctx.act, ctx.mode = act, mode
-        ctx.save_for_backward(x, feah, w, b, om_weight, offset, mask, out if act else None)
-        return out.contiguous(memory_format=torch.channels_last)
+        ctx.save_for_backward(xh, offmask, feah, weight, om_weight, out if act else None)
+        return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, grad_out):
-        x, feah, w, b, om_weight, offset, mask, out = ctx.saved_tensors
+        xh, offmask, feah, weight, om_weight, out = ctx.saved_tensors
         if not grad_out.is_cuda:
             raise RuntimeError("DCN_sep backward: the HIP kernels need a CUDA tensor")
-        g = grad_out.detach()
-        if ctx.act == "lrelu":
-            g = torch.where(out > 0, g, g * 0.1)
-        g_in, g_off, g_mask, g_w, g_b = ops.dcn_v2_backward(x, w, b, offset, mask, g.contiguous(), *_DCN_GEOM)
+        g = _nhwc(grad_out, "DCN_sep backward")
         need_in, need_fea, need_w, need_b, need_omw, need_omb = ctx.needs_input_grad[:6]
-        g_fea = g_omw = g_omb = None
-        if need_fea or need_omw or need_omb:
-            n, H, W, _ = feah.shape
-            # [grad_offset | grad_mask * m (1 - m) | 0]: the pad channels are zeros because the data gradient's
-            # Winograd conv multiplies them
-            g_om = torch.zeros(n, H, W, 256, dtype=torch.float32, device=feah.device)
-            g_om[..., :144] = g_off.permute(0, 2, 3, 1)
-            g_om[..., 144:216] = (g_mask * mask * (1.0 - mask)).permute(0, 2, 3, 1)
-            if need_omw or need_omb:
-                g_omw, g_omb = ops.conv3x3_wgrad_cat([feah], g_om, 216)
-            if need_fea:
-                status = _status_word(feah.device)
-                lay = ops.pack_conv_blocks_dev(om_weight, None, ctx.mode, dgrad=True, status=status)
-                gf = torch.empty(feah.shape, dtype=torch.float32, device=feah.device)
-                ops.conv2d([dict(layer=lay, in0=g_om, out=gf)], status=status)
-                g_fea = gf.permute(0, 3, 1, 2)
-        return (g_in if need_in else None, g_fea, g_w if need_w else None, g_b if need_b else None,
+        need = (need_in, need_fea or need_omw or need_omb, need_w or need_b)
+        g_in = g_fea = g_w = g_b = g_omw = g_omb = None
+        if any(need):
+            g_in, g_om, g_w, g_b = ops.dcn_bwd(xh, offmask, weight, g, out=out, epi=_EPI[ctx.act], need=need)
+        if need_in:
+            g_in = g_in.permute(0, 3, 1, 2)
+        if need_omw or need_omb:
+            g_omw, g_omb = ops.conv3x3_wgrad_cat([feah], g_om, 216)
+        if need_fea:
+            status = _status_word(feah.device)
+            lay = ops.pack_conv_blocks_dev(om_weight, None, ctx.mode, dgrad=True, status=status)
+            gf = torch.empty(feah.shape, dtype=torch.float32, device=feah.device)
+            ops.conv2d([dict(layer=lay, in0=g_om, out=gf)], status=status)
+            g_fea = gf.permute(0, 3, 1, 2)
+        return (g_in, g_fea, g_w if need_w else None, g_b if need_b else None,
                 g_omw if need_omw else None, g_omb if need_omb else None, None, None)
 
 
@@ -643,7 +633,8 @@ class DCN_sep(nn.Module):
     optionally followed by LeakyReLU(0.1).  Parameters under the reference's names -- ``weight``, ``bias``,
     ``conv_offset_mask.weight`` [216, 64, 3, 3], ``conv_offset_mask.bias`` -- with its initialisation (uniform
     weight, zero bias, zeroed offset conv).  The offset / mask conv and its data gradient are stif_conv3x3_wino, its
-    weight gradient stif_conv3x3_wgrad_cat, the deformable conv stif_dcn_v2_forward / stif_dcn_v2_backward."""
+    weight gradient stif_conv3x3_wgrad_cat, the deformable conv stif_dcn_nhwc (fp32, after stif_dcn_offmask_nhwc) with
+    the backward stif_dcn_bwd_nhwc; gradients that are not needed are not computed."""
 
     def __init__(self, act=None, mfma: str = "f16x3"):
         super().__init__()

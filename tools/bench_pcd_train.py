@@ -8,10 +8,13 @@ a gate.
       the nine-tap count and the share of the fp32 MFMA peak (157.3 TFLOP/s); the 64 -> 64 kernel alone beside them.
   (b) stif_upsample2x_bwd_nhwc against torch's autograd of F.interpolate on channels_last, 64 channels, scale 2.
   (c) one forward + backward of train.PCD_Align in both mfma modes, and its split by ops.TRACE label (device events
-      around every library call of one traced step, median over the rounds): in particular the share of
-      stif_dcn_v2_backward, and the untraced rest -- the torch ops between the calls: the NCHW <-> NHWC conversions
-      around the DCN entry points, the activation masks, the sigmoid, torch.cat of the two branches and the
-      allocations.
+      around every library call of one traced step, median over the rounds): in particular the share of the deformable
+      conv's backward, and the untraced rest -- the torch ops between the calls: the activation masks, torch.cat of
+      the two branches and the allocations.
+  (d) ops.dcn_offmask + ops.dcn_bwd (stif_dcn_bwd_nhwc: g_in, g_om, g_w, g_b) against what they replace, at the three
+      pyramid shapes: ops.dcn_v2_backward with the NHWC -> NCHW copies of the input and the output gradient, the
+      offset / mask split with its sigmoid, and the g_om assembly the DCN_sep node made with torch ops; both entry
+      points alone beside them, and the new one without the weight kernel and without the data kernel.
 """
 import argparse
 import os
@@ -134,7 +137,57 @@ def label(kind):
     if kind[0] == "wgrad_cat":
         return f"stif_conv3x3_wgrad_cat {kind[1:]}"
     return {"wgrad": "stif_conv3x3_wgrad", "up2": "stif_upsample2x_nhwc", "up2_bwd": "stif_upsample2x_bwd_nhwc",
-            "dcn_v2_fwd": "stif_dcn_v2_forward", "dcn_v2_bwd": "stif_dcn_v2_backward"}.get(kind[0], kind[0])
+            "dcn_v2_fwd": "stif_dcn_v2_forward", "dcn_v2_bwd": "stif_dcn_v2_backward", "dcn": "stif_dcn_nhwc",
+            "dcn_bwd": "stif_dcn_bwd_nhwc", "dcn_offmask": "stif_dcn_offmask_nhwc"}.get(kind[0], kind[0])
+
+
+DCN_GEOM = (3, 3, 1, 1, 1, 1, 1, 1, 8)
+
+
+def bench_dcn(a):
+    """(d)"""
+    for name, (n, H, W) in LEVELS.items():
+        g = torch.Generator().manual_seed(H)
+        rnd = lambda *s: torch.randn(*s, generator=g).cuda()
+        xh, gh, w, b = rnd(n, H, W, 64), rnd(n, H, W, 64), rnd(64, 64, 3, 3) / 24, rnd(64)
+        om = rnd(n, H, W, 256)           # offsets ~ N(0, 1): a trained module's range
+        om[..., 216:] = 0
+
+        def old_path():
+            x = xh.permute(0, 3, 1, 2).contiguous()
+            offset = om[..., :144].permute(0, 3, 1, 2).contiguous()
+            mask = torch.sigmoid(om[..., 144:216]).permute(0, 3, 1, 2).contiguous()
+            go = gh.permute(0, 3, 1, 2).contiguous()
+            g_in, g_off, g_mask, g_w, g_b = ops.dcn_v2_backward(x, w, b, offset, mask, go, *DCN_GEOM)
+            g_om = torch.zeros(n, H, W, 256, dtype=torch.float32, device=xh.device)
+            g_om[..., :144] = g_off.permute(0, 2, 3, 1)
+            g_om[..., 144:216] = (g_mask * mask * (1.0 - mask)).permute(0, 2, 3, 1)
+            return g_in, g_om, g_w, g_b
+
+        offmask = ops.dcn_offmask(om)
+        x, go = xh.permute(0, 3, 1, 2).contiguous(), gh.permute(0, 3, 1, 2).contiguous()
+        offset = om[..., :144].permute(0, 3, 1, 2).contiguous()
+        mask = torch.sigmoid(om[..., 144:216]).permute(0, 3, 1, 2).contiguous()
+        r = timed({"new": lambda: ops.dcn_bwd(xh, ops.dcn_offmask(om), w, gh), "old": old_path,
+                   "bwd": lambda: ops.dcn_bwd(xh, offmask, w, gh),
+                   "v2": lambda: ops.dcn_v2_backward(x, w, b, offset, mask, go, *DCN_GEOM),
+                   "data": lambda: ops.dcn_bwd(xh, offmask, w, gh, need=(True, True, False)),
+                   "weight": lambda: ops.dcn_bwd(xh, offmask, w, gh, need=(False, False, True)),
+                   "offmask": lambda: ops.dcn_offmask(om)}, a.rounds, a.warmup)
+        flop = 2.0 * 64 * 576 * n * H * W
+        show(f"(d) {name} dcn_offmask + dcn_bwd", r["new"])
+        show(f"(d) {name} dcn_v2_backward + copies, sigmoid, g_om", r["old"])
+        m = show(f"(d) {name} dcn_bwd alone", r["bwd"])
+        print(" " * 56 + peak(2 * flop, m) + " (column-gradient + weight-gradient GEMMs)")
+        show(f"(d) {name} dcn_v2_backward alone", r["v2"])
+        m = show(f"(d) {name} dcn_bwd, g_in + g_om only", r["data"])
+        print(" " * 56 + peak(flop, m))
+        m = show(f"(d) {name} dcn_bwd, g_w + g_b only", r["weight"])
+        print(" " * 56 + peak(flop, m))
+        show(f"(d) {name} dcn_offmask", r["offmask"])
+        ok = min(r["old"]) > max(r["new"])
+        print(f"      ranges {'do not overlap: new max < old min' if ok else 'OVERLAP'}; "
+              f"old / new medians = {statistics.median(r['old']) / statistics.median(r['new']):.1f}x", flush=True)
 
 
 def bench_step(a):
@@ -197,9 +250,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--only", choices=["wgrad", "upsample", "step"])
+    ap.add_argument("--only", choices=["wgrad", "upsample", "step", "dcn"])
     a = ap.parse_args()
     print(f"device: {torch.cuda.get_device_name(0)}, rounds {a.rounds}, warm-up {a.warmup}")
-    for name, fn in (("wgrad", bench_wgrad), ("upsample", bench_upsample), ("step", bench_step)):
+    for name, fn in (("wgrad", bench_wgrad), ("upsample", bench_upsample), ("step", bench_step), ("dcn", bench_dcn)):
         if a.only in (None, name):
             fn(a)
