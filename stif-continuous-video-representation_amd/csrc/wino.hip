@@ -295,22 +295,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     float* dst = smem + buf * BUF_F;
     const int cy0 = (t.oy0 >> 1) - 1, cx0 = (t.ox0 >> 1) - 1;
     const float sc = a.in1_scale;
-    const float w3 = 0.75f * sc, w1 = 0.25f * sc;
+    const float r3 = 0.75f * sc, r1 = 0.25f * sc;   // row weights (not `w1`: that is the coarse map's width)
     for (int f = tid; f < 3 * 17 * 8; f += 256) {
       const int ch = f & 7, q = f >> 3, qr = q / 17, qc = q - 17 * (q / 17);
       const int k = cy0 + qr, m = cx0 + qc;   // coarse rows k, k + 1 and columns m, m + 1
       float* d0 = dst + ((2 * qr) * OM_RP + col_slot(2 * qc) * PITCH + ch) * 4;
       float* d1 = dst + ((2 * qr) * OM_RP + col_slot(2 * qc + 1) * PITCH + ch) * 4;
+      // interior quads only: never with h1 == 1 or w1 == 1.  The column test used to read a float row weight named
+      // w1 (0.25 s), i.e. `m < (unsigned)(0.25 s - 1)`: no quad passed at s = 1 or 2, and at s = 8 column 0 passed
+      // whatever the width -- a 4 x 2 output (coarse 2 x 1) then blended the zero column outside the map
       if (((unsigned)k < (unsigned)(h1 - 1)) & ((unsigned)m < (unsigned)(w1 - 1))) {
         const float* s0 = scr + ((qr * UP_C + qc) * 8 + ch) * 4;
         const f32x4 v00 = ld4(s0), v01 = ld4(s0 + 32), v10 = ld4(s0 + UP_C * 32), v11 = ld4(s0 + UP_C * 32 + 32);
         // columns: b = 0 (map column 2 m + 1) weights (0.75, 0.25), b = 1 (2 m + 2) (0.25, 0.75)
         const f32x4 t00 = 0.75f * v00 + 0.25f * v01, t01 = 0.25f * v00 + 0.75f * v01;
         const f32x4 t10 = 0.75f * v10 + 0.25f * v11, t11 = 0.25f * v10 + 0.75f * v11;
-        st4(d0, w3 * t00 + w1 * t10);
-        st4(d1, w3 * t01 + w1 * t11);
-        st4(d0 + OM_RP * 4, w1 * t00 + w3 * t10);
-        st4(d1 + OM_RP * 4, w1 * t01 + w3 * t11);
+        st4(d0, r3 * t00 + r1 * t10);
+        st4(d1, r3 * t01 + r1 * t11);
+        st4(d0 + OM_RP * 4, r1 * t00 + r3 * t10);
+        st4(d1 + OM_RP * 4, r1 * t01 + r3 * t11);
       } else {
         st4(d0, expand_px(t, 2 * qr, 2 * qc, ch));
         st4(d1, expand_px(t, 2 * qr, 2 * qc + 1, ch));
