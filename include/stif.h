@@ -44,14 +44,24 @@ enum {
   STIF_EPI_LSTM = 5     /* ConvLSTMCell gates (convlstm.py:47-56): out=h_next, out2=c_next, res=c_cur */
 };
 
-#define STIF_MAX_GROUPS 8
+#define STIF_MAX_GROUPS 16
+
+/* Item counts per weight set (stif_conv_args, stif_dcn_args, stif_dcn_sep_args).  A launch covers `ngroups` weight
+ * sets (at most STIF_MAX_GROUPS); set g holds items [item_base[g], item_base[g + 1]) of the launch, so its own count
+ * is item_base[g + 1] - item_base[g], and item i of set g uses in[g] + i * in_item (one item stride per operand and
+ * launch, whatever the counts).  item_base is a prefix array: item_base[0] = 0, strictly increasing up to
+ * item_base[ngroups]; entries past it are ignored.  A table of all zeros is the uniform form: every set holds
+ * `nitems` items (nitems is not read otherwise).  STIF_E_INVALID before any launch: a table that does not start at
+ * 0 or does not increase (an empty set), more than STIF_MAX_GROUPS sets, a total the launch grid cannot hold.  The
+ * kernels find a workgroup's (set, item) by a scan of the prefix entries in scalar registers, once per tile. */
 
 /* Direct/implicit-GEMM convolution on NHWC fp32 maps (replaces nn.Conv2d in the
  * hot path).  The input is the channel concatenation [in0 | in1] (so torch.cat
  * never materialises); in1 may be read through a fused bilinear x2 upsample
  * (F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) times
  * in1_scale, Sakuya_arch_test.py:86-87).  A launch covers `ngroups` weight sets
- * x `nitems` items per set (item i of set g uses in0[g] + i*in0_item, ...).
+ * x `nitems` items per set (item i of set g uses in0[g] + i*in0_item, ...), or
+ * with `item_base` a count of its own per set (see STIF_MAX_GROUPS).
  * Weights are packed by stif_pack_conv_weight. */
 typedef struct {
   const float* in0[STIF_MAX_GROUPS];
@@ -82,6 +92,7 @@ typedef struct {
                               freed and re-allocated while the library is loaded.  Outputs are identical either way.
                               Zero-initialise the whole struct: fields added at its end keep their old meaning
                               only when zero. */
+  int item_base[STIF_MAX_GROUPS + 1];  /* per-set item counts as a prefix array; all zeros = `nitems` per set */
 } stif_conv_args;
 
 /* stif_conv_args.flags: fp32 products on the fp16 MFMA pipe by 3-term operand splitting (x = h + l,
@@ -228,6 +239,7 @@ typedef struct {
   int epi;                              /* STIF_EPI_NONE or STIF_EPI_LRELU */
   int flags;                            /* STIF_CONV_F16X3: w packed STIF_PACK_PLAIN | STIF_PACK_F16X3 */
   int* status;                          /* optional device word, as stif_conv_args.status */
+  int item_base[STIF_MAX_GROUPS + 1];   /* per-set item counts as a prefix array; all zeros = `nitems` per set */
 } stif_dcn_args;
 
 int stif_dcn_nhwc(const stif_dcn_args* args, void* stream);
@@ -302,6 +314,7 @@ typedef struct {
   int epi;                              /* STIF_EPI_NONE or STIF_EPI_LRELU */
   int flags;                            /* STIF_CONV_F16X3 (required) */
   int* status;                          /* optional device word, as stif_conv_args.status */
+  int item_base[STIF_MAX_GROUPS + 1];   /* per-set item counts as a prefix array; all zeros = `nitems` per set */
 } stif_dcn_sep_args;
 
 int stif_dcn_sep_nhwc(const stif_dcn_sep_args* args, void* stream);

@@ -11,7 +11,7 @@ import os
 # STIF_HIP_LIB overrides the in-tree library (kernel experiments); the default is the in-tree build
 LIB_PATH = os.environ.get("STIF_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libstif_hip.so")
 
-MAXG = 8
+MAXG = 16               # stif.h STIF_MAX_GROUPS: weight sets per launch
 EPI_NONE, EPI_LRELU, EPI_RELU, EPI_RES, EPI_OFFMASK, EPI_LSTM = range(6)
 PACK_PLAIN, PACK_OFFMASK, PACK_LSTM, PACK_WINO, PACK_WINO_OFFMASK, PACK_WINO_LSTM, PACK_DCNSEP, PACK_DCNPAIR = range(8)
 PACK_F16X3 = 16          # OR'ed into a PACK_WINO* mode (stif.h STIF_PACK_F16X3)
@@ -23,6 +23,7 @@ STATUS_PACK_RANGE = 16   # status bit of the device packer (stif.h STIF_STATUS_P
 
 _P = C.c_void_p
 _PA = _P * MAXG
+_IB = C.c_int * (MAXG + 1)   # item_base: per-set item counts as a prefix array, all zeros = `nitems` per set
 
 
 class ConvArgs(C.Structure):
@@ -34,7 +35,7 @@ class ConvArgs(C.Structure):
         ("H", C.c_int), ("W", C.c_int), ("C0", C.c_int),
         ("C1", C.c_int), ("in1_mode", C.c_int), ("in1_scale", C.c_float),
         ("Ho", C.c_int), ("Wo", C.c_int), ("cout", C.c_int), ("ks", C.c_int), ("stride", C.c_int),
-        ("epi", C.c_int), ("flags", C.c_int), ("status", _P), ("sched", _P),
+        ("epi", C.c_int), ("flags", C.c_int), ("status", _P), ("sched", _P), ("item_base", _IB),
     ]
 
 
@@ -43,7 +44,7 @@ class DcnArgs(C.Structure):
         ("inp", _PA), ("offmask", _PA), ("w", _PA), ("bias", _PA), ("out", _PA),
         ("in_item", C.c_longlong), ("om_item", C.c_longlong), ("out_item", C.c_longlong),
         ("ngroups", C.c_int), ("nitems", C.c_int), ("H", C.c_int), ("W", C.c_int), ("epi", C.c_int),
-        ("flags", C.c_int), ("status", _P),
+        ("flags", C.c_int), ("status", _P), ("item_base", _IB),
     ]
 
 
@@ -52,7 +53,7 @@ class DcnSepArgs(C.Structure):
         ("fea", _PA), ("inp", _PA), ("w_om", _PA), ("b_om", _PA), ("w", _PA), ("bias", _PA), ("out", _PA),
         ("fea_item", C.c_longlong), ("in_item", C.c_longlong), ("out_item", C.c_longlong),
         ("ngroups", C.c_int), ("nitems", C.c_int), ("H", C.c_int), ("W", C.c_int), ("epi", C.c_int),
-        ("flags", C.c_int), ("status", _P),
+        ("flags", C.c_int), ("status", _P), ("item_base", _IB),
     ]
 
 

@@ -63,8 +63,8 @@ __global__ __launch_bounds__(NW * 64) void k_conv(stif_conv_args a) {
   const int tx = bx % tiles_x;
   const int ty = bx / tiles_x;
   const int slice = blockIdx.y;
-  const int g = blockIdx.z / a.nitems;
-  const int n = blockIdx.z - g * a.nitems;
+  const SetItem si = set_item_of(a.item_base, blockIdx.z);
+  const int g = si.g, n = si.n;
 
   const int H = a.H, W = a.W, C0 = a.C0, C1 = a.C1;
   const float* in0 = a.in0[g] + (size_t)n * a.in0_item;
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IN1 ? 4 : 2
   for (int i = wv; i < NC * 4; i += 4)
     __builtin_amdgcn_global_load_lds(wsl + (i * 64 + lane) * 4, swp + i * 256, 16, 0, 0);
   lds_dma_barrier();
-  const int ntiles = tiles_per_item * a.nitems;
+  const int ntiles = tiles_per_item * (a.item_base[g + 1] - a.item_base[g]);   // this set's own item count
   const int HW = a.H * a.W, C0 = IN1 ? 64 : a.C0, C1 = 64;   // host: (64 | 64) or one C0-channel input
   constexpr int NC0 = IN1 ? NC / 2 : NC;   // chunks read from in0
   const float b0 = a.bias[g][slice * 64 + l32], b1 = a.bias[g][slice * 64 + 32 + l32];
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IN1 ? 4 : 2
 }
 
 template <int NC, int IN1>
-int launch_conv1x1(const stif_conv_args& a, hipStream_t st, int wg_per_cu) {
+int launch_conv1x1(const stif_conv_args& a, int most, hipStream_t st, int wg_per_cu) {
   const int tpi = (a.H * a.W + 31) / 32;
   static int cus = 0;
   if (!cus) {
@@ -379,7 +379,8 @@ int launch_conv1x1(const stif_conv_args& a, hipStream_t st, int wg_per_cu) {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
   }
-  const long long wgs = ((long long)tpi * a.nitems + 3) / 4;
+  if ((long long)tpi * most > 0x7fffffffLL) return stif_fail(STIF_E_INVALID, "stif_conv2d_nhwc: too many tiles");
+  const long long wgs = ((long long)tpi * most + 3) / 4;   // of the largest set: the grid's x is shared by all
   // wg_per_cu workgroups per CU over all (slice, group) grid planes, each walking several M-tiles
   const int per = a.ngroups * (a.cout / 64);
   const int gx = (int)std::max<long long>(1, std::min<long long>(wgs, ((long long)wg_per_cu * cus + per - 1) / per));
@@ -392,7 +393,8 @@ int launch(const stif_conv_args& a, hipStream_t st) {
   constexpr int TH = NW * MT;
   const int tiles = ((a.Wo + 31) / 32) * ((a.Ho + TH - 1) / TH);
   const int slices = ((a.cout + 31) / 32 + NT - 1) / NT;
-  dim3 grid(tiles, slices, a.ngroups * a.nitems);
+  if (a.item_base[a.ngroups] > 65535) return stif_fail(STIF_E_INVALID, "stif_conv2d_nhwc: too many items (grid z)");
+  dim3 grid(tiles, slices, a.item_base[a.ngroups]);
   hipLaunchKernelGGL((k_conv<KS, S, MT, NT, NW, IN1, EPI, F16>), grid, dim3(NW * 64), 0, st, a);
   return stif_check_launch("stif_conv2d_nhwc");
 }
@@ -449,10 +451,11 @@ __global__ __launch_bounds__(256) void k_conv_first(const float* __restrict__ x,
 
 extern "C" int stif_conv2d_nhwc(const stif_conv_args* pa, void* stream) {
   if (!pa) return stif_fail(STIF_E_INVALID, "stif_conv2d_nhwc: null args");
-  const stif_conv_args& a = *pa;
+  stif_conv_args a = *pa;   // the kernels' copy: the item table in the form they scan
   hipStream_t st = (hipStream_t)stream;
-  if (a.ngroups < 1 || a.ngroups > STIF_MAX_GROUPS || a.nitems < 1)
-    return stif_fail(STIF_E_INVALID, "stif_conv2d_nhwc: bad ngroups/nitems");
+  long long items;
+  int most;
+  if (const int rc = stif_item_table("stif_conv2d_nhwc", a.ngroups, a.nitems, a.item_base, &items, &most)) return rc;
   if ((long long)a.H * a.W * std::max(a.C0, std::max(a.C1, a.cout)) * 4 >= 0x7fffffffLL)
     return stif_fail(STIF_E_INVALID, "stif_conv2d_nhwc: item larger than 2 GB (buffer addressing)");
   const bool f16 = a.flags & STIF_CONV_F16X3;
@@ -494,7 +497,7 @@ extern "C" int stif_conv2d_nhwc(const stif_conv_args* pa, void* stream) {
     return stif_fail(STIF_E_INVALID, "strided conv: unsupported epilogue");
   }
   if (a.ks == 1) {
-    if (f16) return f16_cat ? launch_conv1x1<8, 1>(a, st, 4) : launch_conv1x1<13, 0>(a, st, 3);
+    if (f16) return f16_cat ? launch_conv1x1<8, 1>(a, most, st, 4) : launch_conv1x1<13, 0>(a, most, st, 3);
     if (a.epi != STIF_EPI_NONE) return stif_fail(STIF_E_INVALID, "1x1 conv: unsupported epilogue");
     if (a.in1_mode == 0) return launch<1, 1, 2, 2, 4, 0, STIF_EPI_NONE>(a, st);
     if (a.in1_mode == 1) return launch<1, 1, 2, 2, 4, 1, STIF_EPI_NONE>(a, st);

@@ -56,7 +56,8 @@ __global__ __launch_bounds__(64 * DCN_ROWS) void k_dcn(stif_dcn_args a) {
   const int tiles_x = (W + 31) >> 5;
   const int bx = blockIdx.x;
   const int tx = bx % tiles_x, ty = bx / tiles_x;
-  const int g = blockIdx.z / a.nitems, n = blockIdx.z - g * a.nitems;
+  const SetItem si = set_item_of(a.item_base, blockIdx.z);
+  const int g = si.g, n = si.n;
   const float* in = a.in[g] + (size_t)n * a.in_item;
   const float* om = a.offmask[g] + (size_t)n * a.om_item;
   const float* wt = a.w[g];
@@ -231,17 +232,20 @@ __global__ __launch_bounds__(64 * DCN_ROWS) void k_dcn(stif_dcn_args a) {
 
 extern "C" int stif_dcn_nhwc(const stif_dcn_args* pa, void* stream) {
   if (!pa) return stif_fail(STIF_E_INVALID, "stif_dcn_nhwc: null args");
-  const stif_dcn_args& a = *pa;
-  if (a.ngroups < 1 || a.ngroups > STIF_MAX_GROUPS || a.nitems < 1 || a.H < 1 || a.W < 1)
-    return stif_fail(STIF_E_INVALID, "stif_dcn_nhwc: bad sizes");
+  stif_dcn_args a = *pa;   // the kernel's copy: the item table in the form it scans
+  long long items;
+  int most;
+  if (const int rc = stif_item_table("stif_dcn_nhwc", a.ngroups, a.nitems, a.item_base, &items, &most)) return rc;
+  if (a.H < 1 || a.W < 1) return stif_fail(STIF_E_INVALID, "stif_dcn_nhwc: bad sizes");
+  if (items > 65535) return stif_fail(STIF_E_INVALID, "stif_dcn_nhwc: too many items (grid z)");
   if ((long long)a.H * a.W * 64 * 4 >= 0x7fffffffLL)
     return stif_fail(STIF_E_INVALID, "stif_dcn_nhwc: item larger than 2 GB (buffer addressing)");
   const bool f16 = a.flags & STIF_CONV_F16X3;
   // two rows per wave (8-row workgroups, two per CU) when that still gives >= 4 workgroups per CU
-  const long long wg2 = (long long)((a.W + 31) / 32) * ((a.H + 2 * DCN_ROWS - 1) / (2 * DCN_ROWS)) * a.ngroups * a.nitems;
+  const long long wg2 = (long long)((a.W + 31) / 32) * ((a.H + 2 * DCN_ROWS - 1) / (2 * DCN_ROWS)) * items;
   const bool mr2 = f16 && wg2 >= DCN_MR2_MIN;
   const int th = DCN_ROWS * (mr2 ? 2 : 1);   // output rows per workgroup
-  dim3 grid(((a.W + 31) / 32) * ((a.H + th - 1) / th), 1, a.ngroups * a.nitems);
+  dim3 grid(((a.W + 31) / 32) * ((a.H + th - 1) / th), 1, (unsigned)items);
   if (a.epi != STIF_EPI_NONE && a.epi != STIF_EPI_LRELU)
     return stif_fail(STIF_E_INVALID, "stif_dcn_nhwc: epilogue must be NONE or LRELU");
   with_bool(a.epi == STIF_EPI_LRELU, [&](auto lrelu) {

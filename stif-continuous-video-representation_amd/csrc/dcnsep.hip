@@ -93,7 +93,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
   const int L = xcd_block(blockIdx.x, gridDim.x);
   const int z = L / tiles, tl = L - z * tiles;
   const int tx = tl % tiles_x, ty = tl / tiles_x;
-  const int g = z / a.nitems, n = z - g * a.nitems;
+  const SetItem si = set_item_of(a.item_base, z);
+  const int g = si.g, n = si.n;
   const float* fea = a.fea[g] + (size_t)n * a.fea_item;
   const float* in = a.in[g] + (size_t)n * a.in_item;
   const float* wt = a.w[g];
@@ -319,9 +320,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE))) 
 
 extern "C" int stif_dcn_sep_nhwc(const stif_dcn_sep_args* pa, void* stream) {
   if (!pa) return stif_fail(STIF_E_INVALID, "stif_dcn_sep_nhwc: null args");
-  const stif_dcn_sep_args& a = *pa;
-  if (a.ngroups < 1 || a.ngroups > STIF_MAX_GROUPS || a.nitems < 1 || a.H < 1 || a.W < 1)
-    return stif_fail(STIF_E_INVALID, "stif_dcn_sep_nhwc: bad sizes");
+  stif_dcn_sep_args a = *pa;   // the kernel's copy: the item table in the form it scans
+  long long items;
+  int most;
+  if (const int rc = stif_item_table("stif_dcn_sep_nhwc", a.ngroups, a.nitems, a.item_base, &items, &most)) return rc;
+  if (a.H < 1 || a.W < 1) return stif_fail(STIF_E_INVALID, "stif_dcn_sep_nhwc: bad sizes");
   if (!(a.flags & STIF_CONV_F16X3))
     return stif_fail(STIF_E_INVALID, "stif_dcn_sep_nhwc: split-fp16 operands only (flags = STIF_CONV_F16X3)");
   if ((long long)a.H * a.W * 64 * 4 >= 0x7fffffffLL)
@@ -329,7 +332,7 @@ extern "C" int stif_dcn_sep_nhwc(const stif_dcn_sep_args* pa, void* stream) {
   for (int i = 0; i < a.ngroups; ++i)
     if (!a.fea[i] || !a.in[i] || !a.w_om[i] || !a.b_om[i] || !a.w[i] || !a.bias[i] || !a.out[i])
       return stif_fail(STIF_E_INVALID, "stif_dcn_sep_nhwc: null tensor");
-  const long long wgs = (long long)((a.W + TW - 1) / TW) * ((a.H + NW - 1) / NW) * a.ngroups * a.nitems;
+  const long long wgs = (long long)((a.W + TW - 1) / TW) * ((a.H + NW - 1) / NW) * items;
   if (wgs > 0x7fffffff) return stif_fail(STIF_E_INVALID, "stif_dcn_sep_nhwc: grid too large");
   dim3 grid((unsigned)wgs);
   if (a.epi == STIF_EPI_LRELU)

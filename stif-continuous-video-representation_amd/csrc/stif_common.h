@@ -164,6 +164,25 @@ STIF_DEV int xcd_block(int b, int nb) {
   return x * q + min(x, r) + (b >> 3);
 }
 
+// (weight set, item in the set) of item r of a launch whose sets carry their own item counts (stif.h
+// STIF_MAX_GROUPS): `ib` is the launch's prefix table as the launchers hand it to the kernels
+// (stif_item_table: ib[g] = first item of set g, every entry past the last set INT_MAX), so the set is the
+// last entry that r has reached.  r is wave-uniform (a function of the workgroup index): the scan is a
+// bisection of the N - 1 = 16 prefix entries by four scalar loads of kernel arguments at a scalar index, once
+// per tile -- never a lane-indexed read of them, and no entry stays in a register between tiles (a scan of
+// all entries at once costs 16 SGPRs where the persistent kernels have none, and their spills cost VGPRs).
+struct SetItem {
+  int g, n;
+};
+template <int N>
+STIF_DEV SetItem set_item_of(const int (&ib)[N], int r) {
+  static_assert(N == 17, "four bisection steps: 16 sets");
+  int g = 0;
+#pragma unroll
+  for (int s = 8; s >= 1; s >>= 1) g += r >= ib[g + s] ? s : 0;
+  return {g, r - ib[g]};
+}
+
 // Epilogue helper: write one 32 px x 32 cout accumulator tile (lane = cout, regs = px) into the
 // wave's private 4-KB LDS block as [px][co] with the 16-B slot XOR-swizzled by px & 3 (bank-conflict
 // free for both the b32 writes and the b128 row reads), so the global stores become coalesced

@@ -109,8 +109,9 @@ struct Tile {
   int oy0, ox0, slice, g, n;
 };
 // tile order: cout slice fastest (the slices of one spatial tile share its input), then x, y, item
-// (k_wino_om: one slice, a workgroup computes all couts)
-STIF_DEV Tile tile_of(int T, int slices, int tiles_x, int tiles_y, int nitems) {
+// (k_wino_om: one slice, a workgroup computes all couts); the item's weight set from the launch's
+// per-set item table (set_item_of)
+STIF_DEV Tile tile_of(int T, int slices, int tiles_x, int tiles_y, const int (&item_base)[STIF_MAX_GROUPS + 1]) {
   Tile t;
   t.slice = T % slices;
   int r = T / slices;
@@ -118,8 +119,9 @@ STIF_DEV Tile tile_of(int T, int slices, int tiles_x, int tiles_y, int nitems) {
   r /= tiles_x;
   const int y = r % tiles_y;
   r /= tiles_y;
-  t.g = r / nitems;
-  t.n = r - t.g * nitems;
+  const SetItem si = set_item_of(item_base, r);
+  t.g = si.g;
+  t.n = si.n;
   t.oy0 = y * WR;
   t.ox0 = x * 32;
   return t;
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     const float *src0, *src1;
   };
   auto wtile_of = [&](int T) {
-    const Tile t = tile_of(T, slices, tiles_x, tiles_y, a.nitems);
+    const Tile t = tile_of(T, slices, tiles_x, tiles_y, a.item_base);
     const float* src0 = a.in0[t.g] + (size_t)t.n * a.in0_item;
     return WTile{t, src0, IN1 ? a.in1[t.g] + (size_t)t.n * a.in1_item : src0};
   };
@@ -699,7 +701,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const TileRange tr = xcd_tile_range(ntiles);
   int T = tr.T;
   if (T >= tr.end) return;
-  Tile cur = tile_of(T, 1, tiles_x, tiles_y, a.nitems);
+  Tile cur = tile_of(T, 1, tiles_x, tiles_y, a.item_base);
   __amdgpu_buffer_rsrc_t wr = wres(cur.g);
 #pragma unroll
   for (int s = 0; s < RING; ++s) ldb(wr, 0, s, s);
@@ -709,7 +711,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   for (;;) {
     const int Tn = T + tr.stride;
     const bool has_next = Tn < tr.end;
-    const Tile nxt = tile_of(has_next ? Tn : T, 1, tiles_x, tiles_y, a.nitems);
+    const Tile nxt = tile_of(has_next ? Tn : T, 1, tiles_x, tiles_y, a.item_base);
     const __amdgpu_buffer_rsrc_t wrn = wres(nxt.g);
     stage(cur, 1, 1);
     make_a(smem, 0, 0);
@@ -769,7 +771,7 @@ void sched_undo(const int* key, const SchedBase& sb) {
 template <int IN1, int EPI>
 int launch(const stif_conv_args& a, hipStream_t st) {
   const long long tiles =
-      (long long)((a.Wo + 31) / 32) * ((a.Ho + WR - 1) / WR) * ((a.cout + 63) / 64) * a.ngroups * a.nitems;
+      (long long)((a.Wo + 31) / 32) * ((a.Ho + WR - 1) / WR) * ((a.cout + 63) / 64) * a.item_base[a.ngroups];
   if (tiles > 0x7fffffff) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: too many tiles");
   if ((long long)a.H * a.W * std::max(a.C0, std::max(a.C1, a.cout)) * 4 >= 0x7fffffffLL)
     return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: item larger than 2 GB (buffer addressing)");
@@ -802,10 +804,11 @@ int launch(const stif_conv_args& a, hipStream_t st) {
 
 extern "C" int stif_conv3x3_wino(const stif_conv_args* pa, void* stream) {
   if (!pa) return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: null args");
-  const stif_conv_args& a = *pa;
+  stif_conv_args a = *pa;   // the kernels' copy: the item table in the form they scan
   hipStream_t st = (hipStream_t)stream;
-  if (a.ngroups < 1 || a.ngroups > STIF_MAX_GROUPS || a.nitems < 1)
-    return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: bad ngroups/nitems");
+  long long items;
+  int most;
+  if (const int rc = stif_item_table("stif_conv3x3_wino", a.ngroups, a.nitems, a.item_base, &items, &most)) return rc;
   if (a.ks != 3 || a.stride != 1 || a.Ho != a.H || a.Wo != a.W)
     return stif_fail(STIF_E_INVALID, "stif_conv3x3_wino: 3x3 stride-1 'same' convolution only");
   if (a.C0 % 8 || a.C0 <= 0 || (a.in1_mode && (a.C1 % 8 || a.C1 <= 0)))

@@ -13,7 +13,8 @@ independent: both PCD_Align directions (different weights -> launch groups), bot
 ConvLSTM directions (BiDeformableConvLSTM runs the same net on x and reversed x,
 :256-266), pcd_h and pcd_c, all pairs of a window, and all three latent steps of
 the reconstruction trunk.  Per-frame encoder features are computed once per frame
-(a sliding window shares each inner frame between two pairs).
+(a sliding window shares each inner frame between two pairs), and so is the
+BiConvLSTM's first step, which reads one frame and the zero state only (step0_plan).
 """
 from __future__ import annotations
 
@@ -56,6 +57,47 @@ def _split(n, k):
     """Items [0, n) as up to ``k`` contiguous ranges of ceil(n / k) items (the last one may be shorter)."""
     per = -(-n // max(1, min(k, n)))
     return [(c0, min(n, c0 + per)) for c0 in range(0, n, per)]
+
+
+def _bases(counts):
+    """Prefix offsets of per-set item counts: set i holds items [b[i], b[i + 1]) of a flat buffer."""
+    b = [0]
+    for c in counts:
+        b.append(b[-1] + c)
+    return b
+
+
+def step0_plan(pairs, window):
+    """The launches around the BiConvLSTM's first step for one chunk of ``pairs`` pairs, as item counts per
+    weight set (pure: no device, no tensors).  ``window``: the pairs are the adjacent pairs of ``pairs + 1``
+    frames of one sequence, whose per-frame features the caller holds.  Then step 0 -- which reads one frame
+    and the all-zero state only, with the same weights in both directions -- runs once per frame: pair b's
+    forward recurrence continues from frame b's (h0, c0), its reversed one from frame b + 1's.
+
+    Returns a dict: ``frames`` (per-frame items, None without sharing), ``fwd`` / ``rev`` (the frame ranges
+    whose h0 / c0 the two recurrences of the chunk's pairs read) and ``launches``, an ordered dict
+    name -> item count of every weight set of that launch group, in launch order:
+      first_pcd        PCD_Align of the frame pairs, sets (alignment direction)
+      first_fusion     its 1x1 fusion conv
+      input_pyramid    Easy_PCD pyramids of the LSTM inputs, sets (pcd, input); on the window path sets (pcd) of
+                       the frames (the middle latent's ride in step1_pyramid)
+      step0_pcd        step 0's alignments, sets (pcd, [direction,] alignment direction); ``zero_l1`` lists the
+                       sets whose L1 input is the zero state (no L1 offset branch, no L1 DCN)
+      step0_fusion     Easy_PCD.fusion, sets (pcd[, direction])
+      step0_cell       the ConvLSTM cell, sets (direction) or one per-frame set
+      step1_pyramid    pyramids of step 1's state (h0, c0), sets (pcd[, direction]); on the window path the middle
+                       latent's input pyramids ride along as two more sets of ``pairs`` items."""
+    B = int(pairs)
+    if B < 1:
+        raise ValueError("step0_plan: at least one pair")
+    if not window:
+        return dict(frames=None, fwd=None, rev=None, zero_l1=(1, 3, 5, 7), launches=OrderedDict(
+            first_pcd=[B, B], first_fusion=[B], input_pyramid=[B] * 6, step0_pcd=[B] * 8, step0_fusion=[B] * 4,
+            step0_cell=[B, B], step1_pyramid=[B] * 4))
+    F = B + 1
+    return dict(frames=F, fwd=(0, B), rev=(1, F), zero_l1=(1, 3), launches=OrderedDict(
+        first_pcd=[B, B], first_fusion=[B], input_pyramid=[F, F], step0_pcd=[F] * 4, step0_fusion=[F, F],
+        step0_cell=[F], step1_pyramid=[F, F, B, B]))
 
 
 _NO_CAPTURE = ("a windowed / tiled decode reads the HRfeat bounding box back on the host: "
@@ -330,14 +372,19 @@ class LunaTokis(nn.Module):
             ops.dcn_sep([dict(om_layer=lay[n + ".conv_offset_mask"], layer=lay[n], fea=f, inp=x, out=o)
                          for n, f, x, o in fused], epi=epi, status=self._status)
         if rest:
-            n0, f0 = rest[0][0], rest[0][1]
-            om = self._empty(len(rest), *f0.shape[:3], 216)
+            om = self._sets([f.shape[0] for _, f, _, _ in rest], *rest[0][1].shape[1:3], 216)
             self._conv([dict(layer=lay[n + ".conv_offset_mask"], in0=f, out=om[i]) for i, (n, f, x, o) in enumerate(rest)],
                        epi=L.EPI_OFFMASK)
             self._dcn([dict(layer=lay[n], inp=x, offmask=om[i], out=o) for i, (n, f, x, o) in enumerate(rest)], epi=epi)
 
     def _empty(self, *shape):
         return torch.empty(*shape, device=self.device, dtype=torch.float32)
+
+    def _sets(self, counts, *shape):
+        """One buffer per weight set of a launch, set i with counts[i] items of ``shape``: slices of one
+        allocation, so all share the item stride a launch requires."""
+        flat, b = self._empty(sum(counts), *shape), _bases(counts)
+        return [flat[b[i]:b[i + 1]] for i in range(len(counts))]
 
     def _const(self, key, shape, make):
         """Maps that depend only on the packed weights and a shape (the all-zero initial state, its
@@ -454,13 +501,15 @@ class LunaTokis(nn.Module):
         self._conv([dict(layer=self.layers[name + ".conv2"], in0=tmp, out=x, res=x)], epi=L.EPI_RES)
 
     def _pyramid(self, srcs):
-        """fea_L2_conv1/2, fea_L3_conv1/2 with lrelu for a list of (L1 map, weight prefix)."""
-        G = len(srcs)
-        n, H, Wd, _ = srcs[0][0].shape
-        a2 = self._empty(G, n, H // 2, Wd // 2, 64)
-        b2 = self._empty(G, n, H // 2, Wd // 2, 64)
-        a3 = self._empty(G, n, H // 4, Wd // 4, 64)
-        b3 = self._empty(G, n, H // 4, Wd // 4, 64)
+        """fea_L2_conv1/2, fea_L3_conv1/2 with lrelu for a list of (L1 map, weight prefix): one launch per
+        layer over the sources as weight sets, each with its own number of items.  Returns the L2 and the
+        L3 maps, one per source."""
+        _, H, Wd, _ = srcs[0][0].shape
+        counts = [s.shape[0] for s, _ in srcs]
+        a2 = self._sets(counts, H // 2, Wd // 2, 64)
+        b2 = self._sets(counts, H // 2, Wd // 2, 64)
+        a3 = self._sets(counts, H // 4, Wd // 4, 64)
+        b3 = self._sets(counts, H // 4, Wd // 4, 64)
         lay = self.layers
         self._conv([dict(layer=lay[p + "fea_L2_conv1"], in0=s, out=a2[i]) for i, (s, p) in enumerate(srcs)],
                    epi=L.EPI_LRELU, stride=2)
@@ -473,21 +522,22 @@ class LunaTokis(nn.Module):
         return b2, b3
 
     def _pcd_align(self, units, zero_l1=()):
-        """PCD_Align.forward (:71-130) for up to 8 independent (module, direction) units.
+        """PCD_Align.forward (:71-130) for up to 16 independent (module, direction) units, each a weight set
+        of every launch with its own number of items (sets of frames and sets of pairs may share a launch;
+        the window's per-frame step 0 uses sets of frames, _step0_shared).
         unit = (prefix, d, fa[L1,L2,L3], fb[L1,L2,L3], y_out).  ``zero_l1``: indices of units whose
         fa L1 map is all zeros (the ConvLSTM's initial state, convlstm.py:60-63, sampled by the
         reversed-direction alignment of the first step): their L1 DCN samples only zeros, so its output
         is its bias wherever the offsets land (DCN_sep, dcn_v2.py:127-140: sum of 0 * w + b), and the
         L1 offset branch that only steers it (L1_offset_conv1..3, conv_offset_mask) is not run for
         them -- bit-identical to running it (for finite offsets)."""
-        G = len(units)
-        n, H, Wd, _ = units[0][2][0].shape
+        _, H, Wd, _ = units[0][2][0].shape
+        ns = [u[2][0].shape[0] for u in units]          # items per unit
         lay = self.layers
         lv = [(H, Wd), (H // 2, Wd // 2), (H // 4, Wd // 4)]
 
         def buf(level, c=64):
-            h_, w_ = lv[level]
-            return self._empty(G, n, h_, w_, c)
+            return self._sets(ns, *lv[level], c)
 
         def L_(u, name):
             return lay[f"{u[0]}{name}_{u[1]}"]
@@ -541,13 +591,14 @@ class LunaTokis(nn.Module):
         live = [(i, u) for i, u in E(units) if i not in zero_l1]
         d1 = buf(0)
         if live:
-            o1 = self._empty(len(live), n, H, Wd, 64)
+            nl = [ns[i] for i, _ in live]
+            o1 = self._sets(nl, H, Wd, 64)
             conv([dict(layer=L_(u, "L1_offset_conv1"), in0=u[2][0], in1=u[3][0], out=o1[k])
                   for k, (i, u) in E(live)], epi=L.EPI_LRELU, in1_mode=1)
-            o2 = self._empty(len(live), n, H, Wd, 64)
+            o2 = self._sets(nl, H, Wd, 64)
             conv([dict(layer=L_(u, "L1_offset_conv2"), in0=o1[k], in1=l2off[i], out=o2[k]) for k, (i, u) in E(live)],
                  epi=L.EPI_LRELU, in1_mode=2, in1_scale=2.0)
-            l1off = self._empty(len(live), n, H, Wd, 64)
+            l1off = self._sets(nl, H, Wd, 64)
             conv([dict(layer=L_(u, "L1_offset_conv3"), in0=o2[k], out=l1off[k]) for k, (i, u) in E(live)],
                  epi=L.EPI_LRELU)
             del o1, o2
@@ -556,8 +607,8 @@ class LunaTokis(nn.Module):
         # the zero-state units' L1 DCN output is its bias everywhere: a constant map, kept across calls
         d1z = {}
         for i in zero_l1:
-            b = L_(units[i], "L1_dcnpack").b
-            d1z[i] = self._const(("dcn_bias", b.data_ptr()), (n, H, Wd), lambda b=b: b.view(1, 1, 1, 64).expand(
+            b, n = L_(units[i], "L1_dcnpack").b, ns[i]
+            d1z[i] = self._const(("dcn_bias", b.data_ptr()), (n, H, Wd), lambda b=b, n=n: b.view(1, 1, 1, 64).expand(
                 n, H, Wd, 64).contiguous())
         with branch():
             conv_up(lambda i, u, c: dict(layer=L_(u, "L1_fea_conv"), in0=d1z.get(i, d1[i]), in1=c, out=u[4]),
@@ -565,28 +616,83 @@ class LunaTokis(nn.Module):
         if side is not None:
             main.wait_stream(side)   # before any buffer of this call can be freed and reused on main
 
-    def _bilstm_steps(self, X, feats=None):
+    def _step0_shared(self, fr):
+        """The BiConvLSTM's step 0 of a window chunk, once per frame.  ``fr``: [L1, L2, L3] of the chunk's
+        F = pairs + 1 frames.  Step 0 of either recurrence reads one frame, that frame's input pyramids and the
+        all-zero state, through the same ConvBLSTM.forward_net weights in both directions: reversed step 0 of
+        pair b and forward step 0 of pair b + 1 are the same function of frame b + 1, kernel for kernel, so it
+        runs once per frame (step0_plan): F items per weight set where the per-pair form has 2 (F - 1).
+        Returns (h0, c0, input pyramids): h0 / c0 [F, H, W, 64] -- read-only from here on, two recurrences
+        continue from every inner frame's -- and the frames' L2 / L3 input pyramids per pcd."""
+        F_, H, Wd, _ = fr[0].shape
+        lay = self.layers
+        pf = "ConvBLSTM.forward_net."
+        pcds = (pf + "pcd_h.", pf + "pcd_c.")
+        plan = step0_plan(F_ - 1, True)
+        zero = self._zeros(F_, H, Wd, 64)               # the initial h and c (convlstm.py:60-63), never written
+        fp2, fp3 = self._pyramid([(fr[0], pcds[p]) for p in range(2)])
+        zkey = ("zero_pyr", lay[pcds[0] + "fea_L2_conv1"].w.data_ptr())
+        z2, z3 = self._const(zkey, (F_, H, Wd), lambda: self._pyramid([(zero, pcds[p]) for p in range(2)]))
+        Y = self._sets(plan["launches"]["step0_pcd"], H, Wd, 64)     # (pcd, align direction)
+        units = []
+        for p in range(2):
+            f1, f2 = [fr[0], fp2[p], fp3[p]], [zero, z2[p], z3[p]]
+            units.append((pcds[p] + "pcd_align.", 1, f1, f2, Y[2 * p]))
+            units.append((pcds[p] + "pcd_align.", 2, f2, f1, Y[2 * p + 1]))
+        # the reversed alignments sample the all-zero initial state at L1
+        self._pcd_align(units, zero_l1=plan["zero_l1"])
+        T = self._empty(2, F_, H, Wd, 64)               # Easy_PCD.fusion outputs per pcd
+        self._conv([dict(layer=lay[pcds[p] + "fusion"], in0=Y[2 * p], in1=Y[2 * p + 1], out=T[p]) for p in range(2)],
+                   in1_mode=1)
+        h0, c0 = self._empty(F_, H, Wd, 64), self._empty(F_, H, Wd, 64)
+        self._conv([dict(layer=lay[pf + "cell_list.0.conv"], in0=fr[0], in1=T[0], res=T[1], out=h0, out2=c0)],
+                   epi=L.EPI_LSTM, in1_mode=1)
+        return h0, c0, (fp2, fp3)
+
+    def _bilstm_steps(self, X, feats=None, frames=None):
         """BiDeformableConvLSTM.forward (:256-266) with DeformableConvLSTM.forward (:192-242) for
         both directions batched.  X: the 3 latent inputs [B, H, W, 64] (t-major; views with one common
-        item stride).  Returns [3,B,H,W,64] (in ``feats`` when given)."""
+        item stride).  Returns [3,B,H,W,64] (in ``feats`` when given).
+        ``frames``: [L1, L2, L3] of the B + 1 frames whose adjacent pairs the items are (X[0] = their L1[:-1],
+        X[2] = L1[1:]): per-frame step 0 (_step0_shared), on the calling stream before the directions fork;
+        steps 1 and 2 follow per pair, pair b's forward recurrence from frame b's (h0, c0) and its reversed
+        one from frame b + 1's, as views of the per-frame buffers, which nothing writes (steps 1 and 2 put
+        their c elsewhere)."""
         B, H, Wd, _ = X[0].shape
         lay = self.layers
         pf = "ConvBLSTM.forward_net."
         pcds = (pf + "pcd_h.", pf + "pcd_c.")
-        hs = self._empty(2, 3, B, H, Wd, 64)            # h of (direction, step)
-        cs = self._empty(2, B, H, Wd, 64)               # c of the last step (step 0 reads the zero state)
-        zero = self._zeros(B, H, Wd, 64)                # the initial h and c (convlstm.py:60-63), never written
-        # Easy_PCD pyramids (:148-160) of the inputs, once per (pcd, input): the forward direction reads
-        # X[t] and the reversed one X[2 - t] with the same weights, so per-step pyramids of the inputs
-        # would compute each of them twice (bit-identical results, half the work); groups (pcd, t)
-        xp2, xp3 = self._pyramid([(X[t], pcds[p]) for p in range(2) for t in range(3)])
+        shared = frames is not None
+        cs = self._empty(2, B, H, Wd, 64)               # c of the last step run here (step 0 reads the zero state)
+        if shared:
+            h0, c0, (fp2, fp3) = self._step0_shared(frames)
+            plan = step0_plan(B, True)
+            fsl = [slice(*plan["fwd"]), slice(*plan["rev"])]   # the frames of direction d's step 0
+            hs12 = self._empty(2, 2, B, H, Wd, 64)      # h of (direction, step 1 / 2)
+            hs = {(d, t): h0[fsl[d]] if t == 0 else hs12[d, t - 1] for d in range(2) for t in range(3)}
+            # step 1's state pyramids once per frame, from h0 / c0; the middle latent's input pyramids (per
+            # pair) are two more weight sets of the same launches
+            s2, s3 = self._pyramid([(h0, pcds[0]), (c0, pcds[1]), (X[1], pcds[0]), (X[1], pcds[1])])
 
-        def xpyr(p, level, fr):
-            return (xp2 if level == 2 else xp3)[p * 3 + fr]
+            def xpyr(p, level, fr):
+                if fr == 1:
+                    return (s2 if level == 2 else s3)[2 + p]
+                return (fp2 if level == 2 else fp3)[p][fsl[fr // 2]]
+        else:
+            hs_ = self._empty(2, 3, B, H, Wd, 64)       # h of (direction, step)
+            hs = {(d, t): hs_[d, t] for d in range(2) for t in range(3)}
+            zero = self._zeros(B, H, Wd, 64)            # the initial h and c (convlstm.py:60-63), never written
+            # Easy_PCD pyramids (:148-160) of the inputs, once per (pcd, input): the forward direction reads
+            # X[t] and the reversed one X[2 - t] with the same weights, so per-step pyramids of the inputs
+            # would compute each of them twice (bit-identical results, half the work); groups (pcd, t)
+            xp2, xp3 = self._pyramid([(X[t], pcds[p]) for p in range(2) for t in range(3)])
 
-        # the step-0 state pyramids (zeros) once per pcd, depending on the weights only: kept across calls
-        zkey = ("zero_pyr", lay[pcds[0] + "fea_L2_conv1"].w.data_ptr())
-        z2, z3 = self._const(zkey, (B, H, Wd), lambda: self._pyramid([(zero, pcds[p]) for p in range(2)]))
+            def xpyr(p, level, fr):
+                return (xp2 if level == 2 else xp3)[p * 3 + fr]
+
+            # the step-0 state pyramids (zeros) once per pcd, depending on the weights only: kept across calls
+            zkey = ("zero_pyr", lay[pcds[0] + "fea_L2_conv1"].w.data_ptr())
+            z2, z3 = self._const(zkey, (B, H, Wd), lambda: self._pyramid([(zero, pcds[p]) for p in range(2)]))
 
         def step(t, ds):
             """Step t of the directions ds (0 forward, 1 reversed): state pyramids, PCD alignments,
@@ -594,10 +700,14 @@ class LunaTokis(nn.Module):
             fr = [t, 2 - t]                               # forward / reversed sequence
             xin = [X[f] for f in fr]
             pd = [(p, d) for p in range(2) for d in ds]
-            st = {(p, d): zero if t == 0 else (hs[d, t - 1] if p == 0 else cs[d]) for p, d in pd}
             if t == 0:
+                st = {k: zero for k in pd}
                 pyr = {(p, d): (z2[p], z3[p]) for p, d in pd}
+            elif shared and t == 1:
+                st = {(p, d): (h0 if p == 0 else c0)[fsl[d]] for p, d in pd}
+                pyr = {(p, d): (s2[p][fsl[d]], s3[p][fsl[d]]) for p, d in pd}
             else:
+                st = {(p, d): hs[d, t - 1] if p == 0 else cs[d] for p, d in pd}
                 a2, a3 = self._pyramid([(st[p, d], pcds[p]) for p, d in pd])
                 pyr = {k: (a2[i], a3[i]) for i, k in enumerate(pd)}
             nd = len(ds)
@@ -619,11 +729,12 @@ class LunaTokis(nn.Module):
                              out=hs[d, t], out2=cs[d]) for j, d in enumerate(ds)], epi=L.EPI_LSTM, in1_mode=1)
 
         def steps(ds):
-            for t in range(3):
+            for t in range(1 if shared else 0, 3):
                 step(t, ds)
                 yield
 
         # lstm_lanes = 2: the two directions are independent recurrences, one stream each, step by step
+        # (a window's per-frame step 0 ran before this fork, on the calling stream)
         yield from self._lockstep([steps((0, 1))] if self.lstm_lanes < 2 else [steps((0,)), steps((1,))], "lstm")
         if feats is None:
             feats = self._empty(3, B, H, Wd, 64)
@@ -631,10 +742,13 @@ class LunaTokis(nn.Module):
                     for t in range(3)], in1_mode=1)
         return feats
 
-    def _gen_feat_core(self, fea1, fea2, out):
+    def _gen_feat_core(self, fea1, fea2, out, frames=None):
         """Everything after the per-frame features: PCD + fusion, BiConvLSTM, recon trunk, into
         out [3, B, H, W, 64] (generator: yields between stages, see _lockstep).
-        fea1 / fea2: [L1, L2, L3] of the pairs' first / second frames (item = pair)."""
+        fea1 / fea2: [L1, L2, L3] of the pairs' first / second frames (item = pair).
+        ``frames``: [L1, L2, L3] of the B + 1 frames whose adjacent pairs these are (fea1 = frames[:-1],
+        fea2 = frames[1:]; the window path hands them down, nothing is inferred from addresses): the
+        BiConvLSTM's step 0 then runs once per frame (_bilstm_steps)."""
         B, H, Wd, _ = fea1[0].shape
         X1 = self._empty(B, H, Wd, 64)                  # the fused middle latent input
         Y = self._empty(2, B, H, Wd, 64)
@@ -648,7 +762,7 @@ class LunaTokis(nn.Module):
         if not all(x.stride(0) == X1.stride(0) for x in X):   # (a [1, ...] view counts as contiguous in torch)
             X = [X1 if x is X1 else self._empty(B, H, Wd, 64).copy_(x) for x in X]
         # the latents go straight into `out` when it is one contiguous block (one chunk of pairs)
-        feats = yield from self._bilstm_steps(X, out if out.is_contiguous() else None)
+        feats = yield from self._bilstm_steps(X, out if out.is_contiguous() else None, frames)
         del X, X1
         trunk = feats.view(3 * B, H, Wd, 64)
         tmp = self._empty(3 * B, H, Wd, 64)
@@ -656,17 +770,25 @@ class LunaTokis(nn.Module):
         if feats is not out:
             out.copy_(feats)
 
-    def _gen_feat_pairs(self, fea1, fea2, out):
+    def _gen_feat_pairs(self, fea1, fea2, out, frames=None):
         """_gen_feat_core over chunks of about ``chunk_px`` LR pixels of pairs (balanced), so the
         working set stays bounded at large frames; pairs are independent, so chunking does not
-        change a bit of the result (generator)."""
+        change a bit of the result (generator).  ``frames``: the per-frame features [L1, L2, L3] of the
+        B + 1 frames of a window (fea1 / fea2 are its adjacent pairs): a chunk of k pairs shares the
+        BiConvLSTM's first step among its own k + 1 frames (frames are shared inside a chunk only)."""
         B, H, Wd, _ = fea1[0].shape
+        if frames is not None:
+            if frames[0].shape[0] != B + 1:
+                raise ValueError(f"{B} pairs need the features of {B + 1} frames, got {frames[0].shape[0]}")
+            frames = [t.contiguous() for t in frames]    # one item stride for every set of the shared launches
+            fea1, fea2 = [t[:-1] for t in frames], [t[1:] for t in frames]
         per = max(1, self.chunk_px // (H * Wd))
         nch = math.ceil(B / per)
         per = math.ceil(B / nch)
         for c0 in range(0, B, per):
             c1 = min(B, c0 + per)
-            yield from self._gen_feat_core([t[c0:c1] for t in fea1], [t[c0:c1] for t in fea2], out[:, c0:c1])
+            yield from self._gen_feat_core([t[c0:c1] for t in fea1], [t[c0:c1] for t in fea2], out[:, c0:c1],
+                                           None if frames is None else [t[c0:c1 + 1] for t in frames])
 
     # ------------------------------------------------------------------ reference API
     def _check_input(self, x):
@@ -722,7 +844,7 @@ class LunaTokis(nn.Module):
             def lane(c0, c1):
                 l1, l2, l3 = yield from self._frame_features_steps(frames[c0:c1 + 1])
                 yield from self._gen_feat_pairs([l1[:-1], l2[:-1], l3[:-1]], [l1[1:], l2[1:], l3[1:]],
-                                                out[:, c0:c1])
+                                                out[:, c0:c1], [l1, l2, l3])
             self._run_lanes(F_ - 1, lane)
             self._feat = out
             return None
@@ -736,7 +858,7 @@ class LunaTokis(nn.Module):
                           for a, b in zip((a1, a2, a3), last_frame_feats))
         self._run_lanes(F_ - 1, lambda c0, c1: self._gen_feat_pairs(
             [l1[c0:c1], l2[c0:c1], l3[c0:c1]], [l1[c0 + 1:c1 + 1], l2[c0 + 1:c1 + 1], l3[c0 + 1:c1 + 1]],
-            out[:, c0:c1]))
+            out[:, c0:c1], [l1[c0:c1 + 1], l2[c0:c1 + 1], l3[c0:c1 + 1]]))
         self._feat = out
         return None
 

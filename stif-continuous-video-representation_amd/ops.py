@@ -117,12 +117,26 @@ def _split_by_mode(groups, key):
     return [f16, [g for g in groups if not g[key].mode & L.PACK_F16X3]] if 0 < len(f16) < len(groups) else None
 
 
+def _set_items(a, counts) -> int:
+    """Fill the launch's item counts from the groups' own (stif.h item_base): the uniform form (nitems, an all-zero
+    table) when they agree, else the prefix table.  Returns the launch's total items."""
+    a.ngroups = len(counts)
+    if len(set(counts)) == 1:
+        a.nitems = counts[0]
+    else:
+        a.nitems = 0
+        for i, c in enumerate(counts):
+            a.item_base[i + 1] = a.item_base[i] + c
+    return sum(counts)
+
+
 def conv2d(groups, *, epi=L.EPI_NONE, in1_mode=0, in1_scale=1.0, stride=None, status=None):
     """groups: list of dicts {layer: PackedConv, in0, [in1], out, [res], [out2]} with tensors
-    [nitems, H, W, C].  All groups share shapes and item strides.  status: optional int32 device
+    [nitems, H, W, C].  All groups share map shapes and item strides; each may carry its own number of items
+    (one launch of up to 16 weight sets).  status: optional int32 device
     word that f16x3 kernels set on a non-finite output (operand out of the split range)."""
     if not 1 <= len(groups) <= L.MAXG:
-        raise ValueError("conv2d: 1..8 groups")
+        raise ValueError(f"conv2d: 1..{L.MAXG} groups")
     parts = _split_by_mode(groups, "layer")
     if parts:
         for part in parts:
@@ -131,7 +145,7 @@ def conv2d(groups, *, epi=L.EPI_NONE, in1_mode=0, in1_scale=1.0, stride=None, st
     g0 = groups[0]
     lay: PackedConv = g0["layer"]
     in0 = g0["in0"]
-    nitems, H, W, C0 = in0.shape
+    _, H, W, C0 = in0.shape
     C1 = g0["in1"].shape[3] if in1_mode else 0
     ks = lay.ks
     if stride is None:
@@ -150,14 +164,20 @@ def conv2d(groups, *, epi=L.EPI_NONE, in1_mode=0, in1_scale=1.0, stride=None, st
         a.out[i] = _vp(g["out"])
         a.res[i] = _vp(g.get("res"))
         a.out2[i] = _vp(g.get("out2"))
+        nitems = g["in0"].shape[0]
+        if tuple(g["in0"].shape[1:]) != (H, W, C0):
+            raise ValueError(f"conv2d: in0 shape {tuple(g['in0'].shape)} != {(nitems, H, W, C0)}")
         if tuple(g["out"].shape[:3]) != (nitems, Ho, Wo):
             raise ValueError(f"conv2d: output shape {tuple(g['out'].shape)} != {(nitems, Ho, Wo)}")
+        for k in ("in1", "res", "out2"):
+            if g.get(k) is not None and g[k].shape[0] != nitems:
+                raise ValueError(f"conv2d: {k} holds {g[k].shape[0]} items, in0 {nitems}")
     a.in0_item = _item_stride([g["in0"] for g in groups], "in0")
     a.in1_item = _item_stride([g.get("in1") for g in groups], "in1") if in1_mode else 0
     a.out_item = _item_stride([g["out"] for g in groups], "out")
     a.res_item = _item_stride([g.get("res") for g in groups], "res")
     a.out2_item = _item_stride([g.get("out2") for g in groups], "out2")
-    a.ngroups, a.nitems = len(groups), nitems
+    total = _set_items(a, [g["in0"].shape[0] for g in groups])
     a.H, a.W, a.C0, a.C1 = H, W, C0, C1
     a.in1_mode, a.in1_scale = in1_mode, in1_scale
     a.Ho, a.Wo, a.cout, a.ks, a.stride, a.epi = Ho, Wo, lay.cout, ks, stride, epi
@@ -176,12 +196,12 @@ def conv2d(groups, *, epi=L.EPI_NONE, in1_mode=0, in1_scale=1.0, stride=None, st
     if TRACE is not None:
         # algorithmic (direct-convolution) FLOPs, whichever algorithm runs
         # algorithmic HBM bytes: every input read once, every output written once
-        px_in, px_out = H * W * nitems * len(groups), Ho * Wo * nitems * len(groups)
+        px_in, px_out = H * W * total, Ho * Wo * total   # over the sets' own item counts
         c_in = C0 + (C1 if in1_mode == 1 else C1 / 4.0 if in1_mode == 2 else 0)
         c_out = 128 if epi == L.EPI_LSTM else lay.cout
         c_res = 64 if epi in (L.EPI_RES, L.EPI_LSTM) else 0
         trace = (("wino" if wino else "conv", ks, stride, epi, in1_mode, lay.cout),
-                 2.0 * lay.cout * (C0 + C1) * ks * ks * Ho * Wo * nitems * len(groups),
+                 2.0 * lay.cout * (C0 + C1) * ks * ks * Ho * Wo * total,
                  4.0 * (c_in * px_in + (c_out + c_res) * px_out))
     if wino:
         _launch("stif_conv3x3_wino", trace, L.lib().stif_conv3x3_wino, C.byref(a), _stream())
@@ -467,11 +487,15 @@ def dcn(groups, *, epi=L.EPI_NONE, status=None):
         for part in parts:
             dcn(part, epi=epi, status=status)
         return
+    if not 1 <= len(groups) <= L.MAXG:
+        raise ValueError(f"dcn: 1..{L.MAXG} groups")
     g0 = groups[0]
-    nitems, H, W, Cc = g0["inp"].shape
+    _, H, W, Cc = g0["inp"].shape
     assert Cc == 64
     a = L.DcnArgs()
     for i, g in enumerate(groups):
+        if not g["inp"].shape[0] == g["offmask"].shape[0] == g["out"].shape[0]:
+            raise ValueError("dcn: inp / offmask / out of a group must hold the same number of items")
         a.inp[i] = _vp(g["inp"])
         a.offmask[i] = _vp(g["offmask"])
         a.w[i] = _vp(g["layer"].w)
@@ -480,14 +504,14 @@ def dcn(groups, *, epi=L.EPI_NONE, status=None):
     a.in_item = _item_stride([g["inp"] for g in groups], "dcn in")
     a.om_item = _item_stride([g["offmask"] for g in groups], "dcn offmask")
     a.out_item = _item_stride([g["out"] for g in groups], "dcn out")
-    a.ngroups, a.nitems, a.H, a.W, a.epi = len(groups), nitems, H, W, epi
+    total = _set_items(a, [g["inp"].shape[0] for g in groups])
+    a.H, a.W, a.epi = H, W, epi
     f16 = g0["layer"].mode & L.PACK_F16X3
     a.flags = L.CONV_F16X3 if f16 else 0
     a.status = _vp(status)
     trace = None
     if TRACE is not None:
-        trace = (("dcn", epi), 2.0 * 64 * 576 * H * W * nitems * len(groups),
-                 4.0 * (64 + 216 + 64) * H * W * nitems * len(groups))
+        trace = (("dcn", epi), 2.0 * 64 * 576 * H * W * total, 4.0 * (64 + 216 + 64) * H * W * total)
     _launch("stif_dcn_nhwc", trace, L.lib().stif_dcn_nhwc, C.byref(a), _stream())
 
 
@@ -579,13 +603,14 @@ def dcn_sep(groups, *, epi=L.EPI_NONE, status=None):
     groups: list of {om_layer: PackedConv (STIF_PACK_DCNSEP | F16X3), layer: PackedConv (64->64 3x3,
     STIF_PACK_DCNPAIR | F16X3), fea, inp, out} with NHWC [nitems, H, W, 64] tensors."""
     if not 1 <= len(groups) <= L.MAXG:
-        raise ValueError("dcn_sep: 1..8 groups")
+        raise ValueError(f"dcn_sep: 1..{L.MAXG} groups")
     g0 = groups[0]
-    nitems, H, W, Cc = g0["inp"].shape
+    _, H, W, Cc = g0["inp"].shape
     a = L.DcnSepArgs()
     for i, g in enumerate(groups):
         if not dcn_sep_fusable(g["om_layer"], g["layer"]):
             raise ValueError("dcn_sep: layers not packed for the fused kernel")
+        nitems = g["inp"].shape[0]   # each group may carry its own number of items
         for k in ("fea", "inp", "out"):
             if tuple(g[k].shape) != (nitems, H, W, 64):
                 raise ValueError(f"dcn_sep: {k} shape {tuple(g[k].shape)} != {(nitems, H, W, 64)}")
@@ -599,12 +624,13 @@ def dcn_sep(groups, *, epi=L.EPI_NONE, status=None):
     a.fea_item = _item_stride([g["fea"] for g in groups], "dcn_sep fea")
     a.in_item = _item_stride([g["inp"] for g in groups], "dcn_sep in")
     a.out_item = _item_stride([g["out"] for g in groups], "dcn_sep out")
-    a.ngroups, a.nitems, a.H, a.W, a.epi = len(groups), nitems, H, W, epi
+    total = _set_items(a, [g["inp"].shape[0] for g in groups])
+    a.H, a.W, a.epi = H, W, epi
     a.flags = L.CONV_F16X3
     a.status = _vp(status)
     trace = None
     if TRACE is not None:
-        px = H * W * nitems * len(groups)
+        px = H * W * total
         # algorithmic: the offset/mask conv (216 x 576 MACs) + the deformable conv (64 x 576) per pixel;
         # HBM bytes: the offset feature, the DCN input and the output read / written once (768 B / px)
         trace = (("dcnsep", epi), 2.0 * (216 + 64) * 576 * px, 4.0 * 3 * 64 * px)
