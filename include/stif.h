@@ -180,7 +180,8 @@ int stif_conv_first_wgrad(const float* x_nchw, const float* gy, float* gw, float
  * x[0], x[1]: the halves of the forward's concatenated input (nx = 2; the concatenation is never built), NHWC
  * 64-channel maps; gy: NHWC with a pixel pitch of gy_channels floats of which the first cout count (the rest is never read).
  * Supported (nx, gy_channels, cout): (2, 64, 64) the 128 -> 64 concatenation convs, (1, 256, 216) conv_offset_mask
- * with its gradient in the zero-padded 256-channel map the Winograd conv writes, (1, 64, 64) = stif_conv3x3_wgrad.
+ * with its gradient in the zero-padded 256-channel map the Winograd conv writes, (1, 64, 64) = stif_conv3x3_wgrad,
+ * (2, 256, 256) the ConvLSTM cell's 128 -> 256 conv on (input | hidden state), eight blocks.
  * One launch computes every block (cout slice, x map) as stif_conv3x3_wgrad's walk over the same tiles with the same
  * grid, one partial per workgroup and block, and a second adds each block's partials in index order: no
  * floating-point atomics, identical bits for repeated calls, and every 64 x 64 block of gw equals
@@ -197,13 +198,42 @@ typedef struct {
   long long x_item[2], gy_item;
   int n, H, W;
   int nx;                  /* 1 or 2 */
-  int gy_channels, cout;   /* (64, 64) or (256, 216): the pixel pitch of gy and the channels that count */
+  int gy_channels, cout;   /* (64, 64), (256, 216) or (256, 256): the pixel pitch of gy and the channels that count */
   void* workspace;
   size_t workspace_bytes;
 } stif_conv_wgrad_cat_args;
 /* 0 for sizes < 1 or unsupported channel counts. */
 size_t stif_conv3x3_wgrad_cat_workspace_size(int n, int H, int W, int nx, int gy_channels, int cout);
 int stif_conv3x3_wgrad_cat(const stif_conv_wgrad_cat_args* args, void* stream);
+
+/* The weight and bias gradient of the 1x1 conv on one or two 64-channel inputs (fusion, Easy_PCD.fusion,
+ * ConvBLSTM.conv_1x1: (64 | 64) -> 64; nx = 1 is the 64 -> 64 form), training:
+ *   gw[co][64 i + ci] = sum_{n,y,x} gy[n][y][x][co] * x[i][n][y][x][ci],   gb[co] = sum_{n,y,x} gy[n][y][x][co].
+ * The arguments are stif_conv_wgrad_cat_args with gy_channels = cout = 64; gw is [64][64 nx][1][1] OIHW.  fp32 MFMA,
+ * and the deterministic scheme of stif_conv3x3_wgrad: the grid is a function of the shape and the CU count, every
+ * workgroup writes one partial, a second kernel adds them in an order fixed by their number (sixteen interleaved
+ * index-ordered slices, then the slices in order: no atomics, identical bits for repeated calls); the workspace (stif_conv1x1_wgrad_workspace_size bytes, 0 for sizes < 1 or nx outside {1, 2}; 16-B aligned)
+ * may hold anything on entry.  STIF_E_INVALID before any launch as for stif_conv3x3_wgrad_cat. */
+size_t stif_conv1x1_wgrad_workspace_size(int n, int H, int W, int nx);
+int stif_conv1x1_wgrad(const stif_conv_wgrad_cat_args* args, void* stream);
+
+/* The ConvLSTM cell's gates (convlstm.py:44-57) on the pre-activations of its 128 -> 256 conv, for training: pre
+ * [n][H][W][256] in the reference's row order (channel gate * 64 + h, gates i, f, o, g: what stif_conv3x3_wino writes
+ * with STIF_EPI_NONE from a STIF_PACK_WINO pack of the weight), c_cur / h_next / c_next [n][H][W][64]:
+ *   c_next = sigmoid(f) c_cur + sigmoid(i) tanh(g),   h_next = sigmoid(o) tanh(c_next).
+ * Items *_item floats apart (>= 0, multiples of 4; bases 16-B aligned; pixels contiguous); finite for any finite
+ * pre-activation.  STIF_E_INVALID before the launch: a null pointer, n / H / W < 1, a negative or misaligned stride or
+ * base, an item of 2 GB or more (H W 256 floats), output items that overlap. */
+int stif_lstm_gates_nhwc(const float* pre, const float* c_cur, float* h_next, float* c_next, int n, int H, int W,
+                         long long pre_item, long long c_item, long long h_item, long long cn_item, void* stream);
+/* Its backward.  The forward saves only pre and c_cur; the gates and tanh(c_next) are recomputed.  With
+ * dc = g_c_next + g_h o (1 - tanh^2 c_next):  g_pre_i = dc g i (1 - i), g_pre_f = dc c_cur f (1 - f),
+ * g_pre_o = g_h tanh(c_next) o (1 - o), g_pre_g = dc i (1 - g^2), g_c_cur = dc f.  g_h or g_c_next may be NULL (zeros;
+ * both NULL is STIF_E_INVALID), g_c_cur may be NULL (not computed); g_pre [n][H][W][256].  Checks as the forward's. */
+int stif_lstm_gates_bwd_nhwc(const float* pre, const float* c_cur, const float* g_h, const float* g_c_next,
+                             float* g_pre, float* g_c_cur, int n, int H, int W, long long pre_item, long long c_item,
+                             long long gh_item, long long gcn_item, long long gpre_item, long long gcc_item,
+                             void* stream);
 
 /* The adjoint of stif_upsample2x_nhwc: gx = the transpose of scale * F.interpolate(scale_factor=2, bilinear,
  * align_corners=False) applied to gy [n][2 h1][2 w1][c]; gx [n][h1][w1][c], c % 4 == 0, items gy_item / gx_item floats
@@ -498,7 +528,9 @@ int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, int cout, int
 int stif_pack_conv_plain_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, float* w_dst,
                              float* b_dst, void* stream);
 /* stif_pack_conv_weight_dev for one 64 x 64 block of a larger 3x3 weight: rows [co0, co0 + 64) and columns
- * [ci0, ci0 + 64) of the OIHW weight [cout][cin][3][3], cout 64 or 216, cin 64 or 128, co0 / ci0 multiples of 64
+ * [ci0, ci0 + 64) of the OIHW weight [cout][cin][3][3], cout 64 or 216 with cin 64 or 128, or the ConvLSTM cell's
+ * [256][128] (eight blocks in row order are its pack, the four STIF_PACK_DGRAD row blocks of column block ci0 the
+ * data gradient's 256 -> 64 weight of that input half), co0 / ci0 multiples of 64
  * inside it (anything else is STIF_E_INVALID before the launch); rows at or past cout read as zeros, and so does
  * their bias.  Writes one 64 -> 64 pack (stif_conv_weight_floats(64, 64, 3, mode) floats) at w_dst and 64 biases
  * (b[co0 ..], zeros with STIF_PACK_DGRAD) at b_dst; modes, flags and status as stif_pack_conv_weight_dev.  A Winograd
@@ -508,6 +540,14 @@ int stif_pack_conv_plain_dev(const float* w_oihw, const float* b, int cout, int 
  * STIF_PACK_DGRAD pack of one column block of [64][128] is the data gradient's weight for that input half. */
 int stif_pack_conv_block_dev(const float* w_oihw, const float* b, int cout, int cin, int co0, int ci0, int mode,
                              int flags, float* w_dst, float* b_dst, int* status, void* stream);
+/* The packer of the 1x1 (64 | 64) -> 64 layers on the device: w_oihw [64][128][1][1], cout 64, cin 128, ks 1 (anything
+ * else is STIF_E_INVALID).  mode STIF_PACK_PLAIN or STIF_PACK_PLAIN | STIF_PACK_F16X3 with ci0 = 0: byte for byte what
+ * stif_pack_conv_weight(ks = 1) writes in that mode; where the host packer returns STIF_E_RANGE the kernel ORs
+ * STIF_STATUS_PACK_RANGE into *status (required with STIF_PACK_F16X3).  flags = STIF_PACK_DGRAD (mode STIF_PACK_PLAIN,
+ * ci0 = 0 or 64): the fp32 pack of the transposed 64 -> 64 layer w'[ci][co] = w[co][ci0 + ci] with a zero bias (b may
+ * be NULL), so that the 1x1 conv of grad_output is the gradient of that input half. */
+int stif_pack_conv1x1_dev(const float* w_oihw, const float* b, int cout, int cin, int ci0, int mode, int flags,
+                          float* w_dst, float* b_dst, int* status, void* stream);
 
 size_t stif_dec_proj_floats(void);   /* packed fp32 1x1 weight of the LR projection: [25][256][1][8]; the
                                         f16x3 packing: stif_conv_weight_floats(256, 200, 1, STIF_PACK_PLAIN | STIF_PACK_F16X3) */

@@ -177,6 +177,11 @@ EXPORTS = {
     "stif_upsample2x_bwd_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,
                                            C.c_longlong, _P]),
     "stif_pack_conv_block_dev": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P, _P, _P]),
+    "stif_conv1x1_wgrad_workspace_size": (C.c_size_t, [C.c_int] * 4),
+    "stif_conv1x1_wgrad": (C.c_int, [C.POINTER(ConvWgradCatArgs), _P]),
+    "stif_pack_conv1x1_dev": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, _P, _P]),
+    "stif_lstm_gates_nhwc": (C.c_int, [_P] * 4 + [C.c_int] * 3 + [C.c_longlong] * 4 + [_P]),
+    "stif_lstm_gates_bwd_nhwc": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_longlong] * 6 + [_P]),
     "stif_upsample2x_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,
                                        C.c_longlong, _P]),
     "stif_conv_first": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -8,6 +8,8 @@
 // And what PCD_Align's backward lacked: the weight gradient in 64 x 64 channel blocks (the
 // 128 -> 64 concatenation convs, the 64 -> 216 offset / mask conv), the adjoint of the x2 bilinear upsample, and the
 // Winograd packer for a 64 x 64 block of a wider weight.
+// The ConvLSTM cell's 128 -> 256 conv is eight more such blocks: (nx, gy_channels, cout) =
+// (2, 256, 256) in the block weight gradient, a [256][128] weight in the block packer.
 #include <algorithm>
 #include <cstdio>
 
@@ -585,6 +587,7 @@ int fail_as(const char* fn, const char* why) {
 int wgrad_cat_blocks(int nx, int gy_channels, int cout) {
   if (gy_channels == 64 && cout == 64 && (nx == 1 || nx == 2)) return nx;
   if (gy_channels == 256 && cout == 216 && nx == 1) return 4;
+  if (gy_channels == 256 && cout == 256 && nx == 2) return 8;   // the ConvLSTM cell's 128 -> 256 conv
   return 0;
 }
 
@@ -618,7 +621,8 @@ extern "C" int stif_conv3x3_wgrad_cat(const stif_conv_wgrad_cat_args* pa, void* 
   if (!a.x[0] || !a.gy || !a.gw) return fail_as(fn, "null pointer (x[0], gy, gw)");
   if (a.n < 1 || a.H < 1 || a.W < 1) return fail_as(fn, "n, H, W must be >= 1");
   const int blocks = wgrad_cat_blocks(a.nx, a.gy_channels, a.cout);
-  if (!blocks) return fail_as(fn, "unsupported channel counts (nx, gy_channels, cout: 2/64/64, 1/256/216, 1/64/64)");
+  if (!blocks)
+    return fail_as(fn, "unsupported channel counts (nx, gy_channels, cout: 2/64/64, 1/256/216, 1/64/64, 2/256/256)");
   const bool two = a.nx == 2;
   if (two && !a.x[1]) return fail_as(fn, "null pointer (x[1] with nx = 2)");
   if (a.x_item[0] < 0 || (two && a.x_item[1] < 0) || a.gy_item < 0) return fail_as(fn, "negative item stride");
@@ -751,8 +755,8 @@ extern "C" int stif_pack_conv_block_dev(const float* w_oihw, const float* b, int
   if (!w_oihw || !w_dst || !b_dst) return fail_as(fn, "null pointer (w_oihw, w_dst, b_dst)");
   if (mode != STIF_PACK_WINO && mode != (STIF_PACK_WINO | STIF_PACK_F16X3))
     return fail_as(fn, "unsupported mode (STIF_PACK_WINO [| STIF_PACK_F16X3] only)");
-  if ((cout != 64 && cout != 216) || (cin != 64 && cin != 128))
-    return fail_as(fn, "unsupported channel counts (cout 64 or 216, cin 64 or 128)");
+  if (((cout != 64 && cout != 216) || (cin != 64 && cin != 128)) && !(cout == 256 && cin == 128))
+    return fail_as(fn, "unsupported channel counts (cout 64 or 216 with cin 64 or 128, or 256 with 128)");
   if (co0 < 0 || co0 % 64 || co0 >= cout || ci0 < 0 || ci0 % 64 || ci0 >= cin)
     return fail_as(fn, "co0 / ci0 must be multiples of 64 inside the weight");
   if (flags & ~STIF_PACK_DGRAD) return fail_as(fn, "unknown flags");

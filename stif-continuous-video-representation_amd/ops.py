@@ -401,9 +401,10 @@ def upsample2x_bwd(gy: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
 def conv3x3_wgrad_cat(xs, gy: torch.Tensor, cout: int):
     """Weight and bias gradient of a 3x3 'same' conv in 64 x 64 channel blocks (stif_conv3x3_wgrad_cat).  ``xs``: the
     one or two NHWC 64-channel maps whose concatenation was the forward's input (never built); ``gy``: [n, H, W, 64] with
-    ``cout`` = 64, or the 256-channel map of the 64 -> 216 offset / mask conv with ``cout`` = 216 (channels 216.. are
-    never read).  Returns (gw [cout, 64 len(xs), 3, 3] OIHW, gb [cout]).  Every 64 x 64 block of gw has the bits
-    conv3x3_wgrad returns for the same two maps; repeated calls give identical bits."""
+    ``cout`` = 64, the 256-channel map of the 64 -> 216 offset / mask conv with ``cout`` = 216 (channels 216.. are
+    never read), or with two x maps the ConvLSTM cell's 256 pre-activation gradients with ``cout`` = 256.  Returns
+    (gw [cout, 64 len(xs), 3, 3] OIHW, gb [cout]).  Every 64 x 64 block of gw has the bits conv3x3_wgrad returns for the
+    same two maps; repeated calls give identical bits."""
     xs = list(xs)
     if len(xs) not in (1, 2) or gy.dim() != 4 or any(x.dim() != 4 or x.shape[3] != 64 or x.shape[:3] != gy.shape[:3]
                                                       for x in xs):
@@ -411,7 +412,7 @@ def conv3x3_wgrad_cat(xs, gy: torch.Tensor, cout: int):
                          f"{[tuple(x.shape) for x in xs]} and {tuple(gy.shape)}")
     n, H, W, gc = gy.shape
     nx = len(xs)
-    if (nx, gc, cout) not in ((2, 64, 64), (1, 256, 216), (1, 64, 64)):
+    if (nx, gc, cout) not in ((2, 64, 64), (1, 256, 216), (1, 64, 64), (2, 256, 256)):
         raise ValueError(f"conv3x3_wgrad_cat: unsupported channel counts (nx, gy channels, cout) = {(nx, gc, cout)}")
     lib = L.lib()
     a = L.ConvWgradCatArgs()
@@ -442,7 +443,11 @@ def pack_conv_blocks_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mod
     * ``weight`` [216, 64]: the 64 -> 216 layer with its rows zero-padded to 256 (the bytes of ops.pack_conv; the
       PackedConv says cout = 256, which is what stif_conv3x3_wino writes), its four row blocks;
     * ``weight`` [216, 64], ``dgrad``: the data gradient's 256 -> 64 layer, the four DGRAD row blocks;
-    * ``weight`` [64, 128], ``dgrad``, ``half`` = 0 or 1: the data gradient's 64 -> 64 layer of that input half.
+    * ``weight`` [64, 128], ``dgrad``, ``half`` = 0 or 1: the data gradient's 64 -> 64 layer of that input half;
+    * ``weight`` [256, 128]: the ConvLSTM cell's 128 -> 256 layer in the reference's row order (the bytes of
+      ops.pack_conv with PACK_WINO), its eight blocks in row order;
+    * ``weight`` [256, 128], ``dgrad``, ``half`` = 0 or 1: the data gradient's 256 -> 64 layer of that input half, four
+      DGRAD row blocks.
 
     ``bias`` may be None with ``dgrad`` (the bias is zero then); ``status`` as ops.pack_conv_dev."""
     if not (weight.is_cuda and weight.dtype == torch.float32):
@@ -457,6 +462,10 @@ def pack_conv_blocks_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mod
         cout, cin = (64, 256) if dgrad else (256, 64)
     elif shape == (64, 128, 3, 3) and dgrad and half in (0, 1):
         blocks, cout, cin = [(0, 64 * half)], 64, 64
+    elif shape == (256, 128, 3, 3) and not dgrad and half is None:
+        blocks, cout, cin = [(64 * s, 64 * c) for s in range(4) for c in range(2)], 256, 128
+    elif shape == (256, 128, 3, 3) and dgrad and half in (0, 1):
+        blocks, cout, cin = [(64 * s, 64 * half) for s in range(4)], 64, 256
     else:
         raise ValueError(f"pack_conv_blocks_dev: no block form for weight {shape}, dgrad={dgrad}, half={half}")
     weight = weight.detach().contiguous()
@@ -472,6 +481,111 @@ def pack_conv_blocks_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mod
                 shape[1], co0, ci0, mode, L.PACK_DGRAD if dgrad else 0, _vp(wd[i * per:]), _vp(bi), _vp(status),
                 _stream())
     return PackedConv(wd, bd, cout, cin, 3, mode)
+
+
+def conv1x1_wgrad(xs, gy: torch.Tensor):
+    """Weight and bias gradient of the 1x1 conv on one or two 64-channel inputs (stif_conv1x1_wgrad): ``xs`` the NHWC
+    maps whose concatenation was the forward's input (never built), ``gy`` [n, H, W, 64]; any item strides, pixels
+    contiguous.  Returns (gw [64, 64 len(xs), 1, 1] OIHW, gb [64]); repeated calls give identical bits (no atomics)."""
+    xs = list(xs)
+    if len(xs) not in (1, 2) or gy.dim() != 4 or gy.shape[3] != 64 or any(x.dim() != 4 or x.shape != gy.shape
+                                                                             for x in xs):
+        raise ValueError(f"conv1x1_wgrad: one or two x maps and a gy, all [n, H, W, 64], got "
+                         f"{[tuple(x.shape) for x in xs]} and {tuple(gy.shape)}")
+    n, H, W, _ = gy.shape
+    nx = len(xs)
+    lib = L.lib()
+    a = L.ConvWgradCatArgs()
+    for i, x in enumerate(xs):
+        a.x[i], a.x_item[i] = _vp(x), _item_stride([x], "conv1x1_wgrad x")
+    gy_item = _item_stride([gy], "conv1x1_wgrad gy")
+    ws, stream = _wgrad_workspace(gy.device, lib.stif_conv1x1_wgrad_workspace_size(n, H, W, nx))
+    gw = torch.empty(64, 64 * nx, 1, 1, dtype=torch.float32, device=gy.device)
+    gb = torch.empty(64, dtype=torch.float32, device=gy.device)
+    a.gy, a.gw, a.gb, a.gy_item = _vp(gy), _vp(gw), _vp(gb), gy_item
+    a.n, a.H, a.W, a.nx, a.gy_channels, a.cout = n, H, W, nx, 64, 64
+    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
+    trace = None
+    if TRACE is not None:
+        trace = (("wgrad_1x1", nx), 2.0 * 64 * 64 * nx * n * H * W, 4.0 * 64 * (1 + nx) * n * H * W)
+    _launch("stif_conv1x1_wgrad", trace, lib.stif_conv1x1_wgrad, C.byref(a), stream)
+    return gw, gb
+
+
+def pack_conv1x1_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mode: int = L.PACK_PLAIN, dgrad: bool = False,
+                     half: Optional[int] = None, status: Optional[torch.Tensor] = None) -> PackedConv:
+    """The packing on the device of a 1x1 (64 | 64) -> 64 layer (stif_pack_conv1x1_dev): ``weight`` [64, 128, 1, 1],
+    ``mode`` PACK_PLAIN or PACK_PLAIN | PACK_F16X3 -- the bytes of ops.pack_conv, the layer ops.conv2d(in1_mode=1)
+    reads.  ``dgrad`` with ``half`` = 0 or 1: the fp32 pack of the transposed 64 -> 64 layer of that input half (zero
+    bias; ``bias`` may be None).  ``status`` as ops.pack_conv_dev."""
+    if not (weight.is_cuda and weight.dtype == torch.float32):
+        raise ValueError("pack_conv1x1_dev: expected a float32 CUDA weight")
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
+        raise ValueError("pack_conv1x1_dev: expected a float32 CUDA bias")
+    if tuple(weight.shape) != (64, 128, 1, 1) or (half is not None) != dgrad or half not in (None, 0, 1):
+        raise ValueError(f"pack_conv1x1_dev: no form for weight {tuple(weight.shape)}, dgrad={dgrad}, half={half}")
+    weight = weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    cin = 64 if dgrad else 128
+    lib = L.lib()
+    wd = torch.empty(lib.stif_conv_weight_floats(64, cin, 1, mode), dtype=torch.float32, device=weight.device)
+    bd = torch.empty(lib.stif_conv_bias_floats(64, mode), dtype=torch.float32, device=weight.device)
+    _launch("stif_pack_conv1x1_dev", None, lib.stif_pack_conv1x1_dev, _vp(weight), _vp(bias), 64, 128,
+            64 * half if dgrad else 0, mode, L.PACK_DGRAD if dgrad else 0, _vp(wd), _vp(bd), _vp(status), _stream())
+    return PackedConv(wd, bd, 64, cin, 1, mode)
+
+
+def _lstm_maps(what, pre, maps):
+    """Check the gate kernels' maps (``pre`` [n, H, W, 256], the others [n, H, W, 64] or None); their item strides."""
+    if pre.dim() != 4 or pre.shape[3] != 256 or 0 in pre.shape:
+        raise ValueError(f"{what}: pre {tuple(pre.shape)} must be [n, H, W, 256]")
+    want = tuple(pre.shape[:3]) + (64,)
+    for name, t in maps:
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} must be {want}")
+    return [_item_stride([t], f"{what} {name}") for name, t in [("pre", pre)] + list(maps)]
+
+
+def lstm_gates(pre: torch.Tensor, c_cur: torch.Tensor, h_next: Optional[torch.Tensor] = None,
+               c_next: Optional[torch.Tensor] = None):
+    """The ConvLSTM cell's gates (stif_lstm_gates_nhwc): NHWC ``pre`` [n, H, W, 256] in the reference's row order
+    (gates i, f, o, g of 64 hidden channels each) and ``c_cur`` [n, H, W, 64] -> (h_next, c_next), new tensors unless
+    given.  Items may be strided; pixels contiguous."""
+    n, H, W = pre.shape[:3] if pre.dim() == 4 else (0, 0, 0)
+    if h_next is None:
+        h_next = torch.empty(n, H, W, 64, dtype=torch.float32, device=pre.device)
+    if c_next is None:
+        c_next = torch.empty(n, H, W, 64, dtype=torch.float32, device=pre.device)
+    items = _lstm_maps("lstm_gates", pre, [("c_cur", c_cur), ("h_next", h_next), ("c_next", c_next)])
+    trace = (("lstm_gates",), 0.0, 4.0 * (256 + 3 * 64) * n * H * W) if TRACE is not None else None
+    _launch("stif_lstm_gates_nhwc", trace, L.lib().stif_lstm_gates_nhwc, _vp(pre), _vp(c_cur), _vp(h_next), _vp(c_next),
+            n, H, W, *items, torch.cuda.current_stream(pre.device).cuda_stream)
+    return h_next, c_next
+
+
+def lstm_gates_bwd(pre: torch.Tensor, c_cur: torch.Tensor, g_h: Optional[torch.Tensor],
+                   g_c_next: Optional[torch.Tensor], need_c: bool = True, g_pre: Optional[torch.Tensor] = None,
+                   g_c_cur: Optional[torch.Tensor] = None):
+    """The backward of lstm_gates (stif_lstm_gates_bwd_nhwc), the gates recomputed from the forward's inputs ``pre``
+    and ``c_cur``: ``g_h`` / ``g_c_next`` the gradients of its outputs, either None for zeros (not both).  Returns
+    (g_pre [n, H, W, 256], g_c_cur [n, H, W, 64] or None when ``need_c`` is false)."""
+    if g_h is None and g_c_next is None:
+        raise ValueError("lstm_gates_bwd: g_h and g_c_next are both None")
+    n, H, W = pre.shape[:3] if pre.dim() == 4 else (0, 0, 0)
+    if g_pre is None:
+        g_pre = torch.empty(n, H, W, 256, dtype=torch.float32, device=pre.device)
+    if g_c_cur is None and need_c:
+        g_c_cur = torch.empty(n, H, W, 64, dtype=torch.float32, device=pre.device)
+    if tuple(g_pre.shape) != tuple(pre.shape):
+        raise ValueError(f"lstm_gates_bwd: g_pre {tuple(g_pre.shape)} must be {tuple(pre.shape)}")
+    items = _lstm_maps("lstm_gates_bwd", pre, [("c_cur", c_cur), ("g_h", g_h), ("g_c_next", g_c_next)])
+    items += [_item_stride([g_pre], "lstm_gates_bwd g_pre")]
+    items += _lstm_maps("lstm_gates_bwd", pre, [("g_c_cur", g_c_cur)])[1:]
+    moved = 2 * 256 + 64 * (1 + (g_h is not None) + (g_c_next is not None) + (g_c_cur is not None))
+    trace = (("lstm_gates_bwd",), 0.0, 4.0 * moved * n * H * W) if TRACE is not None else None
+    _launch("stif_lstm_gates_bwd_nhwc", trace, L.lib().stif_lstm_gates_bwd_nhwc, _vp(pre), _vp(c_cur), _vp(g_h),
+            _vp(g_c_next), _vp(g_pre), _vp(g_c_cur), n, H, W, *items, torch.cuda.current_stream(pre.device).cuda_stream)
+    return g_pre, g_c_cur
 
 
 def conv_first(x_nchw: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor):

@@ -39,6 +39,12 @@ trunks through the modules below.
   block kernels on a zero-padded 256-channel map (weights packed by stif_pack_conv_block_dev).  The deformable conv
   itself stays in NHWC: stif_dcn_offmask_nhwc, the fused forward stif_dcn_nhwc (fp32) and its backward
   stif_dcn_bwd_nhwc, which writes the offset / mask conv's output gradient in place of any torch assembly.
+* ``Conv1x1Cat``, ``ConvLSTMCell``, ``Easy_PCD``, ``DeformableConvLSTM``, ``BiDeformableConvLSTM``, ``GenFeat`` -- the
+  rest of LunaTokis.gen_feat (Sakuya_arch_test.py:132-266, :313-362): the 1x1 (64 | 64) -> 64 convs (forward
+  stif_conv2d_nhwc on the device pack of stif_pack_conv1x1_dev, backward stif_conv1x1_wgrad and fp32 1x1 data-gradient
+  convs), the ConvLSTM cell as one node (the 128 -> 256 Winograd conv writes the pre-activations, stif_lstm_gates_nhwc
+  the state; the backward recomputes the gates from them), and the compositions up to ``GenFeat``, which takes an
+  optimiser step on everything before the SIREN decoder.
 """
 from __future__ import annotations
 
@@ -692,7 +698,9 @@ class PCD_Align(nn.Module):
         L1_off = m("L1_offset_conv3")(m("L1_offset_conv2")(L1_off, self.up_offset(L2_off)))
         return m("L1_fea_conv")(m("L1_dcnpack")(fa[0], L1_off), self.up_fea(L2_fea))
 
-    def forward(self, fea1, fea2):
+    def branches(self, fea1, fea2):
+        """The two 64-channel halves of ``forward``'s result (the inputs checked as there): what a consumer that takes
+        its two inputs apart (``Conv1x1Cat``) reads without the concatenation."""
         fea1, fea2 = list(fea1), list(fea2)
         if len(fea1) != 3 or len(fea2) != 3:
             raise ValueError("PCD_Align: fea1 and fea2 are lists [L1, L2, L3]")
@@ -710,7 +718,294 @@ class PCD_Align(nn.Module):
             if not t.is_cuda:
                 raise RuntimeError(f"PCD_Align: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
                                    "(move the module and its input to the GPU)")
-        return torch.cat([self._branch("_1", fea1, fea2), self._branch("_2", fea2, fea1)], dim=1)
+        return self._branch("_1", fea1, fea2), self._branch("_2", fea2, fea1)
+
+    def forward(self, fea1, fea2):
+        return torch.cat(self.branches(fea1, fea2), dim=1)
 
     def range_status(self) -> int:
         return range_status(self.L3_dcnpack_1.weight.device)
+
+
+# ---- Easy_PCD, the ConvLSTM cell, BiDeformableConvLSTM, gen_feat (Sakuya_arch_test.py:132-266, :313-362) ----
+
+_PACK1 = {"f16x3": L.PACK_PLAIN | L.PACK_F16X3, "f32": L.PACK_PLAIN}   # the 1x1 layers' packings
+
+
+class _Conv1x1CatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, weight, bias, mode):
+        ah, bh = _nhwc(a, "Conv1x1Cat"), _nhwc(b, "Conv1x1Cat")
+        if ah.shape != bh.shape:
+            raise RuntimeError(f"Conv1x1Cat: the two inputs differ in shape, {tuple(a.shape)} and {tuple(b.shape)}")
+        status = _status_word(ah.device)
+        lay = ops.pack_conv1x1_dev(weight, bias, mode, status=status)
+        out = torch.empty(ah.shape, dtype=torch.float32, device=ah.device)
+        ops.conv2d([dict(layer=lay, in0=ah, in1=bh, out=out)], in1_mode=1, status=status)
+        ctx.save_for_backward(ah, bh, weight)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ah, bh, weight = ctx.saved_tensors
+        g = _nhwc(grad_out, "Conv1x1Cat backward")
+        need_a, need_b, need_w, need_bias = ctx.needs_input_grad[:4]
+        gw = gb = None
+        if need_w or need_bias:
+            gw, gb = ops.conv1x1_wgrad([ah, bh], g)
+        gin = [None, None]
+        for half, need in enumerate((need_a, need_b)):
+            if need:   # fp32 in both modes: the split-fp16 1x1 kernel takes the (64 | 64) and 200-channel inputs only
+                lay = ops.pack_conv1x1_dev(weight, None, L.PACK_PLAIN, dgrad=True, half=half)
+                gx = torch.empty(g.shape, dtype=torch.float32, device=g.device)
+                ops.conv2d([dict(layer=lay, in0=g, out=gx)])
+                gin[half] = gx.permute(0, 3, 1, 2)
+        return gin[0], gin[1], gw if need_w else None, gb if need_bias else None, None
+
+
+class Conv1x1Cat(nn.Module):
+    """nn.Conv2d(128, 64, 1) applied to torch.cat([a, b], 1) without the concatenation (``fusion``,
+    ``Easy_PCD.fusion``, ``ConvBLSTM.conv_1x1``): the forward is stif_conv2d_nhwc with two inputs on the weight packed
+    by stif_pack_conv1x1_dev, the backward stif_conv1x1_wgrad and one fp32 1x1 64 -> 64 conv per input that needs a
+    gradient.  ``weight`` [64, 128, 1, 1] and ``bias`` [64] as nn.Conv2d's (names, shapes, default initialisation)."""
+
+    def __init__(self, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, None, mfma)
+        self.mfma = mfma
+        self.weight = nn.Parameter(torch.empty(64, 128, 1, 1))
+        self.bias = nn.Parameter(torch.empty(64))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(128)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, a, b):
+        return _Conv1x1CatFn.apply(a, b, self.weight, self.bias, _PACK1[self.mfma])
+
+    def range_status(self) -> int:
+        return range_status(self.weight.device)
+
+    def extra_repr(self):
+        return f"128, 64, kernel_size=(1, 1), mfma={self.mfma}"
+
+
+class _ConvLSTMCellFn(torch.autograd.Function):
+    """The whole cell as one node: the two-input Winograd conv writes the 256 pre-activations in the reference's row
+    order, stif_lstm_gates_nhwc the new state.  Saved: the three inputs and the pre-activations; the backward
+    recomputes the gates (stif_lstm_gates_bwd_nhwc)."""
+
+    @staticmethod
+    def forward(ctx, x, h, c, weight, bias, mode):
+        xh, hh, ch = (_nhwc(t, "ConvLSTMCell") for t in (x, h, c))
+        if xh.shape != hh.shape or xh.shape != ch.shape:
+            raise RuntimeError(f"ConvLSTMCell: input {tuple(x.shape)}, h {tuple(h.shape)} and c {tuple(c.shape)} "
+                               "differ in shape")
+        status = _status_word(xh.device)
+        n, H, W, _ = xh.shape
+        pre = torch.empty(n, H, W, 256, dtype=torch.float32, device=xh.device)
+        ops.conv2d([dict(layer=ops.pack_conv_blocks_dev(weight, bias, mode, status=status), in0=xh, in1=hh, out=pre)],
+                   in1_mode=1, status=status)
+        h_next, c_next = ops.lstm_gates(pre, ch)
+        ctx.mode = mode
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xh, hh, ch, pre, weight)
+        return h_next.permute(0, 3, 1, 2), c_next.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g_h, g_c):
+        xh, hh, ch, pre, weight = ctx.saved_tensors
+        if g_h is None and g_c is None:
+            return (None,) * 6
+        g_h = None if g_h is None else _nhwc(g_h, "ConvLSTMCell backward")
+        g_c = None if g_c is None else _nhwc(g_c, "ConvLSTMCell backward")
+        need_x, need_h, need_c, need_w, need_b = ctx.needs_input_grad[:5]
+        g_pre, g_cc = ops.lstm_gates_bwd(pre, ch, g_h, g_c, need_c=need_c)
+        gw = gb = None
+        if need_w or need_b:
+            gw, gb = ops.conv3x3_wgrad_cat([xh, hh], g_pre, 256)
+        gin = [None, None]
+        status = _status_word(pre.device)
+        for half, need in enumerate((need_x, need_h)):
+            if need:
+                lay = ops.pack_conv_blocks_dev(weight, None, ctx.mode, dgrad=True, half=half, status=status)
+                gx = torch.empty(xh.shape, dtype=torch.float32, device=pre.device)
+                ops.conv2d([dict(layer=lay, in0=g_pre, out=gx)], status=status)
+                gin[half] = gx.permute(0, 3, 1, 2)
+        return (gin[0], gin[1], g_cc.permute(0, 3, 1, 2) if need_c else None, gw if need_w else None,
+                gb if need_b else None, None)
+
+
+class _Conv2dParams(nn.Module):
+    """``weight`` / ``bias`` of an nn.Conv2d(cin, cout, 3) with its default initialisation, no forward of its own."""
+
+    def __init__(self, cout, cin):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
+        self.bias = nn.Parameter(torch.empty(cout))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(cin * 9)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+
+class ConvLSTMCell(nn.Module):
+    """convlstm.py:8-58 for 64 input and 64 hidden channels, 3x3: ``forward(x, (h, c)) -> (h_next, c_next)`` with
+    ``conv.weight`` [256, 128, 3, 3] / ``conv.bias`` [256] under the reference's names (rows: gates i, f, o, g of 64
+    hidden channels each).  One autograd node: forward stif_conv3x3_wino on (x | h) and stif_lstm_gates_nhwc; backward
+    stif_lstm_gates_bwd_nhwc, stif_conv3x3_wgrad_cat in eight 64 x 64 blocks and one 256 -> 64 Winograd data-gradient
+    conv per input that needs one."""
+
+    def __init__(self, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, None, mfma)
+        self.mfma = mfma
+        self.conv = _Conv2dParams(256, 128)
+
+    def forward(self, x, state):
+        h, c = state
+        return _ConvLSTMCellFn.apply(x, h, c, self.conv.weight, self.conv.bias, _PACK[self.mfma])
+
+    def range_status(self) -> int:
+        return range_status(self.conv.weight.device)
+
+
+def _check_maps(who, maps, what="[B, 64, H, W]"):
+    """CPU tensors, wrong shapes and sizes that the three pyramid levels cannot halve are refused before any launch."""
+    first = maps[0]
+    for t in maps:
+        if t.dim() != 4 or t.shape[1] != 64 or t.shape != first.shape:
+            raise ValueError(f"{who}: expected {what} maps of one shape, got {[tuple(m.shape) for m in maps]}")
+    if first.shape[2] % 4 or first.shape[3] % 4:
+        raise ValueError(f"{who}: H and W must be multiples of 4 (three pyramid levels), got "
+                         f"{first.shape[2]} x {first.shape[3]}")
+    for t in maps:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
+                               "(move the module and its input to the GPU)")
+
+
+class Easy_PCD(nn.Module):
+    """Sakuya_arch_test.py:132-166 with the reference's submodule names and registration order: the two-level pyramid
+    of both inputs (one pass over the 2B stacked items), ``pcd_align`` and the 1x1 ``fusion`` on its two halves.
+    ``forward(f1, f2)``: [B, 64, H, W] each -> [B, 64, H, W], H and W multiples of 4."""
+
+    def __init__(self, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, None, mfma)
+        self.fea_L2_conv1 = ConvDown(64, "lrelu")
+        self.fea_L2_conv2 = Conv3x3(64, "lrelu", mfma)
+        self.fea_L3_conv1 = ConvDown(64, "lrelu")
+        self.fea_L3_conv2 = Conv3x3(64, "lrelu", mfma)
+        self.pcd_align = PCD_Align(mfma)
+        self.fusion = Conv1x1Cat(mfma)
+
+    def forward(self, f1, f2):
+        _check_maps("Easy_PCD", [f1, f2])
+        B = f1.shape[0]
+        L1 = torch.cat([f1, f2], dim=0)     # the reference stacks on dim 1; the convs are per item
+        L2 = self.fea_L2_conv2(self.fea_L2_conv1(L1))
+        L3 = self.fea_L3_conv2(self.fea_L3_conv1(L2))
+        a, b = self.pcd_align.branches([f1, L2[:B], L3[:B]], [f2, L2[B:], L3[B:]])
+        return self.fusion(a, b)
+
+    def range_status(self) -> int:
+        return range_status(self.fusion.weight.device)
+
+
+class DeformableConvLSTM(nn.Module):
+    """Sakuya_arch_test.py:168-245 for one layer of 64 channels with the reference's submodule names and registration
+    order (``cell_list.0``, ``pcd_h``, ``pcd_c``): ``forward(x)``, x [B, T, 64, H, W] -> the hidden states
+    [B, T, 64, H, W], from a zero initial state on x's device."""
+
+    def __init__(self, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, None, mfma)
+        self.cell_list = nn.ModuleList([ConvLSTMCell(mfma)])
+        self.pcd_h = Easy_PCD(mfma)
+        self.pcd_c = Easy_PCD(mfma)
+
+    def forward(self, x):
+        if x.dim() != 5:
+            raise ValueError(f"DeformableConvLSTM: expected [B, T, 64, H, W], got {tuple(x.shape)}")
+        _check_maps("DeformableConvLSTM", [x[:, 0]], "[B, T, 64, H, W]")
+        h = c = torch.zeros_like(x[:, 0])
+        outs = []
+        for t in range(x.shape[1]):
+            xt = x[:, t]
+            h, c = self.cell_list[0](xt, (self.pcd_h(xt, h), self.pcd_c(xt, c)))
+            outs.append(h)
+        return torch.stack(outs, dim=1)
+
+
+class BiDeformableConvLSTM(nn.Module):
+    """Sakuya_arch_test.py:247-266: ``forward_net`` over the sequence and over its reverse (the same weights),
+    ``conv_1x1`` on (out_fwd[t] | out_rev[T - 1 - t]).  [B, T, 64, H, W] -> [B, T, 64, H, W], H and W multiples of 4;
+    the ``ConvBLSTM.*`` slice of a LunaTokis state dict loads with ``strict=True``."""
+
+    def __init__(self, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, None, mfma)
+        self.forward_net = DeformableConvLSTM(mfma)
+        self.conv_1x1 = Conv1x1Cat(mfma)
+
+    def forward(self, x):
+        if x.dim() != 5:
+            raise ValueError(f"BiDeformableConvLSTM: expected [B, T, 64, H, W], got {tuple(x.shape)}")
+        _check_maps("BiDeformableConvLSTM", [x[:, 0]], "[B, T, 64, H, W]")
+        B, T, C, H, W = x.shape
+        fwd = self.forward_net(x)
+        rev = self.forward_net(x.flip(1)).flip(1)
+        out = self.conv_1x1(fwd.reshape(B * T, C, H, W), rev.reshape(B * T, C, H, W))
+        return out.reshape(B, T, C, H, W)
+
+    def range_status(self) -> int:
+        return range_status(self.conv_1x1.weight.device)
+
+
+_NOT_GEN_FEAT = ("feat_imnet.", "flow_imnet.", "encode_imnet.", "upconv1.", "upconv2.", "HRconv.", "conv_last.")
+
+
+def gen_feat_state_dict(sd) -> dict:
+    """The slice of a LunaTokis state dict that ``GenFeat`` loads with ``strict=True``: everything but the decoder
+    and the unused upsampling layers; numpy arrays become tensors."""
+    return {k: torch.as_tensor(v) for k, v in sd.items() if not k.startswith(_NOT_GEN_FEAT)}
+
+
+class GenFeat(nn.Module):
+    """LunaTokis.gen_feat (Sakuya_arch_test.py:313-362), everything before the decoder, trainable on the engine with
+    the parameters under the reference's top-level names: frames [B, N, 3, H, W] -> features [B, 2N - 1, 64, H, W],
+    H and W multiples of 4.  ``gen_feat_state_dict(sd)`` loads with ``strict=True``."""
+
+    def __init__(self, front_RBs: int = 5, back_RBs: int = 40, mfma: str = "f16x3"):
+        super().__init__()
+        _check_choice(64, None, mfma)
+        self.conv_first = ConvFirst()
+        self.feature_extraction = make_trunk(front_RBs, 64, mfma)
+        self.fea_L2_conv1 = ConvDown(64, "lrelu")
+        self.fea_L2_conv2 = Conv3x3(64, "lrelu", mfma)
+        self.fea_L3_conv1 = ConvDown(64, "lrelu")
+        self.fea_L3_conv2 = Conv3x3(64, "lrelu", mfma)
+        self.pcd_align = PCD_Align(mfma)
+        self.fusion = Conv1x1Cat(mfma)
+        self.ConvBLSTM = BiDeformableConvLSTM(mfma)
+        self.recon_trunk = make_trunk(back_RBs, 64, mfma)
+
+    def forward(self, x):
+        if x.dim() != 5 or x.shape[2] != 3 or x.shape[1] < 2:
+            raise ValueError(f"GenFeat: expected frames [B, N >= 2, 3, H, W], got {tuple(x.shape)}")
+        B, N, _, H, W = x.shape
+        if H % 4 or W % 4:
+            raise ValueError(f"GenFeat: H and W must be multiples of 4 (three pyramid levels), got {H} x {W}")
+        L1 = self.feature_extraction(self.conv_first(x.reshape(B * N, 3, H, W)))
+        L2 = self.fea_L2_conv2(self.fea_L2_conv1(L1))
+        L3 = self.fea_L3_conv2(self.fea_L3_conv1(L2))
+        lv = [t.reshape(B, N, 64, t.shape[2], t.shape[3]) for t in (L1, L2, L3)]
+        seq = [lv[0][:, 0]]
+        for i in range(N - 1):
+            a, b = self.pcd_align.branches([t[:, i] for t in lv], [t[:, i + 1] for t in lv])
+            seq += [self.fusion(a, b), lv[0][:, i + 1]]
+        feats = self.ConvBLSTM(torch.stack(seq, dim=1))
+        T = feats.shape[1]
+        return self.recon_trunk(feats.reshape(B * T, 64, H, W)).reshape(B, T, 64, H, W)
+
+    def range_status(self) -> int:
+        return range_status(self.conv_first.weight.device)
