@@ -248,6 +248,94 @@ int stif_upsample2x_bwd_nhwc(const float* gy, float* gx, int n, int h1, int w1, 
 int stif_upsample2x_nhwc(const float* in, float* out, int n, int h1, int w1, int c, float scale,
                          long long in_item, long long out_item, void* stream);
 
+/* ---- the SIREN decoder for training ----
+ *
+ * The three MLPs (feat_imnet, flow_imnet, encode_imnet; SIREN.py:74-79) run on input matrices in HBM, row-major fp32,
+ * one row per HR pixel: x [n][x_stride], of which the first cin columns are the inputs (201, 263 or 525) and columns
+ * cin .. round8(cin) - 1 are zeros; x_stride is a multiple of 8, at least round8(cin) (columns past round8(cin) are
+ * never read).  nsine sine layers of widths width[0 .. nsine) -- (64, 64, 256) or (64, 64, 256, 256), width[3] = 0 with
+ * three -- each sin(30 (a W^T + b)), then a linear layer to cout in {64, 4, 3}.  w[l] / b[l]: the parameter tensors,
+ * row-major [cout_l][cin_l] and [cout_l] (the last at index nsine).  fp32 MFMA, exact fp32 products.
+ *
+ * stif_siren_fwd writes y [n][cout] and z [n][zw], zw = 384 or 640: the pre-activations z_l = a_{l-1} W_l^T + b_l of
+ * the sine layers side by side (layer l at column width[0] + .. + width[l - 1]).  No activation is stored.
+ *
+ * stif_siren_bwd takes g_y [n][cout], x and the z of the forward, and writes g_w[l] / g_b[l] (the shapes of w / b) of
+ * every layer and, unless g_x is NULL, g_x [n][gx_stride] (gx_stride as x_stride): columns < cin the input gradient,
+ * cin .. round8(cin) - 1 zeros.  sin and cos are recomputed from z.  The weight and bias gradients use no atomics:
+ * per layer, workgroups write partial sums of 64 x 64 blocks into the workspace and a second launch adds them in an
+ * order fixed by their number, stif_siren_wgrad_grid(n, cout_l, cin_l) per block -- a function of n, the layer's shape
+ * and the CU count (0 for sizes out of range).  Repeated calls give identical bits whatever the workspace held.
+ * workspace: stif_siren_bwd_workspace_size(n, nsine) bytes (0 for n < 1 or nsine outside {3, 4}), 16-B aligned; it
+ * holds the g_z of every sine layer (n zw floats) and the partials.
+ *
+ * STIF_E_INVALID, each with its reason, before any launch: null args, a null x / z / y / w[l] / b[l] (backward: g_y,
+ * g_w[l], g_b[l], workspace), n < 1, nsine or widths other than the two lists, cout outside {64, 4, 3}, cin outside
+ * [1, STIF_SIREN_MAX_CIN], a stride that is not a multiple of 8 or smaller than round8(cin), x / z / g_x / workspace
+ * not 16-B aligned, a workspace that is too small.  Zero-initialise the struct, then fill. */
+#define STIF_SIREN_ROW_TILE 64   /* rows per workgroup of the MLP kernels */
+#define STIF_SIREN_MAX_CIN 528
+typedef struct {
+  const float* x;
+  long long x_stride;
+  int n, cin, nsine, cout;
+  int width[4];
+  const float* w[5];
+  const float* b[5];
+  float* y;                /* forward: [n][cout] */
+  float* z;                /* [n][zw]: written by the forward, read by the backward */
+  const float* g_y;        /* backward: [n][cout] */
+  float* g_x;              /* backward: [n][gx_stride] or NULL */
+  long long gx_stride;
+  float* g_w[5];
+  float* g_b[5];
+  void* workspace;
+  size_t workspace_bytes;
+} stif_siren_args;
+int stif_siren_fwd(const stif_siren_args* args, void* stream);
+size_t stif_siren_bwd_workspace_size(int n, int nsine);
+int stif_siren_wgrad_grid(int n, int cout, int cin);
+int stif_siren_bwd(const stif_siren_args* args, void* stream);
+
+/* The builders of the three MLP input matrices and their adjoints (Sakuya_arch_test.py:364-459 without the local
+ * ensemble; N = B HH WW rows, pixel (b, qy, qx) at row (b HH + qy) WW + qx):
+ *   X1 [N][208]: latent at the nearest LR pixel 192 | frames there 6 | rel_y, rel_x | t | 7 zeros;
+ *   X2 [N][264]: HRfeat 64 | bilinear latent 192 | bilinear frames 6 | t | 1 zero  (the fixed query grid);
+ *   X3 [N][528]: HRfeat@grid1 64 | HRfeat@grid2 64 | latent@grid1 192 | latent@grid2 192 | frames@grid1 6 |
+ *                frames@grid2 6 | t | 3 zeros, the grids torch.linspace + flow / ((n - 1) / 2) clamped to
+ *                +-(1 - 1e-6), flow [N][4] = (x1, y1, x2, y2) in HR pixels; bilinear with zero padding.
+ * feat [B][H][W][192] is the NHWC latent, frames [B][6][H][W] the planar LR frame pair, t [B] a time per item,
+ * hrfeat [N][64].  The per-row / per-column tables are the host's (coords.dec_tables: HH / WW entries), the *_first
+ * tables their inverses for the gather-form adjoints (H + 1 / W + 1 entries: the first HR index whose table entry is
+ * >= i; every table is monotone).
+ * Adjoints: x1_bwd writes g_feat [B][H][W][192], each element the sum of the g_X1 rows of the HR rectangle whose
+ * nearest pixel it is; x2_bwd writes g_hrfeat [N][64] = g_X2[:, :64] and g_feat, the adjoint of the fixed bilinear
+ * gather (both gather form, one lane per element in a fixed order: identical bits for repeated calls).  x3_bwd
+ * writes g_flow [N][4] with plain stores (the coordinate gradient of all six samples; exactly zero where the clamp is
+ * active) and ADDS into g_hrfeat [N][64] and g_feat, which the caller zeroes, with fp32 atomics on whole channel rows:
+ * the only order-dependent sums of the decoder backward.  No gradient goes to frames or t.
+ * STIF_E_INVALID before any launch: null geometry, a null pointer in it or among the arguments, B / H / W < 1,
+ * HH / WW < 2 (the warp grid divides by n - 1), more than 2^31 - 1 float4 of any matrix. */
+typedef struct {
+  int B, H, W, HH, WW;
+  const float* feat;
+  const float* frames;
+  const float* t;
+  const int *near_y, *near_x;
+  const float *rel_y, *rel_x;
+  const int *by0, *by1, *bx0, *bx1;
+  const float *wy0, *wy1, *wx0, *wx1;
+  const float *lin_y, *lin_x;
+  const int *near_y_first, *near_x_first, *by0_first, *by1_first, *bx0_first, *bx1_first;
+} stif_dec_train_geom;
+int stif_dec_x1_fwd(const stif_dec_train_geom* g, float* x1, void* stream);
+int stif_dec_x1_bwd(const stif_dec_train_geom* g, const float* g_x1, float* g_feat, void* stream);
+int stif_dec_x2_fwd(const stif_dec_train_geom* g, const float* hrfeat, float* x2, void* stream);
+int stif_dec_x2_bwd(const stif_dec_train_geom* g, const float* g_x2, float* g_hrfeat, float* g_feat, void* stream);
+int stif_dec_x3_fwd(const stif_dec_train_geom* g, const float* hrfeat, const float* flow, float* x3, void* stream);
+int stif_dec_x3_bwd(const stif_dec_train_geom* g, const float* hrfeat, const float* flow, const float* g_x3,
+                    float* g_flow, float* g_hrfeat, float* g_feat, void* stream);
+
 /* conv_first (3 -> 64, 3x3) + LeakyReLU, reading NCHW RGB frames [n,3,h,w]
  * (Sakuya_arch_test.py:318) and writing NHWC [n,h,w,64]. w: [64,3,3,3] as in the state dict. */
 int stif_conv_first(const float* x_nchw, const float* w, const float* b, float* out,

@@ -125,6 +125,30 @@ class DecPointList(C.Structure):
                 ("t_item", C.c_longlong), ("t_point", C.c_longlong), ("npts", C.c_int)]
 
 
+SIREN_ROW_TILE = 64      # stif.h STIF_SIREN_ROW_TILE: rows per workgroup of the SIREN training kernels
+
+
+class SirenArgs(C.Structure):
+    """stif_siren_args: one SIREN MLP on a row-major input matrix, forward-for-training and backward."""
+    _fields_ = [
+        ("x", _P), ("x_stride", C.c_longlong),
+        ("n", C.c_int), ("cin", C.c_int), ("nsine", C.c_int), ("cout", C.c_int), ("width", C.c_int * 4),
+        ("w", _P * 5), ("b", _P * 5), ("y", _P), ("z", _P), ("g_y", _P), ("g_x", _P), ("gx_stride", C.c_longlong),
+        ("g_w", _P * 5), ("g_b", _P * 5), ("workspace", _P), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+DEC_TRAIN_TABLES = ("near_y", "near_x", "rel_y", "rel_x", "by0", "by1", "bx0", "bx1", "wy0", "wy1", "wx0", "wx1",
+                    "lin_y", "lin_x", "near_y_first", "near_x_first", "by0_first", "by1_first", "bx0_first",
+                    "bx1_first")
+
+
+class DecTrainGeom(C.Structure):
+    """stif_dec_train_geom: sizes, the LR maps and the per-axis tables of the decoder's input builders."""
+    _fields_ = [(n, C.c_int) for n in ("B", "H", "W", "HH", "WW")] + [
+        (n, _P) for n in ("feat", "frames", "t") + DEC_TRAIN_TABLES]
+
+
 METRIC_Y, METRIC_SSIM, METRIC_FLOAT = 1, 2, 4  # stif_metric_args.flags (stif.h STIF_METRIC_*)
 FSSIM_VOLUME, FSSIM_PLANAR = 0, 1               # stif_metric_float's mode (stif.h STIF_FSSIM_*)
 
@@ -184,6 +208,16 @@ EXPORTS = {
     "stif_lstm_gates_bwd_nhwc": (C.c_int, [_P] * 6 + [C.c_int] * 3 + [C.c_longlong] * 6 + [_P]),
     "stif_upsample2x_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong,
                                        C.c_longlong, _P]),
+    "stif_siren_fwd": (C.c_int, [C.POINTER(SirenArgs), _P]),
+    "stif_siren_bwd_workspace_size": (C.c_size_t, [C.c_int] * 2),
+    "stif_siren_wgrad_grid": (C.c_int, [C.c_int] * 3),
+    "stif_siren_bwd": (C.c_int, [C.POINTER(SirenArgs), _P]),
+    "stif_dec_x1_fwd": (C.c_int, [C.POINTER(DecTrainGeom), _P, _P]),
+    "stif_dec_x1_bwd": (C.c_int, [C.POINTER(DecTrainGeom), _P, _P, _P]),
+    "stif_dec_x2_fwd": (C.c_int, [C.POINTER(DecTrainGeom), _P, _P, _P]),
+    "stif_dec_x2_bwd": (C.c_int, [C.POINTER(DecTrainGeom), _P, _P, _P, _P]),
+    "stif_dec_x3_fwd": (C.c_int, [C.POINTER(DecTrainGeom), _P, _P, _P, _P]),
+    "stif_dec_x3_bwd": (C.c_int, [C.POINTER(DecTrainGeom)] + [_P] * 7),
     "stif_conv_first": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "stif_dcn_nhwc": (C.c_int, [C.POINTER(DcnArgs), _P]),
     "stif_dcn_sep_nhwc": (C.c_int, [C.POINTER(DcnSepArgs), _P]),

@@ -84,6 +84,32 @@ def dec_tables(h: int, w: int, HH: int, WW: int, shift=None, shift_grid=None) ->
     return out
 
 
+def first_index(table: np.ndarray, n: int) -> np.ndarray:
+    """The inverse of a monotone index table for the gather-form adjoints of the training decoder: n + 1 entries,
+    entry i the first position whose table value is >= i, so the positions that hold i are
+    [first[i], first[i + 1])."""
+    table = np.asarray(table)
+    if table.size > 1 and (np.diff(table) < 0).any():
+        raise ValueError("first_index: the table is not monotone")
+    return np.searchsorted(table, np.arange(n + 1), side="left").astype(np.int32)
+
+
+def dec_train_tables(h: int, w: int, HH: int, WW: int) -> dict:
+    """The tables of a training decode under the field names of stif.h's stif_dec_train_geom: ``dec_tables`` without
+    a shift (near_y, rel_y, by0, by1, wy0, wy1, lin_y and the same along x) plus the inverse tables of the nearest
+    index and of the two bilinear corner indices per axis (near_y_first, by0_first, by1_first, ...)."""
+    t = dec_tables(h, w, HH, WW)
+    out = {}
+    for ax, n in (("y", h), ("x", w)):
+        for k in ("near", "rel", "lin"):
+            out[f"{k}_{ax}"] = t[f"{k}_{ax}"]
+        for k in ("b0", "b1", "w0", "w1"):
+            out[f"{k[0]}{ax}{k[1]}"] = t[f"{k}_{ax}"]
+        for name in (f"near_{ax}", f"b{ax}0", f"b{ax}1"):
+            out[name + "_first"] = first_index(out[name], n)
+    return out
+
+
 TABLE_ORDER = ["near_y", "rel_y", "b0_y", "b1_y", "w0_y", "w1_y", "lin_y",
                "near_x", "rel_x", "b0_x", "b1_x", "w0_x", "w1_x", "lin_x"]
 

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .coords import TABLE_ORDER, check_window, dec_tables
+from .coords import TABLE_ORDER, check_window, dec_tables, dec_train_tables
 
 # Optional launch tracer (bench.py sets it to time the dominant kernel with HIP events on
 # the launch stream): an object with begin(kind: tuple, flops: float) and end().
@@ -586,6 +586,236 @@ def lstm_gates_bwd(pre: torch.Tensor, c_cur: torch.Tensor, g_h: Optional[torch.T
     _launch("stif_lstm_gates_bwd_nhwc", trace, L.lib().stif_lstm_gates_bwd_nhwc, _vp(pre), _vp(c_cur), _vp(g_h),
             _vp(g_c_next), _vp(g_pre), _vp(g_c_cur), n, H, W, *items, torch.cuda.current_stream(pre.device).cuda_stream)
     return g_pre, g_c_cur
+
+
+# ----------------------------------------------------------------------------- the SIREN decoder for training
+SIREN_WIDTHS = {3: (64, 64, 256), 4: (64, 64, 256, 256)}
+
+
+def _round8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+def _siren_args(what, x, weights, biases):
+    """The checks every SIREN call shares, before any launch; returns (args with x / w / b filled, n, kp, zw, cout)."""
+    weights, biases = list(weights), list(biases)
+    nsine = len(weights) - 1
+    if nsine not in SIREN_WIDTHS or len(biases) != len(weights):
+        raise ValueError(f"{what}: 4 or 5 weight / bias pairs (3 or 4 sine layers and the linear one), got "
+                         f"{len(weights)} and {len(biases)}")
+    for t in [x] + weights + biases:
+        if not t.is_cuda:
+            raise RuntimeError(f"{what}: the HIP kernels need CUDA tensors, got one on {t.device} "
+                               "(move the module and its input to the GPU)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: expected float32 tensors, got {t.dtype}")
+    cin, cout = int(weights[0].shape[1]), int(weights[-1].shape[0])
+    dims = [cin] + list(SIREN_WIDTHS[nsine]) + [cout]
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        if tuple(w.shape) != (dims[l + 1], dims[l]) or tuple(b.shape) != (dims[l + 1],) or not w.is_contiguous():
+            raise ValueError(f"{what}: layer {l} must be a contiguous [{dims[l + 1]}, {dims[l]}] weight with its bias "
+                             f"(widths {SIREN_WIDTHS[nsine]}), got {tuple(w.shape)} and {tuple(b.shape)}")
+    kp = _round8(cin)
+    if x.dim() != 2 or x.shape[1] != kp or x.shape[0] < 1 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError(f"{what}: x must be [n >= 1, {kp}] ({cin} inputs and zero pad columns) with contiguous rows, "
+                         f"got {tuple(x.shape)}")
+    a = L.SirenArgs()
+    a.x, a.x_stride = _vp(x), x.stride(0)
+    a.n, a.cin, a.nsine, a.cout = x.shape[0], cin, nsine, cout
+    for l, wd in enumerate(SIREN_WIDTHS[nsine]):
+        a.width[l] = wd
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        a.w[l], a.b[l] = _vp(w), _vp(b)
+    return a, x.shape[0], kp, sum(SIREN_WIDTHS[nsine]), cout
+
+
+def siren_fwd(x: torch.Tensor, weights, biases, y: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None):
+    """A SIREN MLP on the rows of ``x`` for training (stif_siren_fwd): ``x`` [n, round8(cin)] fp32 with zero pad
+    columns (rows may be strided by a multiple of 8), ``weights`` / ``biases`` the parameter tensors of the 3 or 4
+    sine layers and the final linear layer.  Returns (y [n, cout], z [n, 384 or 640]): the output and the saved
+    pre-activations of the sine layers."""
+    a, n, _, zw, cout = _siren_args("siren_fwd", x, weights, biases)
+    if y is None:
+        y = torch.empty(n, cout, dtype=torch.float32, device=x.device)
+    if z is None:
+        z = torch.empty(n, zw, dtype=torch.float32, device=x.device)
+    if tuple(y.shape) != (n, cout) or tuple(z.shape) != (n, zw) or not y.is_contiguous() or not z.is_contiguous():
+        raise ValueError(f"siren_fwd: y must be a contiguous [{n}, {cout}] and z [{n}, {zw}]")
+    a.y, a.z = _vp(y), _vp(z)
+    trace = None
+    if TRACE is not None:
+        macs = sum(int(w.numel()) for w in weights)
+        trace = (("siren_fwd", a.cin, cout), 2.0 * macs * n, 4.0 * n * (x.shape[1] + 2 * zw + cout))
+    _launch("stif_siren_fwd", trace, L.lib().stif_siren_fwd, C.byref(a), torch.cuda.current_stream(x.device).cuda_stream)
+    return y, z
+
+
+def siren_bwd(x: torch.Tensor, z: torch.Tensor, weights, biases, g_y: torch.Tensor, need_x: bool = True,
+              g_x: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, g_params=None):
+    """The backward of siren_fwd (stif_siren_bwd) from ``g_y`` [n, cout], ``x`` and the saved ``z``: returns
+    (g_x [n, round8(cin)] with zero pad columns, or None without ``need_x``; the weight gradients; the bias
+    gradients).  The weight and bias gradients are deterministic (no atomics, whatever ``workspace`` held).
+    ``g_params``: (weight gradients, bias gradients) to write into, contiguous and shaped as the parameters."""
+    a, n, kp, zw, cout = _siren_args("siren_bwd", x, weights, biases)
+    for name, t, shape in (("z", z, (n, zw)), ("g_y", g_y, (n, cout))):
+        if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"siren_bwd: {name} must be a contiguous float32 CUDA [{shape[0]}, {shape[1]}]")
+    lib = L.lib()
+    a.z, a.g_y = _vp(z), _vp(g_y)
+    if need_x:
+        if g_x is None:
+            g_x = torch.empty(n, kp, dtype=torch.float32, device=x.device)
+        if g_x.dim() != 2 or tuple(g_x.shape) != (n, kp) or g_x.stride(1) != 1:
+            raise ValueError(f"siren_bwd: g_x must be [{n}, {kp}] with contiguous rows")
+        a.g_x, a.gx_stride = _vp(g_x), g_x.stride(0)
+    else:
+        g_x = None
+    if g_params is None:
+        g_ws, g_bs = [torch.empty_like(w) for w in weights], [torch.empty_like(b) for b in biases]
+    else:
+        g_ws, g_bs = list(g_params[0]), list(g_params[1])
+        for g, p in zip(g_ws + g_bs, list(weights) + list(biases)):
+            if not g.is_cuda or g.dtype != torch.float32 or g.shape != p.shape or not g.is_contiguous():
+                raise ValueError("siren_bwd: g_params must be contiguous float32 CUDA tensors shaped as the parameters")
+    for l, (gw, gb) in enumerate(zip(g_ws, g_bs)):
+        a.g_w[l], a.g_b[l] = _vp(gw), _vp(gb)
+    nbytes = lib.stif_siren_bwd_workspace_size(n, a.nsine)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    a.workspace, a.workspace_bytes = _vp(workspace), workspace.numel() * workspace.element_size()
+    trace = None
+    if TRACE is not None:
+        macs = sum(int(w.numel()) for w in weights)
+        trace = (("siren_bwd", a.cin, cout), (4.0 if need_x else 4.0 - 2.0 * weights[0].numel() / macs) * macs * n,
+                 4.0 * n * (x.shape[1] * (2 if need_x else 1) + 4 * zw + cout))
+    _launch("stif_siren_bwd", trace, lib.stif_siren_bwd, C.byref(a), torch.cuda.current_stream(x.device).cuda_stream)
+    return g_x, g_ws, g_bs
+
+
+_DEC_TRAIN_TABLES = {}   # (h, w, HH, WW, device index) -> the uploaded tables of coords.dec_train_tables
+
+
+class DecTrainGeom:
+    """The geometry of one training decode (stif_dec_train_geom) and the tensors it points to: the NHWC latent
+    ``feat`` [B, H, W, 192], the planar frames [B, 6, H, W], a time per item ``t`` [B] and the per-axis tables of
+    the HH x WW query grid (uploaded once per size and device).  Refuses CPU tensors, wrong channel counts and
+    HH or WW < 2 before anything is launched."""
+
+    def __init__(self, feat: torch.Tensor, frames: torch.Tensor, t: torch.Tensor, HH: int, WW: int):
+        HH, WW = int(HH), int(WW)
+        for name, v in (("feat", feat), ("frames", frames), ("t", t)):
+            if not v.is_cuda:
+                raise RuntimeError(f"DecTrainGeom: the HIP kernels need CUDA tensors, got {name} on {v.device} "
+                                   "(move the module and its input to the GPU)")
+            if v.dtype != torch.float32 or not v.is_contiguous():
+                raise ValueError(f"DecTrainGeom: {name} must be a contiguous float32 tensor")
+        if feat.dim() != 4 or feat.shape[3] != 192 or 0 in feat.shape:
+            raise ValueError(f"DecTrainGeom: feat must be the NHWC latent [B, H, W, 192], got {tuple(feat.shape)}")
+        B, H, W, _ = feat.shape
+        if tuple(frames.shape) != (B, 6, H, W):
+            raise ValueError(f"DecTrainGeom: frames must be [{B}, 6, {H}, {W}], got {tuple(frames.shape)}")
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"DecTrainGeom: t must be [{B}], got {tuple(t.shape)}")
+        if HH < 2 or WW < 2:
+            raise ValueError(f"DecTrainGeom: HH and WW must be at least 2 (the warp grid divides by n - 1), got "
+                             f"{HH} x {WW}")
+        key = (H, W, HH, WW, feat.device.index)
+        tabs = _DEC_TRAIN_TABLES.get(key)
+        if tabs is None:
+            host = dec_train_tables(H, W, HH, WW)
+            tabs = _DEC_TRAIN_TABLES[key] = {n: torch.from_numpy(np.ascontiguousarray(host[n])).to(feat.device)
+                                             for n in L.DEC_TRAIN_TABLES}
+        self.feat, self.frames, self.t, self.tables = feat, frames, t, tabs
+        self.B, self.H, self.W, self.HH, self.WW, self.N = B, H, W, HH, WW, B * HH * WW
+        g = self.c = L.DecTrainGeom()
+        g.B, g.H, g.W, g.HH, g.WW = B, H, W, HH, WW
+        g.feat, g.frames, g.t = _vp(feat), _vp(frames), _vp(t)
+        for n in L.DEC_TRAIN_TABLES:
+            setattr(g, n, _vp(tabs[n]))
+
+    def _mat(self, what, t, width, make=torch.empty):
+        if t is None:
+            return make(self.N, width, dtype=torch.float32, device=self.feat.device)
+        if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (self.N, width) or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 CUDA [{self.N}, {width}], got {tuple(t.shape)}")
+        return t
+
+    def _lat(self, what, t):
+        if t is None:
+            return torch.empty_like(self.feat)
+        if not t.is_cuda or t.dtype != torch.float32 or t.shape != self.feat.shape or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 CUDA {tuple(self.feat.shape)}, got {tuple(t.shape)}")
+        return t
+
+    def _run(self, name, trace, *ptrs):
+        _launch(name, trace, getattr(L.lib(), name), C.byref(self.c), *ptrs,
+                torch.cuda.current_stream(self.feat.device).cuda_stream)
+
+
+def dec_x1_fwd(g: DecTrainGeom, x1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """feat_imnet's input matrix X1 [N, 208] (stif_dec_x1_fwd): nearest latent and frames, rel_coord, t, zero pad."""
+    x1 = g._mat("dec_x1_fwd: x1", x1, 208)
+    trace = (("dec_x1_fwd",), 0.0, 4.0 * g.N * (208 + 192)) if TRACE is not None else None
+    g._run("stif_dec_x1_fwd", trace, _vp(x1))
+    return x1
+
+
+def dec_x1_bwd(g: DecTrainGeom, g_x1: torch.Tensor, g_feat: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adjoint of dec_x1_fwd with respect to the latent (stif_dec_x1_bwd), gather form: g_feat [B, H, W, 192]."""
+    g_x1 = g._mat("dec_x1_bwd: g_x1", g_x1, 208)
+    g_feat = g._lat("dec_x1_bwd: g_feat", g_feat)
+    trace = (("dec_x1_bwd",), 0.0, 4.0 * (g.N * 192 + g_feat.numel())) if TRACE is not None else None
+    g._run("stif_dec_x1_bwd", trace, _vp(g_x1), _vp(g_feat))
+    return g_feat
+
+
+def dec_x2_fwd(g: DecTrainGeom, hrfeat: torch.Tensor, x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """flow_imnet's input matrix X2 [N, 264] (stif_dec_x2_fwd): HRfeat, the bilinear latent and frames at the fixed
+    query grid, t, zero pad."""
+    hrfeat = g._mat("dec_x2_fwd: hrfeat", hrfeat, 64)
+    x2 = g._mat("dec_x2_fwd: x2", x2, 264)
+    trace = (("dec_x2_fwd",), 0.0, 4.0 * g.N * (264 + 64 + 192)) if TRACE is not None else None
+    g._run("stif_dec_x2_fwd", trace, _vp(hrfeat), _vp(x2))
+    return x2
+
+
+def dec_x2_bwd(g: DecTrainGeom, g_x2: torch.Tensor, g_hrfeat: Optional[torch.Tensor] = None,
+               g_feat: Optional[torch.Tensor] = None):
+    """The adjoint of dec_x2_fwd (stif_dec_x2_bwd), gather form: (g_hrfeat [N, 64], g_feat [B, H, W, 192])."""
+    g_x2 = g._mat("dec_x2_bwd: g_x2", g_x2, 264)
+    g_hrfeat = g._mat("dec_x2_bwd: g_hrfeat", g_hrfeat, 64)
+    g_feat = g._lat("dec_x2_bwd: g_feat", g_feat)
+    trace = (("dec_x2_bwd",), 0.0, 4.0 * (g.N * (192 + 128) + g_feat.numel())) if TRACE is not None else None
+    g._run("stif_dec_x2_bwd", trace, _vp(g_x2), _vp(g_hrfeat), _vp(g_feat))
+    return g_hrfeat, g_feat
+
+
+def dec_x3_fwd(g: DecTrainGeom, hrfeat: torch.Tensor, flow: torch.Tensor,
+               x3: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """encode_imnet's input matrix X3 [N, 528] (stif_dec_x3_fwd): HRfeat, latent and frames at the two warped grids
+    of ``flow`` [N, 4] (x1, y1, x2, y2 in HR pixels), t, zero pad."""
+    hrfeat = g._mat("dec_x3_fwd: hrfeat", hrfeat, 64)
+    flow = g._mat("dec_x3_fwd: flow", flow, 4)
+    x3 = g._mat("dec_x3_fwd: x3", x3, 528)
+    trace = (("dec_x3_fwd",), 0.0, 4.0 * g.N * (528 + 4 * 524)) if TRACE is not None else None
+    g._run("stif_dec_x3_fwd", trace, _vp(hrfeat), _vp(flow), _vp(x3))
+    return x3
+
+
+def dec_x3_bwd(g: DecTrainGeom, hrfeat: torch.Tensor, flow: torch.Tensor, g_x3: torch.Tensor,
+               g_flow: Optional[torch.Tensor] = None):
+    """The adjoint of dec_x3_fwd (stif_dec_x3_bwd): (g_flow [N, 4], g_hrfeat [N, 64], g_feat [B, H, W, 192]).  g_flow
+    is written with plain stores and is exactly zero where a grid is clamped; g_hrfeat and g_feat are zeroed here and
+    scattered into with fp32 atomics -- the only order-dependent sums of the decoder backward."""
+    hrfeat = g._mat("dec_x3_bwd: hrfeat", hrfeat, 64)
+    flow = g._mat("dec_x3_bwd: flow", flow, 4)
+    g_x3 = g._mat("dec_x3_bwd: g_x3", g_x3, 528)
+    g_flow = g._mat("dec_x3_bwd: g_flow", g_flow, 4)
+    g_hrfeat = g._mat("dec_x3_bwd: g_hrfeat", None, 64, torch.zeros)
+    g_feat = torch.zeros_like(g.feat)
+    trace = (("dec_x3_bwd",), 0.0, 4.0 * g.N * (528 + 3 * 4 * 262)) if TRACE is not None else None
+    g._run("stif_dec_x3_bwd", trace, _vp(hrfeat), _vp(flow), _vp(g_x3), _vp(g_flow), _vp(g_hrfeat), _vp(g_feat))
+    return g_flow, g_hrfeat, g_feat
 
 
 def conv_first(x_nchw: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor):

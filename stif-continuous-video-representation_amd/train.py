@@ -13,8 +13,8 @@ Both schedules are recurrences on the group's current lr (each step scales the p
 reference evaluates them, so a resumed optimizer continues the same sequence; ``tests/test_train.py`` checks
 them step for step against sequences recorded from the reference's own classes (tests/golden/make_golden.py
 sched).  ``optimize_step`` is VideoSRBaseModel.optimize_parameters (VideoSR_base_model.py:113-134) for a
-module and one target.  The whole-model HIP forward (``LunaTokis``) is inference-only.  Two of the model's
-operators train on the engine's own kernels: the DCN_sep layers of a torch module through the ``_ext`` drop-in
+module and one target.  The inference model (``model.LunaTokis``) stays inference-only; the whole model trains here as
+``train.LunaTokis`` (last entry below).  The model's operators train on the engine's own kernels: the DCN_sep layers of a torch module through the ``_ext`` drop-in
 (integration/_ext.py: stif_dcn_v2_forward / _backward), and the 3x3 / 64 -> 64 convolutions of the residual
 trunks through the modules below.
 
@@ -45,6 +45,13 @@ trunks through the modules below.
   convs), the ConvLSTM cell as one node (the 128 -> 256 Winograd conv writes the pre-activations, stif_lstm_gates_nhwc
   the state; the backward recomputes the gates from them), and the compositions up to ``GenFeat``, which takes an
   optimiser step on everything before the SIREN decoder.
+* ``Siren``, ``Decoder``, ``LunaTokis``, ``TimesLoss`` -- the SIREN decoder (SIREN.py:27-79, Sakuya_arch_test.py:304-311,
+  :364-459) and the whole model (:1222-1231, ``test=False``), DESIGN.md section 3o.  In training the three MLP input
+  matrices are materialised in HBM, one fp32 row per HR pixel (stif_dec_x1_fwd / x2 / x3 and their adjoints; only the
+  two warped scatters of stif_dec_x3_bwd use atomics), and each MLP is one autograd node over stif_siren_fwd (which saves
+  the sine layers' pre-activations) and stif_siren_bwd (fp32 MFMA, deterministic weight gradients).  ``LunaTokis`` holds
+  the reference's 442 keys (the eight of the unused upsampling layers never receive a gradient) and takes an optimiser
+  step through ``optimize_step`` with ``TimesLoss(CharbonnierLoss())``.  The decoder is fp32 in both ``mfma`` modes.
 """
 from __future__ import annotations
 
@@ -1009,3 +1016,253 @@ class GenFeat(nn.Module):
 
     def range_status(self) -> int:
         return range_status(self.conv_first.weight.device)
+
+
+# ---- the SIREN decoder and the whole model (SIREN.py:27-79, Sakuya_arch_test.py:304-311, :364-459, :1222-1231) ----
+
+class _SirenFn(torch.autograd.Function):
+    """A whole SIREN MLP as one node over stif_siren_fwd / stif_siren_bwd.  Saved: the input matrix, the sine
+    layers' pre-activations and the parameters; the backward recomputes sin and cos."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        nl = len(params) // 2
+        xd = x.detach()
+        y, z = ops.siren_fwd(xd, [p.detach() for p in params[:nl]], [p.detach() for p in params[nl:]])
+        ctx.save_for_backward(xd, z, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, z, *params = ctx.saved_tensors
+        nl = len(params) // 2
+        if not g_y.is_cuda:
+            raise RuntimeError("Siren backward: the HIP kernels need a CUDA tensor")
+        g_x, g_ws, g_bs = ops.siren_bwd(x, z, [p.detach() for p in params[:nl]], [p.detach() for p in params[nl:]],
+                                        g_y.contiguous(), need_x=ctx.needs_input_grad[0])
+        grads = [g if need else None for g, need in zip(g_ws + g_bs, ctx.needs_input_grad[1:])]
+        return (g_x, *grads)
+
+
+class _SineLayer(nn.Module):
+    """SIREN.py:27-53: the parameters of one sine layer under the name ``linear``, with the reference's weight
+    initialisation (first layer U(+-1 / in), others U(+-sqrt(6 / in) / 30)) and nn.Linear's default bias."""
+
+    def __init__(self, in_features, out_features, is_first):
+        super().__init__()
+        self.linear = nn.Linear(in_features, out_features)
+        bound = 1.0 / in_features if is_first else math.sqrt(6.0 / in_features) / 30.0
+        with torch.no_grad():
+            self.linear.weight.uniform_(-bound, bound)
+
+
+class Siren(nn.Module):
+    """SIREN.py:57-79 with ``outermost_linear=True`` and omega_0 = 30: ``hidden_features`` (64, 64, 256) or
+    (64, 64, 256, 256) sine layers sin(30 (x W^T + b)) and a final nn.Linear to ``out_features`` in {64, 4, 3}, the
+    parameters under the reference's names (``net.{i}.linear.weight / bias``, ``net.{last}.weight / bias``) and
+    initialisation.  One autograd node on the HIP kernels (stif_siren_fwd / stif_siren_bwd, fp32 MFMA).  ``forward(x)``:
+    x [..., in_features], or [..., in_features rounded up to 8] with zero pad columns as the decoder's input builders
+    write it (no copy) -> [..., out_features]."""
+
+    def __init__(self, in_features: int, hidden_features, out_features: int):
+        super().__init__()
+        hidden = tuple(int(h) for h in hidden_features)
+        if hidden not in ops.SIREN_WIDTHS.values():
+            raise ValueError(f"Siren: hidden_features must be (64, 64, 256) or (64, 64, 256, 256), got {hidden}")
+        if out_features not in (64, 4, 3):
+            raise ValueError(f"Siren: out_features must be 64, 4 or 3, got {out_features}")
+        if not 1 <= in_features <= 528:
+            raise ValueError(f"Siren: in_features must be in [1, 528], got {in_features}")
+        self.in_features, self.hidden_features, self.out_features = int(in_features), hidden, int(out_features)
+        dims = (self.in_features,) + hidden
+        layers = [_SineLayer(dims[i], dims[i + 1], i == 0) for i in range(len(hidden))]
+        last = nn.Linear(hidden[-1], out_features)
+        bound = math.sqrt(6.0 / hidden[-1]) / 30.0
+        with torch.no_grad():
+            last.weight.uniform_(-bound, bound)
+        self.net = nn.Sequential(*layers, last)
+
+    def _params(self):
+        mods = [m.linear for m in self.net[:-1]] + [self.net[-1]]
+        return [m.weight for m in mods] + [m.bias for m in mods]
+
+    def forward(self, x):
+        kp = (self.in_features + 7) // 8 * 8
+        if not x.is_cuda:
+            raise RuntimeError(f"Siren: the HIP kernels need a CUDA tensor, got one on {x.device} "
+                               "(move the module and its input to the GPU)")
+        if x.dtype != torch.float32 or x.dim() < 1 or x.shape[-1] not in (self.in_features, kp) or x.numel() == 0:
+            raise RuntimeError(f"Siren: expected a float32 [..., {self.in_features}] tensor (or [..., {kp}] with zero pad "
+                               f"columns), got {x.dtype} {tuple(x.shape)}")
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, x.shape[-1])
+        if x2.shape[1] != kp:
+            x2 = nn.functional.pad(x2, (0, kp - x2.shape[1]))
+        if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.stride(0) < kp or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        return _SirenFn.apply(x2, *self._params()).reshape(*lead, self.out_features)
+
+    def extra_repr(self):
+        return f"{self.in_features} -> {self.hidden_features} -> {self.out_features}, omega_0=30"
+
+
+class _DecX1Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lat, geom):
+        ctx.geom = geom
+        return ops.dec_x1_fwd(geom)
+
+    @staticmethod
+    def backward(ctx, g_x1):
+        return ops.dec_x1_bwd(ctx.geom, g_x1.contiguous()) if ctx.needs_input_grad[0] else None, None
+
+
+class _DecX2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hrfeat, lat, geom):
+        ctx.geom = geom
+        return ops.dec_x2_fwd(geom, hrfeat.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, g_x2):
+        g_hr, g_lat = ops.dec_x2_bwd(ctx.geom, g_x2.contiguous())
+        return g_hr if ctx.needs_input_grad[0] else None, g_lat if ctx.needs_input_grad[1] else None, None
+
+
+class _DecX3Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hrfeat, flow, lat, geom):
+        hr, fl = hrfeat.detach().contiguous(), flow.detach().contiguous()
+        ctx.geom = geom
+        ctx.save_for_backward(hr, fl)
+        return ops.dec_x3_fwd(geom, hr, fl)
+
+    @staticmethod
+    def backward(ctx, g_x3):
+        hr, fl = ctx.saved_tensors
+        g_flow, g_hr, g_lat = ops.dec_x3_bwd(ctx.geom, hr, fl, g_x3.contiguous())
+        need = ctx.needs_input_grad
+        return g_hr if need[0] else None, g_flow if need[1] else None, g_lat if need[2] else None, None
+
+
+def _hr_size(H, W, scale):
+    """(HH, WW) of the decode: ``scale`` None -> x4 (Sakuya_arch_test.py:368-371); otherwise its two entries, each an
+    int or a tensor as the reference's collated batches carry it (its first element is taken)."""
+    if scale is None:
+        return 4 * H, 4 * W
+    if isinstance(scale, torch.Tensor):
+        scale = scale.reshape(-1).tolist()
+    if len(scale) != 2:
+        raise ValueError(f"scale must be None or (HH, WW), got {scale!r}")
+    return tuple(int(s.reshape(-1)[0]) if isinstance(s, torch.Tensor) else int(s) for s in scale)
+
+
+def _item_times(t, B, device):
+    """One entry of ``times`` -- a float, or a tensor of 1 or B elements such as the reference's [B, 1] -- as a
+    float32 [B] tensor on ``device`` without a gradient."""
+    if isinstance(t, torch.Tensor):
+        t = t.detach().reshape(-1)
+        if t.numel() not in (1, B):
+            raise ValueError(f"a time query must hold 1 or {B} values, got {t.numel()}")
+        return t.to(device=device, dtype=torch.float32).expand(B).contiguous()
+    return torch.full((B,), float(t), dtype=torch.float32, device=device)
+
+
+def _decode(who, feat_imnet, flow_imnet, encode_imnet, feat, inp, times, scale):
+    """LunaTokis.decoding (Sakuya_arch_test.py:364-459): per time, X1 -> feat_imnet -> HRfeat, X2 -> flow_imnet -> flow,
+    X3 -> encode_imnet -> the frame, every matrix in HBM.  Everything is refused before the first
+    launch: CPU tensors, wrong shapes, HH or WW < 2."""
+    if feat.dim() != 5 or feat.shape[1] != 3 or feat.shape[2] != 64:
+        raise ValueError(f"{who}: expected features [B, 3, 64, H, W], got {tuple(feat.shape)}")
+    B, _, _, H, W = feat.shape
+    if tuple(inp.shape) != (B, 2, 3, H, W):
+        raise ValueError(f"{who}: expected frames [{B}, 2, 3, {H}, {W}], got {tuple(inp.shape)}")
+    HH, WW = _hr_size(H, W, scale)
+    if HH < 2 or WW < 2:
+        raise ValueError(f"{who}: the output must be at least 2 x 2 (the warp grid divides by n - 1), got {HH} x {WW}")
+    if times is None or len(times) == 0:
+        raise ValueError(f"{who}: times is a non-empty list")
+    for t in (feat, inp):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: the HIP kernels need a CUDA tensor, got one on {t.device} "
+                               "(move the module and its input to the GPU)")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: expected float32 tensors, got {t.dtype}")
+    tbs = [_item_times(t, B, feat.device) for t in times]
+    lat = feat.reshape(B, 192, H, W).permute(0, 2, 3, 1).contiguous()      # cat(feat[:, 0..2]) (:365), NHWC
+    frames = inp.detach().reshape(B, 6, H, W).contiguous()
+    outs = []
+    for tb in tbs:
+        geom = ops.DecTrainGeom(lat.detach(), frames, tb, HH, WW)
+        hrfeat = feat_imnet(_DecX1Fn.apply(lat, geom))
+        flow = flow_imnet(_DecX2Fn.apply(hrfeat, lat, geom))
+        pred = encode_imnet(_DecX3Fn.apply(hrfeat, flow, lat, geom))
+        outs.append(pred.reshape(B, HH, WW, 3).permute(0, 3, 1, 2))
+    return outs
+
+
+def _make_imnets(mod):
+    mod.feat_imnet = Siren(201, (64, 64, 256), 64)
+    mod.flow_imnet = Siren(65 + 192 + 6, (64, 64, 256), 4)
+    mod.encode_imnet = Siren(141 + 192 * 2, (64, 64, 256, 256), 3)
+
+
+class Decoder(nn.Module):
+    """LunaTokis.decoding (Sakuya_arch_test.py:364-459) with the three SIREN MLPs under the reference's names
+    (``feat_imnet``, ``flow_imnet``, ``encode_imnet``: 26 keys), trainable on the engine.  ``forward(feat, inp, times,
+    scale=None)``: feat [B, 3, 64, H, W] (gen_feat's output), inp [B, 2, 3, H, W] the LR frames, ``times`` a list of
+    floats or [B, 1] tensors, ``scale`` None (x4), (HH, WW) or a pair of tensors -> a list of [B, 3, HH, WW].  One set
+    of autograd nodes per time; gradients reach ``feat`` and the parameters, never ``inp`` or ``times``.  The local
+    ensemble, windows, tiles, points and time fields of the inference decoder are not part of training."""
+
+    def __init__(self):
+        super().__init__()
+        _make_imnets(self)
+
+    def forward(self, feat, inp, times, scale=None):
+        return _decode("Decoder", self.feat_imnet, self.flow_imnet, self.encode_imnet, feat, inp, times, scale)
+
+
+class LunaTokis(GenFeat):
+    """The whole model (Sakuya_arch_test.py:268-311, :1222-1231 with ``test=False``) trainable on the engine:
+    ``GenFeat``'s parameters, the decoder's three SIREN MLPs and the eight keys of the reference's unused upsampling
+    layers (``upconv1``, ``upconv2``, ``HRconv``, ``conv_last``), which take part in nothing and never receive a
+    gradient -- 442 keys, a reference state dict loads with ``strict=True``.  ``forward(x, times, scale=None)``: frames
+    x [B, 2, 3, H, W], H and W multiples of 4 -> a list of [B, 3, HH, WW], one per time."""
+
+    def __init__(self, front_RBs: int = 5, back_RBs: int = 40, mfma: str = "f16x3"):
+        super().__init__(front_RBs, back_RBs, mfma)
+        self.upconv1 = _Conv2dParams(256, 64)
+        self.upconv2 = _Conv2dParams(256, 64)
+        self.HRconv = _Conv2dParams(64, 64)
+        self.conv_last = _Conv2dParams(3, 64)
+        _make_imnets(self)
+
+    def forward(self, x, times, scale=None):
+        if x.dim() != 5 or x.shape[1] != 2 or x.shape[2] != 3:
+            raise ValueError(f"LunaTokis: expected frames [B, 2, 3, H, W], got {tuple(x.shape)}")
+        if x.shape[3] % 4 or x.shape[4] % 4:
+            raise ValueError(f"LunaTokis: H and W must be multiples of 4 (three pyramid levels), got "
+                             f"{x.shape[3]} x {x.shape[4]}")
+        HH, WW = _hr_size(x.shape[3], x.shape[4], scale)
+        if HH < 2 or WW < 2:
+            raise ValueError(f"LunaTokis: the output must be at least 2 x 2, got {HH} x {WW}")
+        if times is None or len(times) == 0:
+            raise ValueError("LunaTokis: times is a non-empty list")
+        if not x.is_cuda:
+            raise RuntimeError(f"LunaTokis: the HIP kernels need a CUDA tensor, got one on {x.device} "
+                               "(move the module and its input to the GPU)")
+        feat = GenFeat.forward(self, x)
+        return _decode("LunaTokis", self.feat_imnet, self.flow_imnet, self.encode_imnet, feat, x, times, scale)
+
+
+class TimesLoss(nn.Module):
+    """VideoSR_base_model.py:126-128: the pixel criterion summed over the query times, output ``idx`` against
+    ``gt[:, idx]`` -- what ``optimize_step`` needs as its criterion for a model that returns a list of frames."""
+
+    def __init__(self, criterion):
+        super().__init__()
+        self.criterion = criterion
+
+    def forward(self, outs, gt):
+        return sum(self.criterion(o, gt[:, i]) for i, o in enumerate(outs))
