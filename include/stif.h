@@ -313,7 +313,8 @@ int stif_siren_bwd(const stif_siren_args* args, void* stream);
  * gather (both gather form, one lane per element in a fixed order: identical bits for repeated calls).  x3_bwd
  * writes g_flow [N][4] with plain stores (the coordinate gradient of all six samples; exactly zero where the clamp is
  * active) and ADDS into g_hrfeat [N][64] and g_feat, which the caller zeroes, with fp32 atomics on whole channel rows:
- * the only order-dependent sums of the decoder backward.  No gradient goes to frames or t.
+ * the only order-dependent sums of the decoder backward (stif_dec_x3_bwd_contrib + stif_segsum, below, is the ordered
+ * alternative with identical bits on every run).  No gradient goes to frames or t.
  * STIF_E_INVALID before any launch: null geometry, a null pointer in it or among the arguments, B / H / W < 1,
  * HH / WW < 2 (the warp grid divides by n - 1), more than 2^31 - 1 float4 of any matrix. */
 typedef struct {
@@ -378,7 +379,8 @@ int stif_dcn_nhwc(const stif_dcn_args* args, void* stream);
  * element by one lane (g_w / g_b through per-workgroup partials in the workspace, added in index order as
  * stif_conv3x3_wgrad does), so repeated calls on one device give identical bits for these three.  g_in is a sum of
  * fp32 atomic adds -- as in the reference and the drop-in -- whose order varies: its last bits may differ from run to
- * run.  workspace (needed with g_w only): at least stif_dcn_bwd_workspace_size bytes, which equals
+ * run; the ordered alternative, with identical bits on every run, is stif_dcn_bwd_contrib + a sort of its packed
+ * words + stif_segsum (below).  workspace (needed with g_w only): at least stif_dcn_bwd_workspace_size bytes, which equals
  * stif_conv3x3_wgrad_workspace_size(n, H, W, 64, 64), 16-B aligned; its previous contents do not matter.
  * STIF_E_INVALID, each with its reason, before any launch: null args, a null in / offmask / w / gout, an unknown epi,
  * epi LRELU with a null out, all of g_in / g_om / g_w null, g_b without g_w, n / H / W < 1, a negative or misaligned
@@ -403,6 +405,69 @@ typedef struct {
 /* 0 for sizes < 1. */
 size_t stif_dcn_bwd_workspace_size(int n, int H, int W);
 int stif_dcn_bwd_nhwc(const stif_dcn_bwd_args* args, void* stream);
+
+/* ---- Deterministic training: ordered sums in place of the three atomic scatters (g_in of stif_dcn_bwd_nhwc, g_hrfeat
+ * and g_feat of stif_dec_x3_bwd).  Every contribution is stored once with plain stores, the caller sorts the packed
+ * words (any stable or unstable sort: the words are unique), and stif_segsum adds per destination in a fixed order.
+ *
+ * A scatter is a list of E entries e = 0 .. E-1.  Entry e has a destination row key[e] in 0 .. D (D: "this corner does
+ * not count"), an fp32 weight w[e], and a source sub-row of C floats at
+ *   src + ((e >> 2) / K) * row_stride + ((e >> 2) % K) * C + col0
+ * (four corners share a sub-row).  Its packed word is (key[e] << 32) | e as int64.  The value of dst[d][c], d < D:
+ * take the entries with key[e] == d in ascending e, cut the list into chunks of 512, within a chunk start from +0.0f
+ * and do acc = acc + (w[e] * src_e[c]) -- an fp32 multiply and an fp32 add, both rounded to nearest, NOT fused -- and
+ * add the chunk partials the same way in chunk order, starting from the first partial.  A list of at most 512 entries
+ * is a plain sequential sum; an empty list gives +0.0f.
+ *
+ * stif_segsum: dst [D][C] (every row overwritten), `sorted` the packed words in ascending order, seg [D + 1] with
+ * seg[d] = the index in `sorted` of the first word whose key is >= d.  C is 8, 64 or 192.  The kernel does not trust
+ * the indices: segment bounds are clamped to [0, E], an entry id >= E is skipped, every loop is bounded by E; src
+ * must hold ceil(E / 4 / K) rows of row_stride floats and w E floats.  No floating-point atomics; repeated calls give
+ * identical bits.  STIF_E_INVALID before the launch: a null pointer, C not 8 / 64 / 192, D / E / K < 1, D or E >= 2^31,
+ * col0 < 0, col0 or row_stride no multiple of 4, row_stride < K * C + col0, dst / src not 16-byte, w not 4-byte,
+ * sorted / seg not 8-byte aligned. */
+int stif_segsum(float* dst, const float* src, long long row_stride, int K, int col0, const float* w,
+                const long long* sorted, const long long* seg, long long D, long long E, int C, void* stream);
+
+/* stif_dcn_bwd_nhwc's data kernel with stores in place of the g_in scatter (the same MFMA front end): g_om exactly as
+ * stif_dcn_bwd_nhwc writes it (same bytes; NULL: not written), and for pixel p = (i H + y) W + x of the call, group g,
+ * tap k, corner j (low/low, low/high, high/low, high/high), e = ((p * 8 + g) * 9 + k) * 4 + j:
+ *   cm [n H W][8][9][8]  the contribution sub-rows colg * m, every one written (zeros where no corner counts),
+ *   wgt [E]              the corner's bilinear weight product (0 for a corner that does not count),
+ *   words [E]            (key << 32) | e, key = (pixel index of the corner) * 8 + g, or D = n H W 8.
+ * E = n H W 288.  g_in [n][H][W][64] dense is then stif_segsum(g_in, cm, 576, 72, 0, wgt, sorted words, seg, D, E, 8).
+ * Inputs and strides as stif_dcn_bwd_args; all buffers are the caller's, nothing is allocated.  STIF_E_INVALID before
+ * the launch: null args, a null in / offmask / w / gout / cm / wgt / words, an unknown epi, epi LRELU with a null out,
+ * n / H / W < 1, a negative or misaligned stride or base (16 bytes), overlapping g_om items, an item of 2 GB or more,
+ * E >= 2^31 (call it on fewer items: items are independent).  Zero-initialise the struct, then fill. */
+typedef struct {
+  const float* in;
+  const float* offmask;
+  const float* w;
+  const float* gout;
+  const float* out;      /* read only with epi = STIF_EPI_LRELU */
+  float* g_om;           /* NHWC [n][H][W][256], or NULL */
+  float* cm;
+  float* wgt;
+  long long* words;
+  long long in_item, om_item, gout_item, out_item, gom_item;
+  int n, H, W;
+  int epi;
+} stif_dcn_bwd_contrib_args;
+int stif_dcn_bwd_contrib(const stif_dcn_bwd_contrib_args* args, void* stream);
+
+/* stif_dec_x3_bwd with stores in place of its two scatters: g_flow exactly as stif_dec_x3_bwd writes it (same bytes),
+ * and for HR pixel row n of g_x3, grid k (0, 1), corner j (y0 x0, y0 x1, y1 x0, y1 x1), e = (n * 2 + k) * 4 + j, the
+ * weight wx * wy (0 outside the map) and the packed word of the corner on the HR lattice (w_hr, words_hr: key =
+ * b HH WW + y WW + x, or D = B HH WW) and on the LR lattice (w_lr, words_lr: key = b H W + y W + x, or D = B H W).
+ * E = 8 N.  The source sub-rows are g_x3 itself:
+ *   g_hrfeat = stif_segsum(.., g_x3, 528, 2, 0, w_hr, .., D = N, E, 64),
+ *   g_feat   = stif_segsum(.., g_x3, 528, 2, 128, w_lr, .., D = B H W, E, 192).
+ * STIF_E_INVALID as stif_dec_x3_bwd, and: a null w_hr / words_hr / w_lr / words_lr, words not 8-byte aligned,
+ * E >= 2^31. */
+int stif_dec_x3_bwd_contrib(const stif_dec_train_geom* g, const float* hrfeat, const float* flow, const float* g_x3,
+                            float* g_flow, float* w_hr, long long* words_hr, float* w_lr, long long* words_lr,
+                            void* stream);
 
 /* The offset / mask conv's output as the deformable conv reads it: om NHWC [n][H][W][256] in the reference's row order
  * (channel g*18 + 2k (+1) the h (w) offset of group g, tap k; 144 + g*9 + k the mask logit; 216..255 never read) ->

@@ -89,6 +89,18 @@ class DcnBwdArgs(C.Structure):
     ]
 
 
+class DcnBwdContribArgs(C.Structure):
+    """stif_dcn_bwd_contrib_args: stif_dcn_bwd_nhwc's data kernel with the g_in scatter stored as contribution
+    sub-rows ``cm``, corner weights ``wgt`` and packed sort words ``words`` (g_om may be NULL)."""
+    _fields_ = [
+        ("inp", _P), ("offmask", _P), ("w", _P), ("gout", _P), ("out", _P), ("g_om", _P),
+        ("cm", _P), ("wgt", _P), ("words", _P),
+        ("in_item", C.c_longlong), ("om_item", C.c_longlong), ("gout_item", C.c_longlong), ("out_item", C.c_longlong),
+        ("gom_item", C.c_longlong),
+        ("n", C.c_int), ("H", C.c_int), ("W", C.c_int), ("epi", C.c_int),
+    ]
+
+
 class DecTables(C.Structure):
     _fields_ = [(n, _P) for n in ("near_y", "rel_y", "by0", "by1", "wy0", "wy1", "lin_y",
                                   "near_x", "rel_x", "bx0", "bx1", "wx0", "wx1", "lin_x", "hr_y", "hr_x")]
@@ -223,6 +235,10 @@ EXPORTS = {
     "stif_dcn_sep_nhwc": (C.c_int, [C.POINTER(DcnSepArgs), _P]),
     "stif_dcn_bwd_workspace_size": (C.c_size_t, [C.c_int] * 3),
     "stif_dcn_bwd_nhwc": (C.c_int, [C.POINTER(DcnBwdArgs), _P]),
+    "stif_dcn_bwd_contrib": (C.c_int, [C.POINTER(DcnBwdContribArgs), _P]),
+    "stif_dec_x3_bwd_contrib": (C.c_int, [C.POINTER(DecTrainGeom)] + [_P] * 9),
+    "stif_segsum": (C.c_int, [_P, _P, C.c_longlong, C.c_int, C.c_int, _P, _P, _P, C.c_longlong, C.c_longlong, C.c_int,
+                              _P]),
     "stif_dcn_offmask_nhwc": (C.c_int, [_P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, _P]),
     "stif_dcn_v2_workspace_size": (C.c_size_t, [C.c_int] * 14),
     "stif_dcn_v2_forward": (C.c_int, [_P] * 6 + [C.c_int] * 14 + [_P, C.c_size_t, _P]),

@@ -7,7 +7,8 @@
 //   k_dcn_bwd_data  colg[p][c][k] = sum_co w[co][c][k] gout[p][co] on fp32 MFMA, one deformable group at a time, held
 //                   in accumulators; the lane that owns (pixel, tap) turns its eight colg values into grad_offset,
 //                   grad_mask (stored into g_om, one writer per element) and the g_in scatter (LDS tile, then one
-//                   atomic flush per group)
+//                   atomic flush per group); instantiated a second time as stif_dcn_bwd_contrib's kernel, which
+//                   stores the scatter's terms for the ordered sum of segsum.hip instead
 //   k_dcn_bwd_w     k_wgrad<1>'s scheme with the sampled, modulated columns as the B operand: persistent grid,
 //                   [tap][co][ci] accumulators kept across tiles, one partial per workgroup, k_wgrad_reduce
 // The `_ext` drop-in (NCHW, any geometry) stays dcn_v2.hip.
@@ -53,9 +54,24 @@ STIF_DEV f32x4 ld_gout(const float* gout, const float* out, bool lrelu) {
 constexpr int DB_TH = 4, DB_TW = 32, DB_M = DCN_M;
 constexpr int DB_TR = DB_TH + 2 + 2 * DB_M, DB_TC = DB_TW + 2 + 2 * DB_M, DB_TPX = DB_TR * DB_TC;
 
-__global__ __launch_bounds__(64 * DB_TH) void k_dcn_bwd_data(stif_dcn_bwd_args a, int tiles_x, int tiles_per_item) {
+// CONTRIB (stif_dcn_bwd_contrib): the same front end, g_om included, but no scatter.  The lane
+// stores its tap's contribution sub-row cm[p][g][k][8] = colg * m once, the four corner weights and the four packed
+// sort words (key << 32) | e, e = ((p * 8 + g) * 9 + k) * 4 + corner, key = (corner pixel) * 8 + g or the sentinel
+// n H W 8 for a corner that does not count; stif_segsum adds them per destination in a fixed order.
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+struct DcnContrib {
+  float* cm;          // [n H W][8][9][8]
+  float* wgt;         // [E]
+  long long* words;   // [E]
+};
+struct DcnScatter {};   // the atomic path: an empty last kernel argument, which moves no other argument
+
+template <class CT>
+__global__ __launch_bounds__(64 * DB_TH) void k_dcn_bwd_data(stif_dcn_bwd_args a, int tiles_x, int tiles_per_item,
+                                                             CT ct) {
+  constexpr bool CONTRIB = std::is_same<CT, DcnContrib>::value;
   __shared__ __attribute__((aligned(16))) float s_w[64 * 72];   // [co][c][tap] of the group
-  __shared__ float s_gi[8 * DB_TPX];                            // [c][tile pixel]
+  __shared__ float s_gi[CONTRIB ? 1 : 8 * DB_TPX];              // [c][tile pixel]
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l32 = lane & 31, hf = lane >> 5;
   const int H = a.H, W = a.W;
   const int n = blockIdx.x / tiles_per_item, rem = blockIdx.x - n * tiles_per_item;
@@ -91,7 +107,7 @@ __global__ __launch_bounds__(64 * DB_TH) void k_dcn_bwd_data(stif_dcn_bwd_args a
       const int co = i / 18, q = i - co * 18;
       st4(s_w + co * 72 + q * 4, ld4(a.w + co * 576 + g * 72 + q * 4));
     }
-    if (gin)
+    if (!CONTRIB && gin)
       for (int i = tid; i < 8 * DB_TPX; i += 64 * DB_TH) s_gi[i] = 0.f;
     __syncthreads();
 
@@ -165,7 +181,27 @@ __global__ __launch_bounds__(64 * DB_TH) void k_dcn_bwd_data(stif_dcn_bwd_args a
           *reinterpret_cast<float2*>(gom + g * 18 + 2 * tap) = make_float2(vh * m, vw * m);
           gom[144 + g * 9 + tap] = vm * m * (1.f - m);
         }
-        if (gin) {
+        if constexpr (CONTRIB) {
+          if (mine) {
+            const size_t sub = (((size_t)n * H * W + pix) * 8 + g) * 9 + tap;
+            const long long D = (long long)a.n * H * W * 8;
+            const bool any = b1 || b2 || b3 || b4;
+            f32x4 lo, hi;
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) lo[ch] = any ? col[ch] * m : 0.f, hi[ch] = any ? col[4 + ch] * m : 0.f;
+            st4(ct.cm + sub * 8, lo);
+            st4(ct.cm + sub * 8 + 4, hi);
+            st4(ct.wgt + sub * 4, f32x4{b1 ? c.hh * c.hw : 0.f, b2 ? c.hh * c.lw : 0.f, b3 ? c.lh * c.hw : 0.f,
+                                        b4 ? c.lh * c.lw : 0.f});
+            auto word = [&](bool b, int y, int x, int j) {
+              const long long key = b ? (((long long)n * H + y) * W + x) * 8 + g : D;
+              return (key << 32) | (long long)(sub * 4 + j);
+            };
+            i64x2* wd = reinterpret_cast<i64x2*>(ct.words + sub * 4);   // two 16-byte stores
+            wd[0] = i64x2{word(b1, c.h_low, c.w_low, 0), word(b2, c.h_low, c.w_high, 1)};
+            wd[1] = i64x2{word(b3, c.h_high, c.w_low, 2), word(b4, c.h_high, c.w_high, 3)};
+          }
+        } else if (gin) {
           auto scatter = [&](bool b, int y, int x, float wt) {
             if (!b) return;
             const int r = y - ty0, cc = x - tx0;
@@ -187,7 +223,7 @@ __global__ __launch_bounds__(64 * DB_TH) void k_dcn_bwd_data(stif_dcn_bwd_args a
       }
     }
 
-    if (gin) {
+    if (!CONTRIB && gin) {
       __syncthreads();
       for (int i = tid; i < 8 * DB_TPX; i += 64 * DB_TH) {
         const int ch = i & 7, p = i >> 3, r = p / DB_TC, cc = p - r * DB_TC;
@@ -407,7 +443,8 @@ extern "C" int stif_dcn_bwd_nhwc(const stif_dcn_bwd_args* pa, void* stream) {
   }
   if (a.g_in || a.g_om) {
     const int tiles_x = (a.W + DB_TW - 1) / DB_TW, tiles_per_item = tiles_x * ((a.H + DB_TH - 1) / DB_TH);
-    hipLaunchKernelGGL(k_dcn_bwd_data, dim3((unsigned)dtiles), dim3(64 * DB_TH), 0, st, a, tiles_x, tiles_per_item);
+    hipLaunchKernelGGL(k_dcn_bwd_data<DcnScatter>, dim3((unsigned)dtiles), dim3(64 * DB_TH), 0, st, a, tiles_x,
+                       tiles_per_item, DcnScatter{});
     if (int rc = stif_check_launch("stif_dcn_bwd_nhwc (data)")) return rc;
   }
   if (a.g_w) {
@@ -419,6 +456,38 @@ extern "C" int stif_dcn_bwd_nhwc(const stif_dcn_bwd_args* pa, void* stream) {
     return stif_check_launch("stif_dcn_bwd_nhwc (reduce)");
   }
   return STIF_OK;
+}
+
+extern "C" int stif_dcn_bwd_contrib(const stif_dcn_bwd_contrib_args* pa, void* stream) {
+  const char* fn = "stif_dcn_bwd_contrib";
+  if (!pa) return fail_as(fn, "null args");
+  const stif_dcn_bwd_contrib_args& c = *pa;
+  if (!c.in || !c.offmask || !c.w || !c.gout) return fail_as(fn, "null pointer (in, offmask, w, gout)");
+  if (!c.cm || !c.wgt || !c.words) return fail_as(fn, "null pointer (cm, wgt, words)");
+  if (c.epi != STIF_EPI_NONE && c.epi != STIF_EPI_LRELU) return fail_as(fn, "epilogue must be NONE or LRELU");
+  const bool lrelu = c.epi == STIF_EPI_LRELU;
+  if (lrelu && !c.out) return fail_as(fn, "null pointer (out with STIF_EPI_LRELU)");
+  if (c.n < 1 || c.H < 1 || c.W < 1) return fail_as(fn, "n, H, W must be >= 1");
+  if (c.in_item < 0 || c.om_item < 0 || c.gout_item < 0 || (lrelu && c.out_item < 0) || (c.g_om && c.gom_item < 0))
+    return fail_as(fn, "negative item stride");
+  if ((long long)c.H * c.W * GOMC * 4 >= 0x7fffffffLL) return fail_as(fn, "item larger than 2 GB (buffer addressing)");
+  const long long px = (long long)c.H * c.W;
+  if (px * c.n > 0x7fffffffLL / 288) return fail_as(fn, "E = n * H * W * 288 must be < 2^31 (call it on fewer items)");
+  if (misaligned16(c.in) || misaligned16(c.offmask) || misaligned16(c.w) || misaligned16(c.gout) ||
+      (lrelu && misaligned16(c.out)) || misaligned16(c.g_om) || misaligned16(c.cm) || misaligned16(c.wgt) ||
+      misaligned16(c.words) || c.in_item % 4 || c.om_item % 4 || c.gout_item % 4 || (lrelu && c.out_item % 4) ||
+      (c.g_om && c.gom_item % 4))
+    return fail_as(fn, "maps, w, cm, wgt, words and the item strides must be 16-byte aligned");
+  if (c.n > 1 && c.g_om && c.gom_item < px * GOMC) return fail_as(fn, "g_om items overlap (gom_item < H * W * 256)");
+  stif_dcn_bwd_args a = {};
+  a.in = c.in, a.offmask = c.offmask, a.w = c.w, a.gout = c.gout, a.out = c.out, a.g_om = c.g_om;
+  a.in_item = c.in_item, a.om_item = c.om_item, a.gout_item = c.gout_item, a.out_item = c.out_item;
+  a.gom_item = c.gom_item, a.n = c.n, a.H = c.H, a.W = c.W, a.epi = c.epi;
+  const long long dtiles = tiles_of(c.n, c.H, c.W, DB_TH, DB_TW);
+  const int tiles_x = (c.W + DB_TW - 1) / DB_TW, tiles_per_item = tiles_x * ((c.H + DB_TH - 1) / DB_TH);
+  hipLaunchKernelGGL(k_dcn_bwd_data<DcnContrib>, dim3((unsigned)dtiles), dim3(64 * DB_TH), 0,
+                     static_cast<hipStream_t>(stream), a, tiles_x, tiles_per_item, DcnContrib{c.cm, c.wgt, c.words});
+  return stif_check_launch(fn);
 }
 
 extern "C" int stif_dcn_offmask_nhwc(const float* om, float* offmask, long long om_item, long long offmask_item, int n,

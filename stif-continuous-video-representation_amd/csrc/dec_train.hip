@@ -245,10 +245,32 @@ STIF_DEV DXY sample_bwd(const float* map, float* gmap, size_t stride, int Wd, co
 // One wave per HR pixel: lane l takes channel l of HRfeat, channels l, l + 64, l + 128 of the latent and (l < 6)
 // frame plane l, for both grids.  g_flow is the wave's sum of the coordinate gradients through ix = ((g + 1) n - 1) / 2
 // (n the sampled map's size) and g = base + flow / ((NN - 1) / 2), zero where the clamp is active; one plain store.
+// CONTRIB (stif_dec_x3_bwd_contrib): g_flow as above and no scatter.  Lanes 0..3 store corner
+// `lane` of the wave's two samples on each lattice as a weight and a packed sort word (key << 32) | e,
+// e = (n * 2 + grid) * 4 + corner, key = the corner's pixel row of the map or the map's pixel count for a corner
+// outside it; stif_segsum adds w * g_x3 sub-rows per destination in a fixed order.
+struct X3Contrib {
+  float *w_hr, *w_lr;
+  long long *words_hr, *words_lr;
+};
+// corner j of sample_bwd's order (b00, b01, b10, b11) on a map of B items of Hd x Wd pixels, item b
+STIF_DEV void put_corner(const Cn& c, int j, int b, int B, int Hd, int Wd, long long e, float* w, long long* words) {
+  const bool hy = j >> 1, hx = j & 1;
+  const bool ok = (hy ? c.vy1 : c.vy0) && (hx ? c.vx1 : c.vx0);
+  const int y = hy ? c.y1 : c.y0, x = hx ? c.x1 : c.x0;
+  const long long key = ok ? ((long long)b * Hd + y) * Wd + x : (long long)B * Hd * Wd;
+  w[e] = ok ? (hx ? c.wx1 : c.wx0) * (hy ? c.wy1 : c.wy0) : 0.f;
+  words[e] = (key << 32) | e;
+}
+
+struct X3Scatter {};   // the atomic path: an empty last kernel argument, which moves no other argument
+
+template <class CT>
 __global__ __launch_bounds__(256) void k_x3_bwd(Geom g, const float* __restrict__ hrfeat,
                                                 const float* __restrict__ flow, const float* __restrict__ gx3,
                                                 float* __restrict__ g_flow, float* __restrict__ g_hr,
-                                                float* __restrict__ g_feat, long long N) {
+                                                float* __restrict__ g_feat, long long N, CT ct) {
+  constexpr bool CONTRIB = std::is_same<CT, X3Contrib>::value;
   const int lane = threadIdx.x & 63;
   const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -262,12 +284,21 @@ __global__ __launch_bounds__(256) void k_x3_bwd(Geom g, const float* __restrict_
   for (int k = 0; k < 2; ++k) {
     const Warp wx = warp_axis(bx, fv[2 * k], g.WW), wy = warp_axis(by, fv[2 * k + 1], g.HH);
     const Cn ch = corners(wx.g, wy.g, g.WW, g.HH), cl = corners(wx.g, wy.g, g.W, g.H);
-    const DXY dh = sample_bwd(hrfeat + hr_item, g_hr + hr_item, 64, g.WW, ch, lane, grow[k * 64 + lane]);
+    if constexpr (CONTRIB) {
+      if (lane < 4) {
+        const long long e = (n * 2 + k) * 4 + lane;
+        put_corner(ch, lane, p.b, g.B, g.HH, g.WW, e, ct.w_hr, ct.words_hr);
+        put_corner(cl, lane, p.b, g.B, g.H, g.W, e, ct.w_lr, ct.words_lr);
+      }
+    }
+    float* const ghr = CONTRIB ? nullptr : g_hr + hr_item;
+    float* const glr = CONTRIB ? nullptr : g_feat + lr_item;
+    const DXY dh = sample_bwd(hrfeat + hr_item, ghr, 64, g.WW, ch, lane, grow[k * 64 + lane]);
     float lx = 0.f, ly = 0.f;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int c = lane + 64 * j;
-      const DXY d = sample_bwd(g.feat + lr_item, g_feat + lr_item, 192, g.W, cl, c, grow[128 + k * 192 + c]);
+      const DXY d = sample_bwd(g.feat + lr_item, glr, 192, g.W, cl, c, grow[128 + k * 192 + c]);
       lx += d.dx, ly += d.dy;
     }
     if (lane < 6) {
@@ -375,7 +406,24 @@ extern "C" int stif_dec_x3_bwd(const stif_dec_train_geom* g, const float* hrfeat
   if (int rc = check_geom(fn, g, &N)) return rc;
   if (!hrfeat || !flow || !g_x3 || !g_flow || !g_hrfeat || !g_feat)
     return fail_as(fn, "null pointer (hrfeat, flow, g_x3, g_flow, g_hrfeat, g_feat)");
-  hipLaunchKernelGGL(k_x3_bwd, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), *g, hrfeat,
-                     flow, g_x3, g_flow, g_hrfeat, g_feat, N);
+  hipLaunchKernelGGL(k_x3_bwd<X3Scatter>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     *g, hrfeat, flow, g_x3, g_flow, g_hrfeat, g_feat, N, X3Scatter{});
+  return stif_check_launch(fn);
+}
+
+extern "C" int stif_dec_x3_bwd_contrib(const stif_dec_train_geom* g, const float* hrfeat, const float* flow,
+                                       const float* g_x3, float* g_flow, float* w_hr, long long* words_hr,
+                                       float* w_lr, long long* words_lr, void* stream) {
+  const char* fn = "stif_dec_x3_bwd_contrib";
+  long long N;
+  if (int rc = check_geom(fn, g, &N)) return rc;
+  if (!hrfeat || !flow || !g_x3 || !g_flow) return fail_as(fn, "null pointer (hrfeat, flow, g_x3, g_flow)");
+  if (!w_hr || !words_hr || !w_lr || !words_lr) return fail_as(fn, "null pointer (w_hr, words_hr, w_lr, words_lr)");
+  if (N > 0x7fffffffLL / 8) return fail_as(fn, "E = B * HH * WW * 8 must be < 2^31");
+  if ((reinterpret_cast<uintptr_t>(words_hr) | reinterpret_cast<uintptr_t>(words_lr)) & 7)
+    return fail_as(fn, "words_hr and words_lr must be 8-byte aligned");
+  hipLaunchKernelGGL(k_x3_bwd<X3Contrib>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     *g, hrfeat, flow, g_x3, g_flow, static_cast<float*>(nullptr), static_cast<float*>(nullptr), N,
+                     X3Contrib{w_hr, w_lr, words_hr, words_lr});
   return stif_check_launch(fn);
 }

@@ -802,15 +802,62 @@ def dec_x3_fwd(g: DecTrainGeom, hrfeat: torch.Tensor, flow: torch.Tensor,
     return x3
 
 
+def segsum(dst: torch.Tensor, src: torch.Tensor, row_stride: int, K: int, col0: int, w: torch.Tensor,
+           sorted_words: torch.Tensor, seg: torch.Tensor) -> torch.Tensor:
+    """The ordered segment sum stif_segsum (stif.h states the value): ``dst`` [D, C] float32 (C = 8, 64 or 192, every
+    row overwritten), ``src`` the float32 buffer of sub-rows, ``w`` [E] float32, ``sorted_words`` [E] int64 -- the
+    packed words (key << 32) | entry in ascending order -- and ``seg`` [D + 1] int64, seg[d] the index of the first
+    word whose key is >= d.  No atomics: identical bits on every call."""
+    if dst.dim() != 2 or dst.dtype != torch.float32 or not dst.is_cuda or not dst.is_contiguous():
+        raise ValueError(f"segsum: dst must be a contiguous float32 CUDA [D, C], got {tuple(dst.shape)}")
+    D, Cc = dst.shape
+    E = w.numel()
+    for name, t, dt, numel in (("src", src, torch.float32, None), ("w", w, torch.float32, E),
+                               ("sorted_words", sorted_words, torch.int64, E), ("seg", seg, torch.int64, D + 1)):
+        if t.dtype != dt or t.device != dst.device or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+            raise ValueError(f"segsum: {name} must be a contiguous {dt} tensor on {dst.device}"
+                             + (f" of {numel} elements" if numel is not None else ""))
+    rows = ((E + 3) // 4 + K - 1) // max(K, 1)
+    if K >= 1 and src.numel() < (rows - 1) * row_stride + K * Cc + col0:
+        raise ValueError(f"segsum: src holds {src.numel()} floats, fewer than {rows} rows of {row_stride}")
+    trace = (("segsum", Cc), 2.0 * E * Cc, 4.0 * (D * Cc + E * (Cc / 4 + 3))) if TRACE is not None else None
+    _launch("stif_segsum", trace, L.lib().stif_segsum, _vp(dst), _vp(src), row_stride, K, col0, _vp(w),
+            _vp(sorted_words), _vp(seg), D, E, Cc, torch.cuda.current_stream(dst.device).cuda_stream)
+    return dst
+
+
+def _sorted_segments(words: torch.Tensor, D: int):
+    """The packed words of a scatter in ascending order and the D + 1 segment starts: integer torch calls on the
+    device whose results are unique (the words are distinct), so nothing here depends on an order of arrival."""
+    srt = torch.sort(words).values
+    bounds = torch.arange(D + 1, dtype=torch.int64, device=words.device) << 32
+    return srt, torch.searchsorted(srt, bounds)
+
+
 def dec_x3_bwd(g: DecTrainGeom, hrfeat: torch.Tensor, flow: torch.Tensor, g_x3: torch.Tensor,
-               g_flow: Optional[torch.Tensor] = None):
+               g_flow: Optional[torch.Tensor] = None, deterministic: bool = False):
     """The adjoint of dec_x3_fwd (stif_dec_x3_bwd): (g_flow [N, 4], g_hrfeat [N, 64], g_feat [B, H, W, 192]).  g_flow
     is written with plain stores and is exactly zero where a grid is clamped; g_hrfeat and g_feat are zeroed here and
-    scattered into with fp32 atomics -- the only order-dependent sums of the decoder backward."""
+    scattered into with fp32 atomics -- the only order-dependent sums of the decoder backward.  ``deterministic``:
+    the same g_flow bytes from stif_dec_x3_bwd_contrib, which stores every corner's weight and packed sort word in
+    place of the scatters; the words are sorted and stif_segsum adds g_hrfeat and g_feat per destination in a fixed
+    order (identical bits on every call)."""
     hrfeat = g._mat("dec_x3_bwd: hrfeat", hrfeat, 64)
     flow = g._mat("dec_x3_bwd: flow", flow, 4)
     g_x3 = g._mat("dec_x3_bwd: g_x3", g_x3, 528)
     g_flow = g._mat("dec_x3_bwd: g_flow", g_flow, 4)
+    if deterministic:
+        dev, E = g.feat.device, 8 * g.N
+        w_hr, w_lr = torch.empty(2, E, dtype=torch.float32, device=dev)
+        words_hr, words_lr = torch.empty(2, E, dtype=torch.int64, device=dev)
+        trace = (("dec_x3_bwd_contrib",), 0.0, 4.0 * g.N * (528 + 4 * 262 + 8 * 6)) if TRACE is not None else None
+        g._run("stif_dec_x3_bwd_contrib", trace, _vp(hrfeat), _vp(flow), _vp(g_x3), _vp(g_flow), _vp(w_hr),
+               _vp(words_hr), _vp(w_lr), _vp(words_lr))
+        g_hrfeat = g._mat("dec_x3_bwd: g_hrfeat", None, 64)
+        g_feat = torch.empty_like(g.feat)
+        segsum(g_hrfeat, g_x3, 528, 2, 0, w_hr, *_sorted_segments(words_hr, g.N))
+        segsum(g_feat.view(-1, 192), g_x3, 528, 2, 128, w_lr, *_sorted_segments(words_lr, g.B * g.H * g.W))
+        return g_flow, g_hrfeat, g_feat
     g_hrfeat = g._mat("dec_x3_bwd: g_hrfeat", None, 64, torch.zeros)
     g_feat = torch.zeros_like(g.feat)
     trace = (("dec_x3_bwd",), 0.0, 4.0 * g.N * (528 + 3 * 4 * 262)) if TRACE is not None else None
@@ -879,15 +926,65 @@ def dcn_offmask(om: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     return out
 
 
+# The ordered g_in path works on as many items of a call at a time as keep its transient buffers under this many bytes
+# (and E = items * H * W * 288 below 2^31); one item is the least.  Per pixel: the contribution slab 576 floats, 288
+# corner weights (float32), 288 packed words (int64), torch.sort's sorted words and indices (2 x 288 int64) and as much
+# again allowed for the radix sort's own double buffer, and the 8 + 8 int64 of the segment bounds and starts.
+DET_TRANSIENT_BYTES = 1 << 30
+_DET_BYTES_PER_PIXEL = 576 * 4 + 288 * 4 + 288 * 8 * (1 + 2 + 2) + 2 * 8 * 8
+
+
+def _dcn_bwd_ordered(inp, offmask, weight, gout, out, epi, need_om):
+    """(g_in, g_om or None) of dcn_bwd without atomics: stif_dcn_bwd_contrib, a sort of its packed words, the segment
+    starts and stif_segsum, over chunks of items (items are independent, so the chunking cannot change a bit)."""
+    n, H, W, _ = inp.shape
+    dev, px = inp.device, H * W
+    per_chunk = max(1, min(DET_TRANSIENT_BYTES // (_DET_BYTES_PER_PIXEL * px), (2 ** 31 - 1) // (288 * px), n))
+    g_in = torch.empty(n, H, W, 64, dtype=torch.float32, device=dev)
+    g_om = torch.empty(n, H, W, 256, dtype=torch.float32, device=dev) if need_om else None
+    cm = torch.empty(per_chunk * px, 576, dtype=torch.float32, device=dev)
+    wgt = torch.empty(per_chunk * px * 288, dtype=torch.float32, device=dev)
+    words = torch.empty(per_chunk * px * 288, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for i0 in range(0, n, per_chunk):
+        m = min(per_chunk, n - i0)
+        a = L.DcnBwdContribArgs()
+        def item(t, what):
+            stride = _item_stride([t], "dcn_bwd " + what)
+            return _vp(t[i0:]), (stride if m > 1 else px * t.shape[3])
+
+        a.inp, a.in_item = item(inp, "inp")
+        a.offmask, a.om_item = item(offmask, "offmask")
+        a.gout, a.gout_item = item(gout, "gout")
+        a.w = _vp(weight)
+        if epi == L.EPI_LRELU:
+            a.out, a.out_item = item(out, "out")
+        if need_om:
+            a.g_om, a.gom_item = _vp(g_om[i0:]), px * 256
+        E, D = m * px * 288, m * px * 8
+        a.cm, a.wgt, a.words = _vp(cm), _vp(wgt), _vp(words)
+        a.n, a.H, a.W, a.epi = m, H, W, epi
+        trace = None
+        if TRACE is not None:
+            trace = (("dcn_bwd_contrib", epi, need_om), 2.0 * 64 * 576 * m * px,
+                     4.0 * (64 * 2 + 216 + 256 * need_om + 576 + 288 * 3) * m * px)
+        _launch("stif_dcn_bwd_contrib", trace, L.lib().stif_dcn_bwd_contrib, C.byref(a), stream)
+        srt, seg = _sorted_segments(words[:E], D)
+        segsum(g_in[i0:i0 + m].view(D, 8), cm, 576, 72, 0, wgt[:E], srt, seg)
+    return g_in, g_om
+
+
 def dcn_bwd(inp: torch.Tensor, offmask: torch.Tensor, weight: torch.Tensor, gout: torch.Tensor, *,
-            out: Optional[torch.Tensor] = None, epi=L.EPI_NONE, need=(True, True, True)):
+            out: Optional[torch.Tensor] = None, epi=L.EPI_NONE, need=(True, True, True), deterministic: bool = False):
     """Backward of ops.dcn (fp32, one group) on NHWC maps (stif_dcn_bwd_nhwc): ``inp`` / ``gout`` [n, H, W, 64],
     ``offmask`` [n, H, W, 216] as the forward read it, ``weight`` the state dict's [64, 64, 3, 3] on the device,
     ``out`` the forward's output (needed with ``epi`` = EPI_LRELU only: the activation's derivative).  ``need`` =
     (g_in, g_om, g_w): what to compute.  Returns (g_in [n, H, W, 64], g_om [n, H, W, 256], g_w [64, 64, 3, 3],
     g_b [64]) with None for what was not asked for (g_b comes with g_w).  g_om is the gradient of the offset / mask
     conv's 256-channel output: grad_offset in channels 0..143, grad_mask * m (1 - m) in 144..215, zeros in the pad
-    channels.  g_om, g_w and g_b have identical bits on repeated calls; g_in is an fp32 atomic sum."""
+    channels.  g_om, g_w and g_b have identical bits on repeated calls; g_in is an fp32 atomic sum.  ``deterministic``:
+    g_in is the ordered sum instead (stif_dcn_bwd_contrib, a sort, stif_segsum; DET_TRANSIENT_BYTES bounds its
+    transient buffers), with identical bits on repeated calls; g_om, g_w and g_b keep their bytes."""
     need_in, need_om, need_w = (bool(v) for v in need)
     if inp.dim() != 4 or inp.shape[3] != 64 or 0 in inp.shape or gout.shape != inp.shape:
         raise ValueError(f"dcn_bwd: inp {tuple(inp.shape)} and gout {tuple(gout.shape)} must both be [n, H, W, 64]")
@@ -904,6 +1001,12 @@ def dcn_bwd(inp: torch.Tensor, offmask: torch.Tensor, weight: torch.Tensor, gout
         raise ValueError("dcn_bwd: nothing to compute")
     weight = weight.detach().contiguous()
     dev = inp.device
+    if deterministic and need_in:
+        g_in, g_om = _dcn_bwd_ordered(inp, offmask, weight, gout, out, epi, need_om)
+        g_w = g_b = None
+        if need_w:   # the weight kernel alone: already a fixed-order sum
+            _, _, g_w, g_b = dcn_bwd(inp, offmask, weight, gout, out=out, epi=epi, need=(False, False, True))
+        return g_in, g_om, g_w, g_b
     a = L.DcnBwdArgs()
     def item(t, what):   # checks dtype, device and pixel contiguity; the stride of a size-1 dim addresses nothing
         stride = _item_stride([t], "dcn_bwd " + what)

@@ -48,13 +48,14 @@ trunks through the modules below.
 * ``Siren``, ``Decoder``, ``LunaTokis``, ``TimesLoss`` -- the SIREN decoder (SIREN.py:27-79, Sakuya_arch_test.py:304-311,
   :364-459) and the whole model (:1222-1231, ``test=False``), DESIGN.md section 3o.  In training the three MLP input
   matrices are materialised in HBM, one fp32 row per HR pixel (stif_dec_x1_fwd / x2 / x3 and their adjoints; only the
-  two warped scatters of stif_dec_x3_bwd use atomics), and each MLP is one autograd node over stif_siren_fwd (which saves
+  two warped scatters of stif_dec_x3_bwd use atomics, unless ``set_deterministic`` is on), and each MLP is one autograd node over stif_siren_fwd (which saves
   the sine layers' pre-activations) and stif_siren_bwd (fp32 MFMA, deterministic weight gradients).  ``LunaTokis`` holds
   the reference's 442 keys (the eight of the unused upsampling layers never receive a gradient) and takes an optimiser
   step through ``optimize_step`` with ``TimesLoss(CharbonnierLoss())``.  The decoder is fp32 in both ``mfma`` modes.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from collections import Counter, defaultdict
 
@@ -64,6 +65,36 @@ from torch.optim.lr_scheduler import LRScheduler
 
 from . import _lib as L
 from . import ops
+
+_DETERMINISTIC = False
+
+
+def set_deterministic(enabled: bool) -> None:
+    """Reproducible backward passes for the whole model: with True, the three order-dependent sums of training -- g_in
+    of the deformable conv (``DCN_sep``) and g_hrfeat / g_feat of the decoder's warped gather -- are ordered segment
+    sums (ops.dcn_bwd / ops.dec_x3_bwd with ``deterministic=True``) in place of fp32 atomics, so
+    that two steps from the same state on the same batch give the same bytes.  Every other kernel adds in a fixed
+    order either way.  The backward nodes read the switch when they run.  Off by default, and
+    ``torch.use_deterministic_algorithms`` is deliberately not consulted: turning that flag on elsewhere must not
+    change what these modules compute or cost."""
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(enabled)
+
+
+def is_deterministic() -> bool:
+    return _DETERMINISTIC
+
+
+@contextlib.contextmanager
+def deterministic(enabled: bool = True):
+    """``with train.deterministic():`` -- set_deterministic(enabled) for the block (the backward must run inside
+    it), then the previous state again; nests."""
+    previous = is_deterministic()
+    set_deterministic(enabled)
+    try:
+        yield
+    finally:
+        set_deterministic(previous)
 
 
 class CharbonnierLoss(nn.Module):
@@ -616,7 +647,8 @@ class _DCNSepFn(torch.autograd.Function):
         need = (need_in, need_fea or need_omw or need_omb, need_w or need_b)
         g_in = g_fea = g_w = g_b = g_omw = g_omb = None
         if any(need):
-            g_in, g_om, g_w, g_b = ops.dcn_bwd(xh, offmask, weight, g, out=out, epi=_EPI[ctx.act], need=need)
+            g_in, g_om, g_w, g_b = ops.dcn_bwd(xh, offmask, weight, g, out=out, epi=_EPI[ctx.act], need=need,
+                                               deterministic=_DETERMINISTIC)
         if need_in:
             g_in = g_in.permute(0, 3, 1, 2)
         if need_omw or need_omb:
@@ -1140,7 +1172,7 @@ class _DecX3Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_x3):
         hr, fl = ctx.saved_tensors
-        g_flow, g_hr, g_lat = ops.dec_x3_bwd(ctx.geom, hr, fl, g_x3.contiguous())
+        g_flow, g_hr, g_lat = ops.dec_x3_bwd(ctx.geom, hr, fl, g_x3.contiguous(), deterministic=_DETERMINISTIC)
         need = ctx.needs_input_grad
         return g_hr if need[0] else None, g_flow if need[1] else None, g_lat if need[2] else None, None
 

@@ -80,16 +80,22 @@ def bench_kernels(a):
     hr, flow = torch.randn(N, 64, device="cuda") * 0.1, torch.randn(N, 4, device="cuda")
     x = {k: torch.empty(N, w, device="cuda") for k, w in (("x1", 208), ("x2", 264), ("x3", 528))}
     gx = {k: torch.randn(N, w, device="cuda") for k, w in (("x1", 208), ("x2", 264), ("x3", 528))}
-    r = timed({"x1_fwd": lambda: ops.dec_x1_fwd(geom, x["x1"]), "x1_bwd": lambda: ops.dec_x1_bwd(geom, gx["x1"]),
-               "x2_fwd": lambda: ops.dec_x2_fwd(geom, hr, x["x2"]), "x2_bwd": lambda: ops.dec_x2_bwd(geom, gx["x2"]),
-               "x3_fwd": lambda: ops.dec_x3_fwd(geom, hr, flow, x["x3"]),
-               "x3_bwd": lambda: ops.dec_x3_bwd(geom, hr, flow, gx["x3"])}, a.rounds, a.warmup)
+    r = {"x1_fwd": lambda: ops.dec_x1_fwd(geom, x["x1"]), "x1_bwd": lambda: ops.dec_x1_bwd(geom, gx["x1"]),
+         "x2_fwd": lambda: ops.dec_x2_fwd(geom, hr, x["x2"]), "x2_bwd": lambda: ops.dec_x2_bwd(geom, gx["x2"]),
+         "x3_fwd": lambda: ops.dec_x3_fwd(geom, hr, flow, x["x3"]),
+         "x3_bwd": lambda: ops.dec_x3_bwd(geom, hr, flow, gx["x3"])}
+    if a.deterministic:   # the ordered adjoint, alternated with the atomic one
+        r["x3_bwd deterministic"] = lambda: ops.dec_x3_bwd(geom, hr, flow, gx["x3"], deterministic=True)
+    r = timed(r, a.rounds, a.warmup)
     lr = lat.numel()
     for k, nbytes in (("x1_fwd", 4.0 * (N * 208 + lr)), ("x1_bwd", 4.0 * (N * 192 + lr)),
                       ("x2_fwd", 4.0 * (N * (264 + 64) + lr)), ("x2_bwd", 4.0 * (N * (256 + 64) + lr)),
                       ("x3_fwd", 4.0 * (N * (528 + 64 + 4) + lr)), ("x3_bwd", 4.0 * (N * (528 + 2 * 64 + 8) + 2 * lr))):
         m = show(f"(a) dec_{k}", r[k])
         print(" " * 60 + rate(nbytes, m) + " (unique bytes; gathers re-read through the caches)")
+    if a.deterministic:
+        m = show("(a) dec_x3_bwd deterministic (contrib, 2 sorts, 2 segsums)", r["x3_bwd deterministic"])
+        print(" " * 60 + f"deterministic / atomic medians = {m / statistics.median(r['x3_bwd']):.2f}x")
     for net, (cin, hidden, cout) in NETS.items():
         mod = T.Siren(cin, hidden, cout).cuda()
         ps = [p.detach() for p in mod._params()]
@@ -168,8 +174,18 @@ def bench_decoder(a):
     with torch.no_grad():
         d = (dec(feat, inp, [0.5], (HH, WW))[0] - torch_decoder(P, feat, inp, 0.5, HH, WW)).abs().max()
     print(f"(b) max |engine - torch| of the forward: {float(d):.2e}")
-    r = timed({"engine": engine, "torch": autograd}, a.rounds, a.warmup)
+    def engine_det():
+        with T.deterministic():
+            engine()
+
+    fns = {"engine": engine, "torch": autograd}
+    if a.deterministic:
+        fns["engine deterministic"] = engine_det
+    r = timed(fns, a.rounds, a.warmup)
     me = show(f"(b) train.Decoder forward + backward, {B}x{HH}x{WW}", r["engine"])
+    if a.deterministic:
+        md = show("(b) the same under train.deterministic()", r["engine deterministic"])
+        print(" " * 60 + f"deterministic / atomic medians = {md / me:.2f}x")
     mt = show("(b) the same decoder by torch autograd (fp32)", r["torch"])
     print(" " * 60 + f"torch / engine = {mt / me:.2f}")
     torch.cuda.reset_peak_memory_stats()
@@ -213,9 +229,11 @@ def label(kind):
         return f"stif_{kind[0]} {kind[1]} -> {kind[2]}"
     if kind[0].startswith("dec_x"):
         return "stif_" + kind[0]
+    if kind[0] == "segsum":
+        return f"stif_segsum C {kind[1]}"
     return "gen_feat: " + {"wino": "stif_conv3x3_wino", "conv": "stif_conv2d_nhwc", "wgrad": "stif_conv3x3_wgrad",
                            "wgrad_cat": "stif_conv3x3_wgrad_cat", "dcn": "stif_dcn_nhwc",
-                           "dcn_bwd": "stif_dcn_bwd_nhwc"}.get(kind[0], kind[0])
+                           "dcn_bwd": "stif_dcn_bwd_nhwc", "dcn_bwd_contrib": "stif_dcn_bwd_contrib"}.get(kind[0], kind[0])
 
 
 def bench_step(a):
@@ -237,8 +255,18 @@ def bench_step(a):
             p.grad = None
         crit(net(x, [0.5], (HH, WW)), gt).backward()
 
-    r = timed({"step": step}, a.rounds, a.warmup)
-    show(f"(c) train.LunaTokis f16x3 forward + loss + backward, {B}x2x3x{H}x{W} -> {HH}x{WW}", r["step"])
+    def det_step():
+        with T.deterministic():
+            step()
+
+    fns = {"step": step}
+    if a.deterministic:
+        fns["deterministic"] = det_step
+    r = timed(fns, a.rounds, a.warmup)
+    ms = show(f"(c) train.LunaTokis f16x3 forward + loss + backward, {B}x2x3x{H}x{W} -> {HH}x{WW}", r["step"])
+    if a.deterministic:
+        md = show("(c) the same step under train.deterministic()", r["deterministic"])
+        print(" " * 60 + f"deterministic / atomic medians = {md / ms:.2f}x")
     print(f"(c) range_status {net.range_status()}")
     per, whole = defaultdict(list), []
     for _ in range(max(3, a.rounds // 3)):
@@ -247,7 +275,7 @@ def bench_step(a):
         ops.TRACE = tr
         try:
             e0.record()
-            step()
+            (det_step if a.deterministic else step)()
             e1.record()
         finally:
             ops.TRACE = None
@@ -260,7 +288,7 @@ def bench_step(a):
         for k, us in by.items():
             per[k].append(us)
     wm = statistics.median(whole)
-    print(f"(c) split of one traced step (events around every call): {wm:9.1f} us", flush=True)
+    print(f"(c) split of one traced {'deterministic ' if a.deterministic else ''}step (events around every call): {wm:9.1f} us", flush=True)
     for k, us in sorted(per.items(), key=lambda kv: -statistics.median(kv[1])):
         m = statistics.median(us)
         print(f"      {k:56s} {m:9.1f} us  {100 * m / wm:5.1f} %", flush=True)
@@ -272,6 +300,9 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scale", type=int, default=2, help="HR size = scale x 128 (the reference trains at 1..4)")
     ap.add_argument("--only", choices=["kernels", "decoder", "step"])
+    ap.add_argument("--deterministic", action="store_true",
+                    help="add the ordered-sum paths (ops.dec_x3_bwd(deterministic=True), train.deterministic()) beside "
+                         "the atomic ones in every section; the traced step of (c) is then the deterministic one")
     a = ap.parse_args()
     print(f"device: {torch.cuda.get_device_name(0)}, rounds {a.rounds}, warm-up {a.warmup}, scale x{a.scale}")
     for name, fn in (("kernels", bench_kernels), ("decoder", bench_decoder), ("step", bench_step)):

@@ -140,7 +140,8 @@ def label(kind):
     return {"wgrad": "stif_conv3x3_wgrad", "wgrad_s2": "stif_conv3x3s2_wgrad", "dgrad_s2": "stif_conv3x3s2_dgrad",
             "up2": "stif_upsample2x_nhwc", "up2_bwd": "stif_upsample2x_bwd_nhwc", "dcn": "stif_dcn_nhwc",
             "dcn_bwd": "stif_dcn_bwd_nhwc", "dcn_offmask": "stif_dcn_offmask_nhwc",
-            "lstm_gates": "stif_lstm_gates_nhwc", "lstm_gates_bwd": "stif_lstm_gates_bwd_nhwc"}.get(kind[0], kind[0])
+            "lstm_gates": "stif_lstm_gates_nhwc", "lstm_gates_bwd": "stif_lstm_gates_bwd_nhwc",
+            "dcn_bwd_contrib": "stif_dcn_bwd_contrib", "segsum": "stif_segsum"}.get(kind[0], kind[0])
 
 
 def bench_step(a):
@@ -164,8 +165,15 @@ def bench_step(a):
         x.grad = None
         net(x).backward(gout)
 
-    r = timed({k: (lambda net=net: step(net)) for k, net in nets.items()}, a.rounds, a.warmup)
-    for k in nets:
+    def det_step(net):
+        with T.deterministic():
+            step(net)
+
+    fns = {k: (lambda net=net: step(net)) for k, net in nets.items()}
+    if a.deterministic:   # the same nets under train.deterministic(), alternated with the atomic lines
+        fns.update({k + " deterministic": (lambda net=net: det_step(net)) for k, net in nets.items()})
+    r = timed(fns, a.rounds, a.warmup)
+    for k in fns:
         show(f"(c) BiDeformableConvLSTM {k} forward + backward, 6x3x128x128", r[k])
     assert nets["f16x3"].range_status() == 0
     per = defaultdict(list)
@@ -176,7 +184,7 @@ def bench_step(a):
         ops.TRACE = tr
         try:
             e0.record()
-            step(nets["f16x3"])
+            (det_step if a.deterministic else step)(nets["f16x3"])
             e1.record()
         finally:
             ops.TRACE = None
@@ -189,7 +197,7 @@ def bench_step(a):
         for k, us in by.items():
             per[k].append(us)
     wm = statistics.median(whole)
-    print(f"(c) split of one traced f16x3 step (events around every call): {wm:9.1f} us", flush=True)
+    print(f"(c) split of one traced f16x3 {'deterministic ' if a.deterministic else ''}step (events around every call): {wm:9.1f} us", flush=True)
     for k, us in sorted(per.items(), key=lambda kv: -statistics.median(kv[1])):
         m = statistics.median(us)
         print(f"      {k:56s} {m:9.1f} us  {100 * m / wm:5.1f} %", flush=True)
@@ -200,6 +208,9 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=["gates", "wgrad", "step"])
+    ap.add_argument("--deterministic", action="store_true",
+                    help="add the steps under train.deterministic() beside the atomic ones in (c); the traced step is "
+                         "then the deterministic one")
     a = ap.parse_args()
     print(f"device: {torch.cuda.get_device_name(0)}, rounds {a.rounds}, warm-up {a.warmup}")
     for name, fn in (("gates", bench_gates), ("wgrad", bench_wgrad), ("step", bench_step)):

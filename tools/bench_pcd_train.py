@@ -138,7 +138,8 @@ def label(kind):
         return f"stif_conv3x3_wgrad_cat {kind[1:]}"
     return {"wgrad": "stif_conv3x3_wgrad", "up2": "stif_upsample2x_nhwc", "up2_bwd": "stif_upsample2x_bwd_nhwc",
             "dcn_v2_fwd": "stif_dcn_v2_forward", "dcn_v2_bwd": "stif_dcn_v2_backward", "dcn": "stif_dcn_nhwc",
-            "dcn_bwd": "stif_dcn_bwd_nhwc", "dcn_offmask": "stif_dcn_offmask_nhwc"}.get(kind[0], kind[0])
+            "dcn_bwd": "stif_dcn_bwd_nhwc", "dcn_offmask": "stif_dcn_offmask_nhwc",
+            "dcn_bwd_contrib": "stif_dcn_bwd_contrib", "segsum": "stif_segsum"}.get(kind[0], kind[0])
 
 
 DCN_GEOM = (3, 3, 1, 1, 1, 1, 1, 1, 8)
@@ -168,12 +169,16 @@ def bench_dcn(a):
         x, go = xh.permute(0, 3, 1, 2).contiguous(), gh.permute(0, 3, 1, 2).contiguous()
         offset = om[..., :144].permute(0, 3, 1, 2).contiguous()
         mask = torch.sigmoid(om[..., 144:216]).permute(0, 3, 1, 2).contiguous()
-        r = timed({"new": lambda: ops.dcn_bwd(xh, ops.dcn_offmask(om), w, gh), "old": old_path,
-                   "bwd": lambda: ops.dcn_bwd(xh, offmask, w, gh),
-                   "v2": lambda: ops.dcn_v2_backward(x, w, b, offset, mask, go, *DCN_GEOM),
-                   "data": lambda: ops.dcn_bwd(xh, offmask, w, gh, need=(True, True, False)),
-                   "weight": lambda: ops.dcn_bwd(xh, offmask, w, gh, need=(False, False, True)),
-                   "offmask": lambda: ops.dcn_offmask(om)}, a.rounds, a.warmup)
+        r = {"new": lambda: ops.dcn_bwd(xh, ops.dcn_offmask(om), w, gh), "old": old_path,
+             "bwd": lambda: ops.dcn_bwd(xh, offmask, w, gh),
+             "v2": lambda: ops.dcn_v2_backward(x, w, b, offset, mask, go, *DCN_GEOM),
+             "data": lambda: ops.dcn_bwd(xh, offmask, w, gh, need=(True, True, False)),
+             "weight": lambda: ops.dcn_bwd(xh, offmask, w, gh, need=(False, False, True)),
+             "offmask": lambda: ops.dcn_offmask(om)}
+        if a.deterministic:   # the ordered g_in, alternated with the atomic lines above
+            r["det"] = lambda: ops.dcn_bwd(xh, offmask, w, gh, deterministic=True)
+            r["det-data"] = lambda: ops.dcn_bwd(xh, offmask, w, gh, need=(True, True, False), deterministic=True)
+        r = timed(r, a.rounds, a.warmup)
         flop = 2.0 * 64 * 576 * n * H * W
         show(f"(d) {name} dcn_offmask + dcn_bwd", r["new"])
         show(f"(d) {name} dcn_v2_backward + copies, sigmoid, g_om", r["old"])
@@ -185,6 +190,11 @@ def bench_dcn(a):
         m = show(f"(d) {name} dcn_bwd, g_w + g_b only", r["weight"])
         print(" " * 56 + peak(flop, m))
         show(f"(d) {name} dcn_offmask", r["offmask"])
+        if a.deterministic:
+            md = show(f"(d) {name} dcn_bwd alone, deterministic", r["det"])
+            mdd = show(f"(d) {name} dcn_bwd, g_in + g_om only, deterministic", r["det-data"])
+            print(f"      deterministic / atomic medians: dcn_bwd {md / statistics.median(r['bwd']):.2f}x, "
+                  f"g_in + g_om only {mdd / statistics.median(r['data']):.2f}x", flush=True)
         ok = min(r["old"]) > max(r["new"])
         print(f"      ranges {'do not overlap: new max < old min' if ok else 'OVERLAP'}; "
               f"old / new medians = {statistics.median(r['old']) / statistics.median(r['new']):.1f}x", flush=True)
@@ -215,8 +225,15 @@ def bench_step(a):
             t.grad = None
         net(fea1, fea2).backward(gout)
 
-    r = timed({k: (lambda net=net: step(net)) for k, net in nets.items()}, a.rounds, a.warmup)
-    for k in nets:
+    def det_step(net):
+        with T.deterministic():
+            step(net)
+
+    fns = {k: (lambda net=net: step(net)) for k, net in nets.items()}
+    if a.deterministic:   # the same nets under train.deterministic(), alternated with the atomic lines
+        fns.update({k + " deterministic": (lambda net=net: det_step(net)) for k, net in nets.items()})
+    r = timed(fns, a.rounds, a.warmup)
+    for k in fns:
         show(f"(c) PCD_Align {k} forward + backward, 6 x 128 x 128", r[k])
     assert nets["f16x3"].range_status() == 0
     per = defaultdict(list)
@@ -227,7 +244,7 @@ def bench_step(a):
         ops.TRACE = tr
         try:
             e0.record()
-            step(nets["f16x3"])
+            (det_step if a.deterministic else step)(nets["f16x3"])
             e1.record()
         finally:
             ops.TRACE = None
@@ -240,7 +257,7 @@ def bench_step(a):
         for k, us in by.items():
             per[k].append(us)
     wm = statistics.median(whole)
-    print(f"(c) split of one traced f16x3 step (events around every call): {wm:9.1f} us", flush=True)
+    print(f"(c) split of one traced f16x3 {'deterministic ' if a.deterministic else ''}step (events around every call): {wm:9.1f} us", flush=True)
     for k, us in sorted(per.items(), key=lambda kv: -statistics.median(kv[1])):
         m = statistics.median(us)
         print(f"      {k:56s} {m:9.1f} us  {100 * m / wm:5.1f} %", flush=True)
@@ -251,6 +268,9 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=["wgrad", "upsample", "step", "dcn"])
+    ap.add_argument("--deterministic", action="store_true",
+                    help="add the ordered-sum paths (train.deterministic(), ops.dcn_bwd(deterministic=True)) beside "
+                         "the atomic ones in (c) and (d); the traced step of (c) is then the deterministic one")
     a = ap.parse_args()
     print(f"device: {torch.cuda.get_device_name(0)}, rounds {a.rounds}, warm-up {a.warmup}")
     for name, fn in (("wgrad", bench_wgrad), ("upsample", bench_upsample), ("step", bench_step), ("dcn", bench_dcn)):
