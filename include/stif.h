@@ -619,6 +619,22 @@ int stif_resize_frames(const unsigned char* bgr, float* out_rgb_nchw, int nf, in
 /* (clamp(x, 0, 1) * 255).astype(uint8) of NCHW RGB frames [n][3][H][W] -> HWC uint8 [n][H][W][3]. */
 int stif_frames_to_u8(const float* nchw, unsigned char* hwc, int n, int H, int W, void* stream);
 
+/* ---- training batches (data/__init__.py:124-154 collate_function2, data/util.py:126-140 augment_a2) ---- */
+
+/* n square crops of uint8 BGR HWC frames -> float RGB planes out [n][3][o][o]:
+ *   imresize_np(crop, scale, True).astype(float32) / 255, then flip W, flip H, transpose H/W (in that order, as
+ *   selected by flags), BGR -> RGB, HWC -> CHW.
+ * Crop k is the G x G square whose top-left pixel is src + crop_off[k] (an element offset), its rows row_stride[k]
+ * elements apart: a crop of a larger device-resident frame is read in place, a packed buffer of crops has
+ * row_stride = 3 G.  crop_off and row_stride are device arrays.  w [o][P], idx [o] (first symmetric-padded index) and
+ * s0 (leading padding) come from calculate_weights_indices for (G -> o) (stif_amd.video.resize_tables); H and W share
+ * them.  The padding mirrors at the crop's edge and no byte outside a crop is read.  Before the augmentation the
+ * values are bit-identical to stif_resize_frames of the crop (same fmaf order).  One launch, no workspace, no atomics.
+ * STIF_E_INVALID before any launch: a null pointer; n, G, o or P < 1; s0 > G; unknown flag bits. */
+enum { STIF_BATCH_HFLIP = 1, STIF_BATCH_VFLIP = 2, STIF_BATCH_ROT90 = 4 };
+int stif_build_batch(const unsigned char* src, const long long* crop_off, const long long* row_stride, float* out,
+                     int n, int G, int o, const float* w, const int* idx, int P, int s0, unsigned flags, void* stream);
+
 /* ---- host-side weight packing (pure CPU, callable without a GPU) ---- */
 enum { STIF_PACK_PLAIN = 0, STIF_PACK_OFFMASK = 1, STIF_PACK_LSTM = 2, STIF_PACK_WINO = 3, STIF_PACK_WINO_OFFMASK = 4,
        STIF_PACK_WINO_LSTM = 5, STIF_PACK_DCNSEP = 6, STIF_PACK_DCNPAIR = 7 };

@@ -17,6 +17,8 @@ Layout:
   serving.py  option files, define_G / load_network / VideoSRModel (checkpoint drop-in)
   train.py    Charbonnier loss, the two restart LR schedules, Adam set-up (training drop-ins); trainable
               Conv3x3 / ResidualBlock_noBN / make_trunk on the HIP conv forward, data- and weight-gradient kernels
+  data.py     training batches from frame folders: window index, the reference's collate draws, the on-device batch
+              builder (stif_build_batch) and its numpy restatement, the prefetching loader (tools/train.py is the loop)
 """
 from . import weights  # noqa: F401
 from . import coords  # noqa: F401
@@ -24,7 +26,7 @@ from . import coords  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent parts load lazily so that weight/coords utilities work without torch/GPU
-    if name in ("ops", "packing", "model", "video", "parallel", "_lib", "serving", "train", "metrics", "y4m"):
+    if name in ("ops", "packing", "model", "video", "parallel", "_lib", "serving", "train", "metrics", "y4m", "data"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     if name == "LunaTokis":

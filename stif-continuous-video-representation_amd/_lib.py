@@ -175,6 +175,7 @@ class MetricArgs(C.Structure):
     ]
 
 
+BATCH_HFLIP, BATCH_VFLIP, BATCH_ROT90 = 1, 2, 4   # stif_build_batch flags (stif.h STIF_BATCH_*)
 YUV_BT601, YUV_BT709 = 0, 1   # stif_yuv_format.matrix (stif.h STIF_YUV_*)
 
 
@@ -282,6 +283,7 @@ EXPORTS = {
     "stif_resize_frames": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int,
                                                                  _P]),
     "stif_frames_to_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "stif_build_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_uint, _P]),
     "stif_pack_dec_proj_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P]),
     "stif_conv_weight_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "stif_conv_bias_floats": (C.c_size_t, [C.c_int, C.c_int]),

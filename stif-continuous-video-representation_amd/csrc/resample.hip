@@ -242,3 +242,136 @@ extern "C" int stif_frames_to_u8(const float* nchw, unsigned char* hwc, int n, i
   hipLaunchKernelGGL(k_to_u8, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nchw, hwc, n, H, W);
   return stif_check_launch("stif_frames_to_u8");
 }
+
+// ---------------------------------------------------------------- training batches
+// data/__init__.py:124-154 (collate_function2) + data/util.py:126-140 (augment_a2) for one group of frames: n square
+// G x G crops of uint8 BGR HWC frames -> imresize_np(crop, scale, True).astype(float32) / 255, flip W, flip H,
+// transpose H/W, BGR -> RGB, HWC -> CHW, as float [n][3][o][o].  The crop is square, so H and W share one table.
+namespace {
+
+constexpr int BB_LDS_BYTES = 48 * 1024;
+enum { BB_HFLIP = 1, BB_VFLIP = 2, BB_ROT90 = 4 };
+
+// symmetric padding mirrors at the crop's edge (the reference resizes the crop, not the frame); the clamp keeps a
+// table that does not belong to (G, s0) inside the crop as well: no byte outside a crop is ever read
+STIF_DEV int crop_src(int j, int G, int s0) { return min(max(sym_src(j, G, s0), 0), G - 1); }
+
+// One workgroup = a T x T tile of one crop's output before augmentation, T * T * 3 values over 256 threads.
+//   1. the uint8 window the tile's taps cover (rows and columns of the symmetric-padded crop, mirrors materialised)
+//      is staged in LDS, each row read as consecutive bytes;
+//   2. H pass: hbuf[i][column][c] = sum over q ascending of w[y][q] * window row -- fp32, LDS only;
+//   3. W pass over hbuf, p ascending, / 255.f: the fmaf order of k_resize_in, so the value of pixel (y, x) is
+//      bit-identical to stif_resize_frames of the crop;
+//   4. the store applies the augmentation and the channel order: pixel (y, x) of BGR channel c goes to plane 2 - c,
+//      row / column (yf, xf), or (xf, yf) under rot90, with xf = o - 1 - x under hflip and yf = o - 1 - y under
+//      vflip.  The thread index runs fastest along the OUTPUT row (x without rot90, y with it), so a wave's stores
+//      are runs of consecutive floats either way.
+// `cap` is the window side the LDS was sized for (host: from G / o and P).  A tile whose table spans more than that
+// (a hand-made table) takes the direct path: the same sums straight from global memory.
+__global__ __launch_bounds__(256) void k_build_batch(const unsigned char* __restrict__ src,
+                                                     const long long* __restrict__ crop_off,
+                                                     const long long* __restrict__ row_stride,
+                                                     float* __restrict__ out, int G, int o,
+                                                     const float* __restrict__ w, const int* __restrict__ idx, int P,
+                                                     int s0, unsigned flags, int T, int cap) {
+  extern __shared__ __align__(16) unsigned char bb_lds[];
+  float* hbuf = reinterpret_cast<float*>(bb_lds);                          // [T][cap * 3]
+  unsigned char* win = bb_lds + (size_t)T * cap * 3 * sizeof(float);       // [cap][cap * 3]
+  const int f = blockIdx.z, tid = threadIdx.x;
+  const int y0 = blockIdx.y * T, x0 = blockIdx.x * T;
+  const int ny = min(T, o - y0), nx = min(T, o - x0);
+  const bool rot = flags & BB_ROT90;
+  const unsigned char* img = src + crop_off[f];
+  const long long pitch = row_stride[f];
+  const int pitch_l = cap * 3;
+
+  long long rlo = idx[y0], rhi = rlo + P, clo = idx[x0], chi = clo + P;
+  for (int i = 1; i < ny; ++i) {
+    const long long v = idx[y0 + i];
+    rlo = v < rlo ? v : rlo;
+    rhi = v + P > rhi ? v + P : rhi;
+  }
+  for (int i = 1; i < nx; ++i) {
+    const long long v = idx[x0 + i];
+    clo = v < clo ? v : clo;
+    chi = v + P > chi ? v + P : chi;
+  }
+  const bool staged = rhi - rlo <= cap && chi - clo <= cap;     // uniform over the workgroup
+  const int rspan = staged ? (int)(rhi - rlo) : 0, cspan3 = staged ? 3 * (int)(chi - clo) : 0;
+
+  if (staged) {
+    for (int r = tid >> 6; r < rspan; r += 4) {
+      const unsigned char* row = img + (long long)crop_src((int)rlo + r, G, s0) * pitch;
+      for (int t = tid & 63; t < cspan3; t += 64) {
+        const int j = t / 3;
+        win[r * pitch_l + t] = row[crop_src((int)clo + j, G, s0) * 3 + (t - 3 * j)];
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < ny * cspan3; e += 256) {
+      const int i = e / cspan3, t = e - i * cspan3;
+      const float* wy = w + (size_t)(y0 + i) * P;
+      const unsigned char* col = win + (idx[y0 + i] - (int)rlo) * pitch_l + t;
+      float acc = 0.f;
+      for (int q = 0; q < P; ++q) acc = fmaf(wy[q], (float)col[q * pitch_l], acc);
+      hbuf[i * pitch_l + t] = acc;
+    }
+    __syncthreads();
+  }
+
+  const int nb = rot ? ny : nx, na = rot ? nx : ny;      // b runs along the output row
+  for (int e = tid; e < 3 * na * nb; e += 256) {
+    const int c = e / (na * nb), r2 = e - c * na * nb;
+    const int a = r2 / nb, b = r2 - a * nb;
+    const int i = rot ? b : a, j = rot ? a : b;
+    const int y = y0 + i, x = x0 + j;
+    const float* wx = w + (size_t)x * P;
+    float acc = 0.f;
+    if (staged) {
+      const float* h = hbuf + i * pitch_l + (idx[x] - (int)clo) * 3 + c;
+      for (int p = 0; p < P; ++p) acc = fmaf(wx[p], h[3 * p], acc);
+    } else {
+      const float* wy = w + (size_t)y * P;
+      for (int p = 0; p < P; ++p) {
+        const unsigned char* px = img + crop_src(idx[x] + p, G, s0) * 3 + c;
+        float col = 0.f;
+        for (int q = 0; q < P; ++q) col = fmaf(wy[q], (float)px[(long long)crop_src(idx[y] + q, G, s0) * pitch], col);
+        acc = fmaf(wx[p], col, acc);
+      }
+    }
+    const int xf = (flags & BB_HFLIP) ? o - 1 - x : x, yf = (flags & BB_VFLIP) ? o - 1 - y : y;
+    const int Y = rot ? xf : yf, X = rot ? yf : xf;
+    out[(((size_t)f * 3 + (2 - c)) * o + Y) * o + X] = acc / 255.f;
+  }
+}
+
+}  // namespace
+
+extern "C" int stif_build_batch(const unsigned char* src, const long long* crop_off, const long long* row_stride,
+                                float* out, int n, int G, int o, const float* w, const int* idx, int P, int s0,
+                                unsigned flags, void* stream) {
+  if (!src || !crop_off || !row_stride || !out || !w || !idx || n < 1 || G < 1 || o < 1 || P < 1 || s0 < 0 || s0 > G ||
+      (flags & ~7u))
+    return stif_fail(STIF_E_INVALID, "stif_build_batch: bad arguments");
+  if (n > 65535 || G > (1 << 24) || P > (1 << 16)) return stif_fail(STIF_E_INVALID, "stif_build_batch: too large for the grid");
+  // the largest tile whose window fits the LDS budget: T outputs span at most (T - 1) / scale + P + 1 padded
+  // pixels per axis, and 1 / scale < G / (o - 1) because o = ceil(G scale)
+  int T = 32, cap = 0;
+  size_t lds = 0;
+  for (;; T >>= 1) {
+    if (T > 1 && T / 2 >= o) continue;
+    const long long c = (o > 1 ? ((long long)(T - 1) * G + o - 2) / (o - 1) : 0) + P + 1;
+    const long long bytes = (long long)T * c * 3 * (long long)sizeof(float) + c * c * 3;
+    if (bytes <= BB_LDS_BYTES) {
+      cap = (int)c;
+      lds = (size_t)bytes;
+      break;
+    }
+    if (T == 1) break;      // no window fits (a very long kernel): every tile takes the direct path, cap = 0
+  }
+  const unsigned tiles = (unsigned)((o + T - 1) / T);
+  if (tiles > 65535) return stif_fail(STIF_E_INVALID, "stif_build_batch: too large for the grid");
+  hipLaunchKernelGGL(k_build_batch, dim3(tiles, tiles, (unsigned)n), dim3(256), lds, (hipStream_t)stream, src, crop_off,
+                     row_stride, out, G, o, w, idx, P, s0, flags, T, cap);
+  return stif_check_launch("stif_build_batch");
+}
