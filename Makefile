@@ -14,7 +14,7 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -I$(PKG)/csrc -
 # launch (profiles/r06_nopk_ab.log).
 # Device-only feature: the host pass prints "not a recognized feature for this target (ignoring feature)".
 NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
-NOPK_SRC := wino decoder conv conv_bwd resample dcnsep dcn dcn_v2 dcn_bwd metrics yuv scene lstm conv1x1_bwd siren_train dec_train segsum
+NOPK_SRC := wino decoder conv conv_bwd resample dcnsep dcn dcn_v2 dcn_bwd metrics yuv scene lstm conv1x1_bwd siren_train dec_train segsum grad_arena
 
 all: $(LIB)
 

@@ -469,6 +469,37 @@ int stif_dec_x3_bwd_contrib(const stif_dec_train_geom* g, const float* hrfeat, c
                             float* g_flow, float* w_hr, long long* words_hr, float* w_lr, long long* words_lr,
                             void* stream);
 
+/* ---- Data-parallel training: the gradient arena and the rank-ordered sum.
+ *
+ * stif_grad_pack gathers nseg fp32 tensors into one arena in a single launch.  segs_dev is a device table of nseg
+ * stif_grad_seg in ascending dst order: segment s copies n floats from src (4-byte aligned; 16-byte loads where the
+ * address allows, dword loads otherwise) to arena + dst, dst a multiple of 4 floats.  The gap after a segment up to the
+ * next multiple of 4 and the arena's tail -- from the end of the last segment, rounded up to 4, to arena_floats -- are
+ * written as +0.0f; floats between two segments beyond that gap are left as they are.  Stores are 16 bytes.
+ * Workgroups walk chunks of STIF_GRAD_CHUNK floats: a segment has ceil(n / STIF_GRAD_CHUNK) chunks (none for n = 0),
+ * a chunk never spans segments, and chunk0 is the prefix table, the number of chunks of the segments before this one.
+ * The table's contents are the caller's responsibility; the kernel still bounds every access to the arena by
+ * arena_floats, and its loops by nseg and arena_floats.  STIF_E_INVALID before the launch: a null pointer, nseg < 1 or
+ * above STIF_GRAD_MAX_SEGS, an arena that is not 16-byte or a table that is not 8-byte aligned, arena_floats < 4, not
+ * a multiple of 4 or above 2^31 - 1. */
+#define STIF_GRAD_CHUNK 1024
+#define STIF_GRAD_MAX_SEGS (1 << 20)
+typedef struct {
+  const float* src;
+  long long dst;       /* offset in the arena, in floats */
+  long long n;         /* floats */
+  long long chunk0;    /* chunks of the segments before this one */
+} stif_grad_seg;
+int stif_grad_pack(const stif_grad_seg* segs_dev, int nseg, float* arena, long long arena_floats, void* stream);
+
+/* dst[i] = ((slab[0][i] + slab[1][i]) + ...) + slab[R - 1][i] for i < n, slab[r] = slab + r * row_floats: plain fp32
+ * adds, rounded to nearest, in rank order; R = 1 copies.  No atomics and nothing to contract: repeated calls give
+ * identical bits, whatever the grid.  STIF_E_INVALID before the launch: a null pointer, R outside 1 ..
+ * STIF_RANK_SUM_MAX_RANKS, n < 4 or not a multiple of 4, n > row_floats, row_floats not a multiple of 4, n or
+ * row_floats above 2^31 - 1, slab or dst not 16-byte aligned, dst overlapping the R rows read. */
+#define STIF_RANK_SUM_MAX_RANKS 64
+int stif_rank_sum(const float* slab, long long row_floats, int R, float* dst, long long n, void* stream);
+
 /* The offset / mask conv's output as the deformable conv reads it: om NHWC [n][H][W][256] in the reference's row order
  * (channel g*18 + 2k (+1) the h (w) offset of group g, tap k; 144 + g*9 + k the mask logit; 216..255 never read) ->
  * offmask NHWC [n][H][W][216] = [group][tap][dy, dx, sigmoid(logit)].  Offsets are copied bit for bit; the sigmoid is

@@ -176,6 +176,8 @@ class MetricArgs(C.Structure):
 
 
 BATCH_HFLIP, BATCH_VFLIP, BATCH_ROT90 = 1, 2, 4   # stif_build_batch flags (stif.h STIF_BATCH_*)
+GRAD_CHUNK, GRAD_MAX_SEGS = 1024, 1 << 20         # stif.h STIF_GRAD_CHUNK, STIF_GRAD_MAX_SEGS
+RANK_SUM_MAX_RANKS = 64                           # stif.h STIF_RANK_SUM_MAX_RANKS
 YUV_BT601, YUV_BT709 = 0, 1   # stif_yuv_format.matrix (stif.h STIF_YUV_*)
 
 
@@ -240,6 +242,8 @@ EXPORTS = {
     "stif_dec_x3_bwd_contrib": (C.c_int, [C.POINTER(DecTrainGeom)] + [_P] * 9),
     "stif_segsum": (C.c_int, [_P, _P, C.c_longlong, C.c_int, C.c_int, _P, _P, _P, C.c_longlong, C.c_longlong, C.c_int,
                               _P]),
+    "stif_grad_pack": (C.c_int, [_P, C.c_int, _P, C.c_longlong, _P]),
+    "stif_rank_sum": (C.c_int, [_P, C.c_longlong, C.c_int, _P, C.c_longlong, _P]),
     "stif_dcn_offmask_nhwc": (C.c_int, [_P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, _P]),
     "stif_dcn_v2_workspace_size": (C.c_size_t, [C.c_int] * 14),
     "stif_dcn_v2_forward": (C.c_int, [_P] * 6 + [C.c_int] * 14 + [_P, C.c_size_t, _P]),

@@ -394,6 +394,20 @@ def _decode_crop(path, r, c, G, dst):
     dst[...] = rgb[r:r + G, c:c + G, ::-1]
 
 
+def rank_items(batch_size: int, world: int, rank: int):
+    """The items [a, b) of a global batch that ``rank`` of ``world`` trains on: contiguous slices, the first
+    ``batch_size % world`` ranks one item longer.  More ranks than items is refused: a rank with nothing to do would
+    still have to enter every collective."""
+    batch_size, world, rank = int(batch_size), int(world), int(rank)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"rank {rank} of world {world}")
+    if world > batch_size:
+        raise ValueError(f"{world} ranks cannot share a batch of {batch_size}: every rank needs at least one item")
+    base, rem = divmod(batch_size, world)
+    a = rank * base + min(rank, rem)
+    return a, a + base + (1 if rank < rem else 0)
+
+
 class BatchLoader:
     """Training batches built ahead of the loop.  Batch ``i`` (0-based, counted over epochs) is a pure function of
     ``(seed, i)``: epoch ``e = i // (len(index) // batch_size)`` uses the permutation of ``stream_rng(seed, "epoch",
@@ -406,11 +420,20 @@ class BatchLoader:
     batch over behind an event, which the iterating thread's current stream waits on (no host wait).  ``workers`` is
     capped at 16 and never derived from the machine's CPU count; ``workers=0`` builds every batch in the iterating
     thread.  ``device=None`` or "cpu" yields ``build_batch_host`` batches (no GPU needed).  All frames of a batch
-    must share a size: otherwise ValueError names the paths."""
+    must share a size: otherwise ValueError names the paths.
+
+    ``rank`` / ``world`` (data-parallel training): ``batch_size`` stays the global batch and
+    ``plan(i)`` is computed for all of it exactly as with one process -- one ``draw_collate_params``, then every item's
+    ``sample`` in item order, so the collate stream is the same -- but only the items ``rank_items(batch_size, world,
+    rank)`` are decoded, staged and built.  The rank's batch is rows [a, b) of the single-process batch bit for bit
+    (``LQs``, ``GT``, ``time``) with the same ``shape``; every rank decodes at the batch's one scale, and ``per_epoch``
+    stays global."""
 
     def __init__(self, index: ClipIndex, batch_size: int, seed, lq_size: int = LQ_SIZE, workers: int = 4,
-                 prefetch: int = 2, device="cuda", start: int = 0):
+                 prefetch: int = 2, device="cuda", start: int = 0, rank: int = 0, world: int = 1):
         resize_geometry(lq_size, 2.0)
+        self.rank, self.world = int(rank), int(world)
+        self.items = rank_items(batch_size, world, rank) if batch_size >= 1 else (0, 0)
         if batch_size < 1 or len(index) < batch_size:
             raise ValueError(f"{len(index)} windows cannot fill a batch of {batch_size}")
         if workers < 0 or prefetch < 1:
@@ -467,6 +490,8 @@ class BatchLoader:
     def build(self, i: int, pool=None):
         """Batch i on the current stream (or on the host)."""
         paths, times, params = self.plan(i)
+        a, b = self.items
+        paths, times = paths[a:b], times[a:b]
         stage = self._stage(paths, params, pool)
         if self.device is None:
             return build_batch_host(stage.numpy(), params, times)

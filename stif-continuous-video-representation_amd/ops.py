@@ -826,6 +826,92 @@ def segsum(dst: torch.Tensor, src: torch.Tensor, row_stride: int, K: int, col0: 
     return dst
 
 
+class GradTable:
+    """The device table of one ``grad_pack`` layout (stif.h stif_grad_seg): segment i holds ``sizes[i]`` floats at
+    ``offsets[i]``, each offset the previous end rounded up to 4 floats; ``floats`` is the end of the last segment,
+    rounded.  Sizes, offsets and the chunk prefix are fixed; the source pointers are refreshed by ``update`` and
+    uploaded (from pinned memory, on the current stream, nothing read back) only when one of them changed."""
+
+    def __init__(self, sizes, device):
+        self.sizes = tuple(int(s) for s in sizes)
+        if not self.sizes or len(self.sizes) > L.GRAD_MAX_SEGS or min(self.sizes) < 0:
+            raise ValueError(f"grad_pack: 1 .. {L.GRAD_MAX_SEGS} tensors, got {len(self.sizes)}")
+        host = np.zeros((len(self.sizes), 4), np.int64)
+        off = chunk = 0
+        for i, n in enumerate(self.sizes):
+            host[i, 1:] = (off, n, chunk)
+            off += (n + 3) & ~3
+            chunk += -(-n // L.GRAD_CHUNK)
+        self.offsets, self.floats = host[:, 1].tolist(), off
+        self.device = torch.device(device)
+        self.host = torch.from_numpy(host)
+        self.ptrs = self.dev = self._uploaded = None
+        if self.device.type == "cuda":
+            self.host = self.host.pin_memory()
+            self.dev = torch.empty((len(self.sizes), 4), dtype=torch.int64, device=self.device)
+
+    def update(self, tensors):
+        ptrs = [t.data_ptr() for t in tensors]
+        if ptrs == self.ptrs:
+            return
+        if self._uploaded is not None:
+            self._uploaded.synchronize()      # the pinned rows may still be on their way from the last change
+        self.host[:, 0] = torch.tensor(ptrs, dtype=torch.int64)
+        self.dev.copy_(self.host, non_blocking=True)
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record(torch.cuda.current_stream(self.device))
+        self.ptrs = ptrs
+
+
+def grad_pack(tensors: Sequence[torch.Tensor], arena: torch.Tensor, table: Optional[GradTable] = None) -> GradTable:
+    """stif_grad_pack: the contiguous float32 CUDA ``tensors`` (views at any 4-byte offset included) gathered into the
+    1-d float32 ``arena`` in one launch, tensor i at ``table.offsets[i]``; the gap after each tensor up to a multiple
+    of 4 floats and the arena's tail are written as +0.0.  The device table is built once per layout (the tensors'
+    sizes) and returned: hand it back as ``table`` on the next call and only changed source pointers are uploaded.
+    Runs on the current stream (use a table on one stream only) and reads nothing back."""
+    tensors = list(tensors)
+    if arena.dim() != 1 or arena.dtype != torch.float32 or not arena.is_cuda or not arena.is_contiguous():
+        raise ValueError(f"grad_pack: arena must be a contiguous 1-d float32 CUDA tensor, got {arena.dtype} "
+                         f"{tuple(arena.shape)} on {arena.device}")
+    dev = arena.get_device()
+    for i, t in enumerate(tensors):
+        if t.dtype is not torch.float32 or not t.is_cuda or t.get_device() != dev or not t.is_contiguous():
+            raise ValueError(f"grad_pack: tensor {i} must be a contiguous float32 tensor on {arena.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} (strides {t.stride()}) on {t.device}")
+    sizes = tuple(t.numel() for t in tensors)
+    if table is None or table.sizes != sizes or table.device != arena.device:
+        table = GradTable(sizes, arena.device)
+    if table.floats > arena.numel():
+        raise ValueError(f"grad_pack: the layout needs {table.floats} floats, the arena holds {arena.numel()}")
+    with torch.cuda.device(arena.device):
+        table.update(tensors)
+        moved = 4.0 * (sum(sizes) + arena.numel())
+        trace = (("grad_pack", len(sizes)), 0.0, moved) if TRACE is not None else None
+        _launch("stif_grad_pack", trace, L.lib().stif_grad_pack, _vp(table.dev), len(sizes), _vp(arena), arena.numel(),
+                torch.cuda.current_stream(arena.device).cuda_stream)
+    return table
+
+
+def rank_sum(slab: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """stif_rank_sum: ``dst`` [n] = ((slab[0] + slab[1]) + ...) + slab[R - 1], plain fp32 adds in row order -- the
+    cross-rank gradient sum with a defined order.  ``slab`` float32 CUDA [R, row] with
+    contiguous rows of at least n floats, R <= 64, n a multiple of 4; ``dst`` must not overlap it.  Identical bits on
+    every call; runs on the current stream and reads nothing back."""
+    if slab.dim() != 2 or slab.dtype != torch.float32 or not slab.is_cuda or (slab.shape[1] > 1 and slab.stride(1) != 1):
+        raise ValueError(f"rank_sum: slab must be a float32 CUDA [R, row] with contiguous rows, got {slab.dtype} "
+                         f"{tuple(slab.shape)} on {slab.device}")
+    if dst.dim() != 1 or dst.dtype != torch.float32 or dst.device != slab.device or not dst.is_contiguous():
+        raise ValueError(f"rank_sum: dst must be a contiguous 1-d float32 tensor on {slab.device}")
+    R, n = slab.shape[0], dst.numel()
+    if n > slab.shape[1]:
+        raise ValueError(f"rank_sum: dst holds {n} floats, a slab row {slab.shape[1]}")
+    row = slab.stride(0) if R > 1 else max(slab.shape[1], n)
+    trace = (("rank_sum", R), float((R - 1) * n), 4.0 * (R + 1) * n) if TRACE is not None else None
+    _launch("stif_rank_sum", trace, L.lib().stif_rank_sum, _vp(slab), row, R, _vp(dst), n,
+            torch.cuda.current_stream(slab.device).cuda_stream)
+    return dst
+
+
 def _sorted_segments(words: torch.Tensor, D: int):
     """The packed words of a scatter in ascending order and the D + 1 segment starts: integer torch calls on the
     device whose results are unique (the words are distinct), so nothing here depends on an order of arrival."""

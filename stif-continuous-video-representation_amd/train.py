@@ -60,6 +60,7 @@ import math
 from collections import Counter, defaultdict
 
 import torch
+import torch.distributed as dist
 from torch import nn
 from torch.optim.lr_scheduler import LRScheduler
 
@@ -1298,3 +1299,286 @@ class TimesLoss(nn.Module):
 
     def forward(self, outs, gt):
         return sum(self.criterion(o, gt[:, i]) for i, o in enumerate(outs))
+
+
+# ---- data-parallel training: the gradient arena, the rank-ordered sum, DataParallel (DESIGN.md section 3r) ----
+
+def _named(params):
+    """[(name, parameter)] of a module, of ``named_parameters()``-style pairs, or of bare parameters."""
+    if isinstance(params, nn.Module):
+        return list(params.named_parameters())
+    out = []
+    for i, p in enumerate(params):
+        out.append(tuple(p) if isinstance(p, (tuple, list)) else (str(i), p))
+    if not out:
+        raise ValueError("GradArena: no parameters")
+    return out
+
+
+class GradArena:
+    """One contiguous fp32 buffer for the gradients of ``params`` (a module, ``named_parameters()`` pairs or
+    parameters), in that order: parameter i lives at ``offsets[i]``, the previous end rounded up to 4 floats, and
+    ``total`` is the sum of the rounded sizes.  The layout is fixed here.  ``pack()`` gathers the ``.grad`` tensors into
+    the arena (or into ``out``, a row of a slab) with one stif_grad_pack launch, gaps written as +0.0; ``views()`` are
+    per-parameter views of the arena and ``assign()`` makes them the ``.grad``s, so that the optimiser steps on the
+    reduced arena and nothing is copied back."""
+
+    def __init__(self, params):
+        named = _named(params)
+        self.names, self.params = [k for k, _ in named], [p for _, p in named]
+        dev = self.params[0].device
+        for k, p in named:
+            if p.dtype != torch.float32 or p.device != dev:
+                raise ValueError(f"GradArena: {k} is {p.dtype} on {p.device}; float32 parameters on one device only")
+        self.table = ops.GradTable([p.numel() for p in self.params], dev)
+        self.sizes, self.offsets, self.total = list(self.table.sizes), list(self.table.offsets), self.table.floats
+        self.arena = torch.zeros(max(self.total, 4), dtype=torch.float32, device=dev)
+        self._views = None
+
+    def grads(self):
+        missing = [k for k, p in zip(self.names, self.params) if p.grad is None]
+        if missing:
+            raise RuntimeError(f"{len(missing)} covered parameter(s) received no gradient in this backward: "
+                               + ", ".join(missing[:8]) + (" ..." if len(missing) > 8 else ""))
+        return [p.grad for p in self.params]
+
+    def pack(self, out: torch.Tensor = None) -> torch.Tensor:
+        out = self.arena if out is None else out
+        self.table = ops.grad_pack(self.grads(), out, self.table)
+        return out
+
+    def views(self):
+        """Per-parameter views of the arena, made once: the same tensors are handed out every step."""
+        if self._views is None:
+            self._views = [self.arena[o:o + n].view_as(p) for o, n, p in zip(self.offsets, self.sizes, self.params)]
+        return self._views
+
+    def assign(self):
+        for p, v in zip(self.params, self.views()):
+            p.grad = v
+
+
+def _covered(net: nn.Module):
+    """The parameters that received a gradient in the backward just run, as named_parameters() pairs."""
+    return [(k, p) for k, p in net.named_parameters() if p.grad is not None]
+
+
+def _staged(group) -> bool:
+    """parallel.halo_exchange's backend rule: gloo moves CPU tensors, so device buffers are staged through (pinned)
+    host memory -- which is what lets several ranks share one GPU; nccl takes the device buffers as they are."""
+    return dist.get_backend(group) == "gloo"
+
+
+def _small_gather(values, group, device) -> torch.Tensor:
+    """One small collective: every rank's int64 ``values`` as a CPU [world, len(values)] tensor."""
+    world = dist.get_world_size(group)
+    dev = "cpu" if _staged(group) else device
+    mine = torch.tensor(list(values), dtype=torch.int64, device=dev)
+    rows = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(rows, mine, group=group)
+    return torch.stack(rows).cpu()
+
+
+def _names_hash(names) -> int:
+    import hashlib
+    return int.from_bytes(hashlib.sha256("\n".join(names).encode()).digest()[:8], "little", signed=True)
+
+
+def check_covered_set(covered, every, group=None, device="cpu") -> None:
+    """The first step's agreement on which parameters the arena covers: one small collective compares a hash of the
+    covered names over the ranks.  On a mismatch -- seen by every rank alike, so all of them leave together instead of
+    hanging in an exchange of different sizes -- the ranks trade the names they leave out and RuntimeError lists
+    them."""
+    hashes = _small_gather([_names_hash(covered)], group, device)[:, 0].tolist()
+    if len(set(hashes)) == 1:
+        return
+    left_out = sorted(set(every) - set(covered))
+    per_rank = [None] * dist.get_world_size(group)
+    dist.all_gather_object(per_rank, left_out, group=group)
+    common = set.intersection(*[set(x) for x in per_rank])
+    odd = [f"rank {r}: " + (", ".join(k for k in x if k not in common) or "-") for r, x in enumerate(per_rank)]
+    raise RuntimeError("DataParallel: the ranks disagree on which parameters received a gradient in the first "
+                       "backward; without a gradient only on " + "; ".join(odd))
+
+
+class DataParallel:
+    """Data-parallel optimiser steps with sum semantics: every rank runs forward and backward
+    on its own items of the global batch, the gradients are summed over ranks -- never averaged, the reference's loss is
+    a sum -- and every rank takes the optimiser step one process would take on the whole batch, up to fp32
+    reassociation.  The gradients cross as one arena in one collective:
+
+    * ``reduce="sum"``: one ``dist.all_reduce(SUM)`` on the arena (the backend's order of addition);
+    * ``reduce="ordered"``: ``all_gather`` into a [world, N] slab, then stif_rank_sum, ((g0 + g1) + g2) + ... by rank
+      on every rank: replicas stay bitwise identical, a run is the same under gloo and RCCL, and ``emulate_ranks``
+      reproduces it in one process;
+    * ``reduce=None`` (default): "ordered" while ``is_deterministic()``, "sum" otherwise, read at every step.
+
+    At construction rank 0's parameters and buffers are broadcast.  The arena covers exactly the parameters that
+    received a gradient in the first backward (434 of LunaTokis' 442); the ranks compare a hash of that set once
+    (``check_covered_set``), and a covered parameter without a gradient on a later step raises.  With the gloo backend
+    the arena is staged through pinned host memory; with nccl the device buffers go unstaged and
+    ``parallel.warm_group`` runs first.  ``world == 1`` needs no process group.  ``step`` forces no host
+    synchronisation of its own (gloo's staging waits for the copy); ``global_loss()`` and ``range_status()`` are the
+    reads, for ``print_freq``."""
+
+    def __init__(self, net: nn.Module, optimizer, group=None, reduce=None):
+        if reduce not in (None, "sum", "ordered"):
+            raise ValueError(f"reduce must be 'sum', 'ordered' or None, got {reduce!r}")
+        self.net, self.optimizer, self.group, self.reduce = net, optimizer, group, reduce
+        self.distributed = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(group) if self.distributed else 1
+        self.rank = dist.get_rank(group) if self.distributed else 0
+        self.arena = self._slab = self._host = self._host_slab = self._loss = None
+        if self.world > 1:
+            if self.world > L.RANK_SUM_MAX_RANKS:
+                raise ValueError(f"DataParallel: at most {L.RANK_SUM_MAX_RANKS} ranks, got {self.world}")
+            if not _staged(group):
+                from . import parallel
+                parallel.warm_group(group)
+            self._broadcast()
+
+    def _broadcast(self):
+        stage = _staged(self.group)
+        src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+        with torch.no_grad():
+            for t in list(self.net.parameters()) + list(self.net.buffers()):
+                buf = t.detach().cpu() if stage else t.detach()
+                dist.broadcast(buf, src, group=self.group)
+                if stage and self.rank != 0:
+                    t.copy_(buf)
+
+    def _first_backward(self):
+        named = _covered(self.net)
+        if not named:
+            raise RuntimeError("DataParallel: no parameter received a gradient")
+        if self.world > 1:
+            check_covered_set([k for k, _ in named], [k for k, _ in self.net.named_parameters()], self.group,
+                              named[0][1].device)
+        self.arena = GradArena(named)
+        covered = {id(p) for p in self.arena.params}
+        self._outside = [(k, p) for k, p in self.net.named_parameters() if id(p) not in covered]
+
+    def _mode(self):
+        return self.reduce or ("ordered" if is_deterministic() else "sum")
+
+    def _reduce(self):
+        a, N = self.arena.arena, self.arena.arena.numel()
+        stage, mode = _staged(self.group), self._mode()
+        if stage and self._host is None:
+            self._host = torch.empty(N, dtype=torch.float32, pin_memory=a.is_cuda)
+        if mode == "sum":
+            if not stage:
+                dist.all_reduce(a, op=dist.ReduceOp.SUM, group=self.group)
+                return
+            self._host.copy_(a, non_blocking=True)
+            _wait(a)
+            dist.all_reduce(self._host, op=dist.ReduceOp.SUM, group=self.group)
+            a.copy_(self._host, non_blocking=True)
+            return
+        if self._slab is None:
+            self._slab = torch.empty(self.world, N, dtype=torch.float32, device=a.device)
+        if not stage:
+            dist.all_gather_into_tensor(self._slab, a, group=self.group)
+        else:
+            if self._host_slab is None:
+                self._host_slab = torch.empty(self.world, N, dtype=torch.float32, pin_memory=a.is_cuda)
+            self._host.copy_(a, non_blocking=True)
+            _wait(a)
+            dist.all_gather(list(self._host_slab.unbind(0)), self._host, group=self.group)
+            self._slab.copy_(self._host_slab, non_blocking=True)
+        ops.rank_sum(self._slab, a)
+
+    def step(self, criterion, inputs, gt, weight: float = 1.0) -> torch.Tensor:
+        """optimize_step for this rank's items of the global batch: zero_grad(set_to_none=True), forward,
+        ``weight * criterion``, backward, pack, reduce over the ranks, the arena's views as ``.grad``,
+        ``optimizer.step()``.  Returns this rank's loss as a device tensor."""
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = weight * criterion(self.net(*inputs), gt)
+        loss.backward()
+        if self.arena is None:
+            self._first_backward()
+        else:
+            late = [k for k, p in self._outside if p.grad is not None]
+            if late:
+                raise RuntimeError("DataParallel: parameter(s) outside the arena received a gradient (the covered set "
+                                   "is fixed by the first backward): " + ", ".join(late[:8]))
+        self.arena.pack()
+        if self.world > 1:
+            self._reduce()
+        self.arena.assign()
+        self.optimizer.step()
+        self._loss = loss.detach()
+        return self._loss
+
+    def global_loss(self) -> float:
+        """The last step's loss summed over the ranks in rank order (fp32); one synchronisation and, with several
+        ranks, one small collective."""
+        if self._loss is None:
+            raise RuntimeError("DataParallel.global_loss: no step taken yet")
+        mine = self._loss.reshape(1).to(torch.float32)
+        if self.world == 1:
+            return float(mine)
+        dev = "cpu" if _staged(self.group) else mine.device
+        rows = [torch.empty(1, dtype=torch.float32, device=dev) for _ in range(self.world)]
+        dist.all_gather(rows, mine.to(dev), group=self.group)
+        total = rows[0].cpu()
+        for r in rows[1:]:
+            total = total + r.cpu()
+        return float(total)
+
+    def range_status(self) -> int:
+        """``train.range_status`` of this rank's device, ORed over the ranks."""
+        dev = next(self.net.parameters()).device
+        bits = range_status(dev)
+        if self.world > 1:
+            for b in _small_gather([bits], self.group, dev)[:, 0].tolist():
+                bits |= int(b)
+        return bits
+
+    def replicas_agree(self) -> bool:
+        """One small collective: an exact integer checksum of every parameter's bits, compared over the ranks."""
+        if self.world == 1:
+            return True
+        dev = next(self.net.parameters()).device
+        total = torch.zeros((), dtype=torch.int64, device=dev)
+        for i, p in enumerate(self.net.parameters()):
+            total += p.detach().reshape(-1).view(torch.int32).to(torch.int64).sum() * (2 * i + 1)
+        sums = _small_gather([int(total)], self.group, dev)[:, 0].tolist()
+        return len(set(sums)) == 1
+
+
+def _wait(t: torch.Tensor) -> None:
+    """A host collective reads the staging buffer next: wait for the copies queued on ``t``'s stream."""
+    if t.is_cuda:
+        torch.cuda.current_stream(t.device).synchronize()
+
+
+def emulate_ranks(net: nn.Module, optimizer, criterion, per_rank_batches, weight: float = 1.0) -> torch.Tensor:
+    """The definition ``DataParallel`` with the ordered sum is held to, in one process: from the same state, each
+    ``(inputs, gt)`` of ``per_rank_batches`` in turn takes rank r's forward and backward and is packed into row r of a
+    slab; stif_rank_sum adds the rows in rank order, the arena's views become the ``.grad``s and the optimiser takes
+    one step.  Also "accumulate over micro-batches" on one GPU.  Returns the losses summed in rank order (a device
+    tensor, fp32).  The arena and the slab are kept on the optimiser (``optimizer.emulated_arena``, a ``GradArena``)
+    for the next call with as many batches."""
+    batches = list(per_rank_batches)
+    R = len(batches)
+    if not 1 <= R <= L.RANK_SUM_MAX_RANKS:
+        raise ValueError(f"emulate_ranks: 1 .. {L.RANK_SUM_MAX_RANKS} batches, got {R}")
+    total = arena = slab = None
+    for r, (inputs, gt) in enumerate(batches):
+        optimizer.zero_grad(set_to_none=True)
+        loss = weight * criterion(net(*inputs), gt)
+        loss.backward()
+        if r == 0:
+            named = _covered(net)
+            arena, slab = getattr(optimizer, "emulated_arena", None), getattr(optimizer, "emulated_slab", None)
+            if arena is None or arena.names != [k for k, _ in named] or slab.shape[0] != R:
+                arena = optimizer.emulated_arena = GradArena(named)
+                slab = optimizer.emulated_slab = torch.empty(R, arena.arena.numel(), dtype=torch.float32,
+                                                             device=arena.arena.device)
+        arena.pack(slab[r])
+        total = loss.detach() if total is None else total + loss.detach()
+    ops.rank_sum(slab, arena.arena)
+    arena.assign()
+    optimizer.step()
+    return total
