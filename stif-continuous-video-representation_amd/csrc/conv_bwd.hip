@@ -10,6 +10,9 @@
 // Winograd packer for a 64 x 64 block of a wider weight.
 // The ConvLSTM cell's 128 -> 256 conv is eight more such blocks: (nx, gy_channels, cout) =
 // (2, 256, 256) in the block weight gradient, a [256][128] weight in the block packer.
+// The weight-gradient entries share one device body (wgrad_walk: k_wgrad<S> and k_wgrad_cat only pick their pointers
+// and their gy view), one reduce (k_wgrad_reduce in wgrad_part.h, by block) and one checked launch (wgrad_run); the two
+// Winograd device packers share pack_wino_run.
 #include <algorithm>
 #include <cstdio>
 
@@ -45,103 +48,30 @@ struct WgradTile {
 constexpr int WG_PER_CU = STIF_WGRAD_WG_PER_CU;
 // GW_FLOATS, PART (one workgroup's partial) and k_wgrad_reduce: wgrad_part.h
 
-// x is [H][W][64] per item, gy [Ho][Wo][64]; the tiles walk gy
-template <int S>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG_PER_CU)))
-void k_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ ws, long long x_item,
-             long long gy_item, int H, int W, int Ho, int Wo, int tiles_x, int tiles_per_item, int ntiles) {
-  constexpr int TH = WgradTile<S>::TH, TW = WgradTile<S>::TW, XH = WgradTile<S>::XH, XW = WgradTile<S>::XW;
-  __shared__ __attribute__((aligned(16))) float s_x[XH * XW * 64];
-  __shared__ __attribute__((aligned(16))) float s_gy[TH * TW * 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int cot = wave >> 1, cit = wave & 1, l32 = lane & 31, hf = lane >> 5;
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  float bsum = 0.f;   // sum of this lane's gy values: cout cot * 32 + l32, pixels of parity hf
-
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int n = t / tiles_per_item, rem = t - n * tiles_per_item, ty = rem / tiles_x, tx = rem - ty * tiles_x;
-    const int y0 = ty * TH, x0 = tx * TW;
-    const float* xi = x + (size_t)n * x_item;
-    const float* gi = gy + (size_t)n * gy_item;
-    __syncthreads();   // the previous tile's reads are done
-#pragma unroll
-    for (int k = 0; k < (XH * XW * 16 + 255) / 256; ++k) {
-      const int i = tid + k * 256;
-      if (i < XH * XW * 16) {
-        const int c4 = i & 15, p = i >> 4, py = p / XW, px = p - py * XW;
-        const int yy = S * y0 + py - 1, xx = S * x0 + px - 1;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = ld4(xi + ((size_t)yy * W + xx) * 64 + c4 * 4);
-        st4(s_x + p * 64 + c4 * 4, v);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < TH * TW * 16 / 256; ++k) {
-      const int i = tid + k * 256;
-      const int c4 = i & 15, p = i >> 4, py = p / TW, px = p - py * TW;
-      const int yy = y0 + py, xx = x0 + px;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (yy < Ho && xx < Wo) v = ld4(gi + ((size_t)yy * Wo + xx) * 64 + c4 * 4);
-      st4(s_gy + p * 64 + c4 * 4, v);
-    }
-    __syncthreads();
-    // k step (r, xs): gy pixels (r, 2 xs + hf) of the tile; tap (kh, kw) reads x tile pixel
-    // (S r + kh, S (2 xs + hf) + kw)
-    const float* ap = s_gy + hf * 64 + cot * 32 + l32;
-    const float* bp = s_x + S * hf * 64 + cit * 32 + l32;
-#pragma unroll
-    for (int r = 0; r < TH; ++r) {
-#pragma unroll 2
-      for (int xs = 0; xs < TW / 2; ++xs) {
-        const float a = ap[(r * TW + 2 * xs) * 64];
-        bsum += a;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-          for (int kw = 0; kw < 3; ++kw)
-            acc[kh * 3 + kw] = mfma32(a, bp[((S * r + kh) * XW + S * 2 * xs + kw) * 64], acc[kh * 3 + kw]);
-      }
-    }
-  }
-
-  float* part = ws + (size_t)blockIdx.x * PART;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      part[t * 4096 + (cot * 32 + mfma_row(r, lane)) * 64 + cit * 32 + l32] = acc[t][r];
-  const float other = __shfl_xor(bsum, 32);
-  if (cit == 0 && hf == 0) part[GW_FLOATS + cot * 32 + l32] = bsum + other;
-}
-
-// The weight gradient in 64 x 64 channel blocks, a sibling of k_wgrad<1> -- a shared template
-// cost k_wgrad two VGPRs.  blockIdx.y = slice * nx + xi is the block of cout slice `slice` (gy channels co0 = 64 slice
-// .. of a pixel pitch of gc floats; channels at or past cout are zeros in LDS and never loaded) against the input map
-// x[xi].  Every block is k_wgrad<1>'s walk: the same tiles, grid, staging and k order, one partial per workgroup and
-// block (block-major in the workspace), so its sums are the bits stif_conv3x3_wgrad computes for the same two
-// 64-channel maps.  The x tile is staged once per block (four times for the 216 form): the loop is MFMA-paced.
-struct WgradCat {
-  const float* x[2];
-  long long x_item[2];
-  int nx, gc, cout;
+// The gy map a walk reads.  GyPlain: [Ho][Wo][64], every channel live -- pitch, offset and limit fold to constants.
+// GySlice: 64 channels from co0 of a pixel pitch of gc floats; channels at or past cout are zeros in LDS, never loaded.
+struct GyPlain {
+  __device__ int pitch() const { return 64; }
+  __device__ int offset() const { return 0; }
+  __device__ bool live(int) const { return true; }
+};
+struct GySlice {
+  int gc, co0, cout;
+  __device__ int pitch() const { return gc; }
+  __device__ int offset() const { return co0; }
+  __device__ bool live(int c) const { return co0 + c < cout; }
 };
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG_PER_CU)))
-void k_wgrad_cat(WgradCat c, const float* __restrict__ gy, float* __restrict__ ws, long long gy_item, int H, int W,
-                 int tiles_x, int tiles_per_item, int ntiles) {
-  constexpr int S = 1;   // S, Ho, Wo are kept so that the body below reads line for line as k_wgrad's
-  const int blk = blockIdx.y, slice = blk / c.nx, xi_ = blk - slice * c.nx, co0 = slice * 64, GC = c.gc, cv = c.cout;
-  const float* __restrict__ x = xi_ ? c.x[1] : c.x[0];
-  const long long x_item = xi_ ? c.x_item[1] : c.x_item[0];
-  const int Ho = H, Wo = W;
+// The tile walk of one 64 x 64 channel block: x is [H][W][64] per item, gy [Ho][Wo][view] -- the tiles walk gy -- and
+// the workgroup's partial is the one of block `blk` (block-major in the workspace).
+template <int S, class GyView>
+__device__ __forceinline__ void wgrad_walk(const int tid, const GyView v, const float* x, const float* gy, float* ws,
+                                           int blk, long long x_item, long long gy_item, int H, int W, int Ho, int Wo,
+                                           int tiles_x, int tiles_per_item, int ntiles) {
   constexpr int TH = WgradTile<S>::TH, TW = WgradTile<S>::TW, XH = WgradTile<S>::XH, XW = WgradTile<S>::XW;
   __shared__ __attribute__((aligned(16))) float s_x[XH * XW * 64];
   __shared__ __attribute__((aligned(16))) float s_gy[TH * TW * 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lane = tid & 63, wave = tid >> 6;
   const int cot = wave >> 1, cit = wave & 1, l32 = lane & 31, hf = lane >> 5;
   f32x16 acc[9];
 #pragma unroll
@@ -162,9 +92,9 @@ void k_wgrad_cat(WgradCat c, const float* __restrict__ gy, float* __restrict__ w
       if (i < XH * XW * 16) {
         const int c4 = i & 15, p = i >> 4, py = p / XW, px = p - py * XW;
         const int yy = S * y0 + py - 1, xx = S * x0 + px - 1;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = ld4(xi + ((size_t)yy * W + xx) * 64 + c4 * 4);
-        st4(s_x + p * 64 + c4 * 4, v);
+        f32x4 v4 = {0.f, 0.f, 0.f, 0.f};
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) v4 = ld4(xi + ((size_t)yy * W + xx) * 64 + c4 * 4);
+        st4(s_x + p * 64 + c4 * 4, v4);
       }
     }
 #pragma unroll
@@ -172,9 +102,9 @@ void k_wgrad_cat(WgradCat c, const float* __restrict__ gy, float* __restrict__ w
       const int i = tid + k * 256;
       const int c4 = i & 15, p = i >> 4, py = p / TW, px = p - py * TW;
       const int yy = y0 + py, xx = x0 + px;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (yy < Ho && xx < Wo && co0 + c4 * 4 < cv) v = ld4(gi + ((size_t)yy * Wo + xx) * GC + co0 + c4 * 4);
-      st4(s_gy + p * 64 + c4 * 4, v);
+      f32x4 v4 = {0.f, 0.f, 0.f, 0.f};
+      if (yy < Ho && xx < Wo && v.live(c4 * 4)) v4 = ld4(gi + ((size_t)yy * Wo + xx) * v.pitch() + v.offset() + c4 * 4);
+      st4(s_gy + p * 64 + c4 * 4, v4);
     }
     __syncthreads();
     // k step (r, xs): gy pixels (r, 2 xs + hf) of the tile; tap (kh, kw) reads x tile pixel
@@ -206,24 +136,30 @@ void k_wgrad_cat(WgradCat c, const float* __restrict__ gy, float* __restrict__ w
   if (cit == 0 && hf == 0) part[GW_FLOATS + cot * 32 + l32] = bsum + other;
 }
 
-// gw / gb of every block = its G partials summed in index order; gw stored OIHW with rows of 64 nx input channels,
-// rows at or past cout skipped, gb from the blocks of x[0]
-__global__ __launch_bounds__(256) void k_wgrad_cat_reduce(const float* __restrict__ ws, int G, float* __restrict__ gw,
-                                                          float* __restrict__ gb, int nx, int cout) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= PART) return;
-  const int blk = blockIdx.y, slice = blk / nx, xi = blk - slice * nx;
-  const float* p = ws + (size_t)blk * G * PART;
-  float s = 0.f;
-#pragma unroll 8
-  for (int g = 0; g < G; ++g) s += p[(size_t)g * PART + idx];
-  if (idx < GW_FLOATS) {
-    const int tap = idx >> 12, co = slice * 64 + ((idx >> 6) & 63), ci = xi * 64 + (idx & 63);
-    if (co < cout) gw[((size_t)co * 64 * nx + ci) * 9 + tap] = s;
-  } else if (gb != nullptr && xi == 0) {
-    const int co = slice * 64 + idx - GW_FLOATS;
-    if (co < cout) gb[co] = s;
-  }
+template <int S>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG_PER_CU)))
+void k_wgrad(const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ ws, long long x_item,
+             long long gy_item, int H, int W, int Ho, int Wo, int tiles_x, int tiles_per_item, int ntiles) {
+  wgrad_walk<S>(threadIdx.x, GyPlain{}, x, gy, ws, 0, x_item, gy_item, H, W, Ho, Wo, tiles_x, tiles_per_item, ntiles);
+}
+
+// The weight gradient in 64 x 64 channel blocks: blockIdx.y = slice * nx + xi is the block of
+// cout slice `slice` (gy channels 64 slice .. of a pixel pitch of gc floats) against the input map x[xi].  Every block
+// is k_wgrad<1>'s walk -- the same tiles, grid, staging and k order, one partial per workgroup and block (block-major
+// in the workspace) -- so its sums are the bits stif_conv3x3_wgrad computes for the same two 64-channel maps.  The x
+// tile is staged once per block (four times for the 216 form): the loop is MFMA-paced.
+struct WgradCat {
+  const float* x[2];
+  long long x_item[2];
+  int nx, gc, cout;
+};
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG_PER_CU)))
+void k_wgrad_cat(WgradCat c, const float* __restrict__ gy, float* __restrict__ ws, long long gy_item, int H, int W,
+                 int tiles_x, int tiles_per_item, int ntiles) {
+  const int blk = blockIdx.y, slice = blk / c.nx, xi = blk - slice * c.nx;
+  wgrad_walk<1>(threadIdx.x, GySlice{c.gc, slice * 64, c.cout}, xi ? c.x[1] : c.x[0], gy, ws, blk,
+                xi ? c.x_item[1] : c.x_item[0], gy_item, H, W, H, W, tiles_x, tiles_per_item, ntiles);
 }
 
 // tiles over the gy map of an x of H x W (stride 2: Ho = (H + 1) / 2, Wo = (W + 1) / 2)
@@ -246,41 +182,79 @@ size_t wgrad_workspace_size(int n, int H, int W, int cin, int cout) {
 
 bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
-// the entry point of stride S; `fn` prefixes every message
+int fail_as(const char* fn, const char* why) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", fn, why);
+  return stif_fail(STIF_E_INVALID, msg);
+}
+
+// the (cout slice, x map) blocks of a supported (nx, gy_channels, cout), 0 for anything else
+int wgrad_cat_blocks(int nx, int gy_channels, int cout) {
+  if (gy_channels == 64 && cout == 64 && (nx == 1 || nx == 2)) return nx;
+  if (gy_channels == 256 && cout == 216 && nx == 1) return 4;
+  if (gy_channels == 256 && cout == 256 && nx == 2) return 8;   // the ConvLSTM cell's 128 -> 256 conv
+  return 0;
+}
+
+// Every weight-gradient entry: the checks, then the walk and the reduce.  `a` is the block form's arguments (the
+// 64 -> 64 entries are its (1, 64, 64) case), `blocks` its block count or 0 for unsupported channel counts (`chans`
+// says which are supported), `ptrs` names the pointers that must not be null; `fn` prefixes every message.  cat:
+// k_wgrad_cat over the blocks (stride 1 only: it is k_wgrad<1>'s walk, so S = 1 with it), otherwise k_wgrad<S>.
 template <int S>
-int wgrad_entry(const char* fn, const stif_conv_wgrad_args* pa, void* stream) {
+int wgrad_run(const char* fn, const stif_conv_wgrad_cat_args& a, int blocks, bool cat, const char* ptrs,
+              const char* chans, void* stream) {
   constexpr int TH = WgradTile<S>::TH, TW = WgradTile<S>::TW;
   char msg[160];
-  auto fail = [&](const char* why) {
-    snprintf(msg, sizeof msg, "%s: %s", fn, why);
-    return stif_fail(STIF_E_INVALID, msg);
-  };
-  if (!pa) return fail("null args");
-  const stif_conv_wgrad_args& a = *pa;
-  if (!a.x || !a.gy || !a.gw) return fail("null pointer (x, gy, gw)");
-  if (a.n < 1 || a.H < 1 || a.W < 1) return fail("n, H, W must be >= 1");
-  if (a.cin != 64 || a.cout != 64) return fail("unsupported channel counts (64 -> 64 only)");
-  if (a.x_item < 0 || a.gy_item < 0) return fail("negative item stride");
-  if ((long long)a.H * a.W * 64 * 4 >= 0x7fffffffLL) return fail("item larger than 2 GB (buffer addressing)");
-  if (misaligned16(a.x) || misaligned16(a.gy) || a.x_item % 4 || a.gy_item % 4)
-    return fail("x / gy and their item strides must be 16-byte aligned");
+  if (!a.x[0] || !a.gy || !a.gw) return fail_as(fn, ptrs);
+  if (a.n < 1 || a.H < 1 || a.W < 1) return fail_as(fn, "n, H, W must be >= 1");
+  if (!blocks) return fail_as(fn, chans);
+  const bool two = a.nx == 2;
+  if (two && !a.x[1]) return fail_as(fn, "null pointer (x[1] with nx = 2)");
+  if (a.x_item[0] < 0 || (two && a.x_item[1] < 0) || a.gy_item < 0) return fail_as(fn, "negative item stride");
+  if ((long long)a.H * a.W * a.gy_channels * 4 >= 0x7fffffffLL)
+    return fail_as(fn, "item larger than 2 GB (buffer addressing)");
+  if (misaligned16(a.x[0]) || (two && misaligned16(a.x[1])) || misaligned16(a.gy) || a.x_item[0] % 4 ||
+      (two && a.x_item[1] % 4) || a.gy_item % 4)
+    return fail_as(fn, "x / gy and their item strides must be 16-byte aligned");
   const long long tiles = wgrad_tiles<S>(a.n, a.H, a.W);
-  if (tiles > 0x7fffffffLL) return fail("too many tiles");
+  if (tiles > 0x7fffffffLL) return fail_as(fn, "too many tiles");
   const int G = wgrad_grid(tiles);
-  if (!a.workspace || a.workspace_bytes < (size_t)G * PART * sizeof(float))
-    return fail(S == 1 ? "workspace too small (stif_conv3x3_wgrad_workspace_size)"
-                       : "workspace too small (stif_conv3x3s2_wgrad_workspace_size)");
-  if (misaligned16(a.workspace)) return fail("workspace not 16-byte aligned");
+  if (!a.workspace || a.workspace_bytes < (size_t)blocks * G * PART * sizeof(float)) {
+    snprintf(msg, sizeof msg, "workspace too small (%s_workspace_size)", fn);
+    return fail_as(fn, msg);
+  }
+  if (misaligned16(a.workspace)) return fail_as(fn, "workspace not 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int Ho = (a.H + S - 1) / S, Wo = (a.W + S - 1) / S;
   const int tiles_x = (Wo + TW - 1) / TW, tiles_per_item = tiles_x * ((Ho + TH - 1) / TH);
   float* ws = static_cast<float*>(a.workspace);
-  hipLaunchKernelGGL(k_wgrad<S>, dim3(G), dim3(256), 0, st, a.x, a.gy, ws, a.x_item, a.gy_item, a.H, a.W, Ho, Wo,
-                     tiles_x, tiles_per_item, (int)tiles);
+  if (cat) {
+    WgradCat c{{a.x[0], two ? a.x[1] : a.x[0]}, {a.x_item[0], two ? a.x_item[1] : a.x_item[0]}, a.nx, a.gy_channels,
+               a.cout};
+    hipLaunchKernelGGL(k_wgrad_cat, dim3(G, blocks), dim3(256), 0, st, c, a.gy, ws, a.gy_item, a.H, a.W, tiles_x,
+                       tiles_per_item, (int)tiles);
+  } else {
+    hipLaunchKernelGGL(k_wgrad<S>, dim3(G), dim3(256), 0, st, a.x[0], a.gy, ws, a.x_item[0], a.gy_item, a.H, a.W, Ho,
+                       Wo, tiles_x, tiles_per_item, (int)tiles);
+  }
   if (int rc = stif_check_launch(fn)) return rc;
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3((PART + 255) / 256), dim3(256), 0, st, ws, G, a.gw, a.gb);
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3((PART + 255) / 256, blocks), dim3(256), 0, st, ws, G, a.gw, a.gb, a.nx,
+                     a.cout);
   snprintf(msg, sizeof msg, "%s (reduce)", fn);
   return stif_check_launch(msg);
+}
+
+// the 64 -> 64 entry of stride S
+template <int S>
+int wgrad_entry(const char* fn, const stif_conv_wgrad_args* pa, void* stream) {
+  if (!pa) return fail_as(fn, "null args");
+  stif_conv_wgrad_cat_args a{};
+  a.x[0] = pa->x, a.gy = pa->gy, a.gw = pa->gw, a.gb = pa->gb;
+  a.x_item[0] = pa->x_item, a.gy_item = pa->gy_item;
+  a.n = pa->n, a.H = pa->H, a.W = pa->W, a.nx = 1, a.gy_channels = 64, a.cout = 64;
+  a.workspace = pa->workspace, a.workspace_bytes = pa->workspace_bytes;
+  return wgrad_run<S>(fn, a, pa->cin == 64 && pa->cout == 64, false, "null pointer (x, gy, gw)",
+                      "unsupported channel counts (64 -> 64 only)", stream);
 }
 
 // ---- Winograd weight packing on the device: the bytes of pack.cpp's pack_wino / pack_wino_f16x3 ----
@@ -577,20 +551,6 @@ __global__ __launch_bounds__(256) void k_cf_wgrad_reduce(const float* __restrict
 long long cf_chunks(int n, int h, int w) { return ((long long)n * h * w + CF_WG_PX - 1) / CF_WG_PX; }
 int cf_grid(long long chunks) { return (int)std::min<long long>(chunks, (long long)CF_WG_PER_CU * stif_num_cus()); }
 
-int fail_as(const char* fn, const char* why) {
-  char msg[160];
-  snprintf(msg, sizeof msg, "%s: %s", fn, why);
-  return stif_fail(STIF_E_INVALID, msg);
-}
-
-// the (cout slice, x map) blocks of a supported (nx, gy_channels, cout), 0 for anything else
-int wgrad_cat_blocks(int nx, int gy_channels, int cout) {
-  if (gy_channels == 64 && cout == 64 && (nx == 1 || nx == 2)) return nx;
-  if (gy_channels == 256 && cout == 216 && nx == 1) return 4;
-  if (gy_channels == 256 && cout == 256 && nx == 2) return 8;   // the ConvLSTM cell's 128 -> 256 conv
-  return 0;
-}
-
 }  // namespace
 
 extern "C" size_t stif_conv3x3_wgrad_workspace_size(int n, int H, int W, int cin, int cout) {
@@ -615,39 +575,10 @@ extern "C" size_t stif_conv3x3_wgrad_cat_workspace_size(int n, int H, int W, int
 
 extern "C" int stif_conv3x3_wgrad_cat(const stif_conv_wgrad_cat_args* pa, void* stream) {
   const char* fn = "stif_conv3x3_wgrad_cat";
-  constexpr int TH = WgradTile<1>::TH, TW = WgradTile<1>::TW;
   if (!pa) return fail_as(fn, "null args");
-  const stif_conv_wgrad_cat_args& a = *pa;
-  if (!a.x[0] || !a.gy || !a.gw) return fail_as(fn, "null pointer (x[0], gy, gw)");
-  if (a.n < 1 || a.H < 1 || a.W < 1) return fail_as(fn, "n, H, W must be >= 1");
-  const int blocks = wgrad_cat_blocks(a.nx, a.gy_channels, a.cout);
-  if (!blocks)
-    return fail_as(fn, "unsupported channel counts (nx, gy_channels, cout: 2/64/64, 1/256/216, 1/64/64, 2/256/256)");
-  const bool two = a.nx == 2;
-  if (two && !a.x[1]) return fail_as(fn, "null pointer (x[1] with nx = 2)");
-  if (a.x_item[0] < 0 || (two && a.x_item[1] < 0) || a.gy_item < 0) return fail_as(fn, "negative item stride");
-  if ((long long)a.H * a.W * a.gy_channels * 4 >= 0x7fffffffLL)
-    return fail_as(fn, "item larger than 2 GB (buffer addressing)");
-  if (misaligned16(a.x[0]) || (two && misaligned16(a.x[1])) || misaligned16(a.gy) || a.x_item[0] % 4 ||
-      (two && a.x_item[1] % 4) || a.gy_item % 4)
-    return fail_as(fn, "x / gy and their item strides must be 16-byte aligned");
-  const long long tiles = wgrad_tiles<1>(a.n, a.H, a.W);
-  if (tiles > 0x7fffffffLL) return fail_as(fn, "too many tiles");
-  const int G = wgrad_grid(tiles);
-  if (!a.workspace || a.workspace_bytes < (size_t)blocks * G * PART * sizeof(float))
-    return fail_as(fn, "workspace too small (stif_conv3x3_wgrad_cat_workspace_size)");
-  if (misaligned16(a.workspace)) return fail_as(fn, "workspace not 16-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int tiles_x = (a.W + TW - 1) / TW, tiles_per_item = tiles_x * ((a.H + TH - 1) / TH);
-  float* ws = static_cast<float*>(a.workspace);
-  WgradCat c{{a.x[0], two ? a.x[1] : a.x[0]}, {a.x_item[0], two ? a.x_item[1] : a.x_item[0]}, a.nx, a.gy_channels,
-             a.cout};
-  hipLaunchKernelGGL(k_wgrad_cat, dim3(G, blocks), dim3(256), 0, st, c, a.gy, ws, a.gy_item, a.H, a.W, tiles_x,
-                     tiles_per_item, (int)tiles);
-  if (int rc = stif_check_launch(fn)) return rc;
-  hipLaunchKernelGGL(k_wgrad_cat_reduce, dim3((PART + 255) / 256, blocks), dim3(256), 0, st, ws, G, a.gw, a.gb, a.nx,
-                     a.cout);
-  return stif_check_launch("stif_conv3x3_wgrad_cat (reduce)");
+  return wgrad_run<1>(fn, *pa, wgrad_cat_blocks(pa->nx, pa->gy_channels, pa->cout), true, "null pointer (x[0], gy, gw)",
+                      "unsupported channel counts (nx, gy_channels, cout: 2/64/64, 1/256/216, 1/64/64, 2/256/256)",
+                      stream);
 }
 
 extern "C" int stif_upsample2x_bwd_nhwc(const float* gy, float* gx, int n, int h1, int w1, int c, float scale,
@@ -729,36 +660,14 @@ extern "C" int stif_pack_conv_plain_dev(const float* w_oihw, const float* b, int
   return stif_check_launch(fn);
 }
 
-extern "C" int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, int mode,
-                                         int flags, float* w_dst, float* b_dst, int* status, void* stream) {
-  if (!w_oihw || !w_dst || !b_dst)
-    return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: null pointer (w_oihw, w_dst, b_dst)");
-  if (mode != STIF_PACK_WINO && mode != (STIF_PACK_WINO | STIF_PACK_F16X3))
-    return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: unsupported mode (STIF_PACK_WINO [| STIF_PACK_F16X3] only)");
-  if (ks != 3) return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: winograd pack needs a 3x3 kernel");
-  if (cin != 64 || cout != 64)
-    return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: unsupported channel counts (64 -> 64 only)");
-  if (flags & ~STIF_PACK_DGRAD) return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: unknown flags");
-  const bool dgrad = (flags & STIF_PACK_DGRAD) != 0, f16 = (mode & STIF_PACK_F16X3) != 0;
-  if (!b && !dgrad)
-    return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: null bias (allowed with STIF_PACK_DGRAD only)");
-  if (f16 && !status)
-    return stif_fail(STIF_E_INVALID, "stif_pack_conv_weight_dev: STIF_PACK_F16X3 needs a status word (range report)");
-  hipLaunchKernelGGL(k_pack_wino, dim3(16), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, b, w_dst, b_dst,
-                     status, f16 ? 1 : 0, dgrad ? 1 : 0, 64, 64, 0, 0);
-  return stif_check_launch("stif_pack_conv_weight_dev");
-}
-
-extern "C" int stif_pack_conv_block_dev(const float* w_oihw, const float* b, int cout, int cin, int co0, int ci0,
-                                        int mode, int flags, float* w_dst, float* b_dst, int* status, void* stream) {
-  const char* fn = "stif_pack_conv_block_dev";
+// The two Winograd device packers: the checks, then k_pack_wino on the 64 x 64 block at (co0, ci0) of the [cout][cin]
+// weight.  `shape_err`: the entry's own refusal of its sizes, or null.
+static int pack_wino_run(const char* fn, const char* shape_err, const float* w_oihw, const float* b, int cout, int cin,
+                         int co0, int ci0, int mode, int flags, float* w_dst, float* b_dst, int* status, void* stream) {
   if (!w_oihw || !w_dst || !b_dst) return fail_as(fn, "null pointer (w_oihw, w_dst, b_dst)");
   if (mode != STIF_PACK_WINO && mode != (STIF_PACK_WINO | STIF_PACK_F16X3))
     return fail_as(fn, "unsupported mode (STIF_PACK_WINO [| STIF_PACK_F16X3] only)");
-  if (((cout != 64 && cout != 216) || (cin != 64 && cin != 128)) && !(cout == 256 && cin == 128))
-    return fail_as(fn, "unsupported channel counts (cout 64 or 216 with cin 64 or 128, or 256 with 128)");
-  if (co0 < 0 || co0 % 64 || co0 >= cout || ci0 < 0 || ci0 % 64 || ci0 >= cin)
-    return fail_as(fn, "co0 / ci0 must be multiples of 64 inside the weight");
+  if (shape_err) return fail_as(fn, shape_err);
   if (flags & ~STIF_PACK_DGRAD) return fail_as(fn, "unknown flags");
   const bool dgrad = (flags & STIF_PACK_DGRAD) != 0, f16 = (mode & STIF_PACK_F16X3) != 0;
   if (!b && !dgrad) return fail_as(fn, "null bias (allowed with STIF_PACK_DGRAD only)");
@@ -766,4 +675,24 @@ extern "C" int stif_pack_conv_block_dev(const float* w_oihw, const float* b, int
   hipLaunchKernelGGL(k_pack_wino, dim3(16), dim3(256), 0, static_cast<hipStream_t>(stream), w_oihw, b, w_dst, b_dst,
                      status, f16 ? 1 : 0, dgrad ? 1 : 0, cout, cin, co0, ci0);
   return stif_check_launch(fn);
+}
+
+extern "C" int stif_pack_conv_weight_dev(const float* w_oihw, const float* b, int cout, int cin, int ks, int mode,
+                                         int flags, float* w_dst, float* b_dst, int* status, void* stream) {
+  const char* err = ks != 3                    ? "winograd pack needs a 3x3 kernel"
+                    : cin != 64 || cout != 64 ? "unsupported channel counts (64 -> 64 only)"
+                                              : nullptr;
+  return pack_wino_run("stif_pack_conv_weight_dev", err, w_oihw, b, 64, 64, 0, 0, mode, flags, w_dst, b_dst, status,
+                       stream);
+}
+
+extern "C" int stif_pack_conv_block_dev(const float* w_oihw, const float* b, int cout, int cin, int co0, int ci0,
+                                        int mode, int flags, float* w_dst, float* b_dst, int* status, void* stream) {
+  const char* err = nullptr;
+  if (((cout != 64 && cout != 216) || (cin != 64 && cin != 128)) && !(cout == 256 && cin == 128))
+    err = "unsupported channel counts (cout 64 or 216 with cin 64 or 128, or 256 with 128)";
+  else if (co0 < 0 || co0 % 64 || co0 >= cout || ci0 < 0 || ci0 % 64 || ci0 >= cin)
+    err = "co0 / ci0 must be multiples of 64 inside the weight";
+  return pack_wino_run("stif_pack_conv_block_dev", err, w_oihw, b, cout, cin, co0, ci0, mode, flags, w_dst, b_dst,
+                       status, stream);
 }

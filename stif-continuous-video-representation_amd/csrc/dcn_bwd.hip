@@ -452,7 +452,7 @@ extern "C" int stif_dcn_bwd_nhwc(const stif_dcn_bwd_args* pa, void* stream) {
     float* ws = static_cast<float*>(a.workspace);
     hipLaunchKernelGGL(k_dcn_bwd_w, dim3(G), dim3(256), 0, st, a, ws, tiles_x, tiles_per_item, (int)wtiles);
     if (int rc = stif_check_launch("stif_dcn_bwd_nhwc (weight)")) return rc;
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((PART + 255) / 256), dim3(256), 0, st, ws, G, a.g_w, a.g_b);
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3((PART + 255) / 256), dim3(256), 0, st, ws, G, a.g_w, a.g_b, 1, 64);
     return stif_check_launch("stif_dcn_bwd_nhwc (reduce)");
   }
   return STIF_OK;

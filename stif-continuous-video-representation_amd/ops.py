@@ -209,32 +209,82 @@ def conv2d(groups, *, epi=L.EPI_NONE, in1_mode=0, in1_scale=1.0, stride=None, st
         _launch("stif_conv2d_nhwc", trace, L.lib().stif_conv2d_nhwc, C.byref(a), _stream())
 
 
+def _pack_dev(what: str, weight, bias, mode: int, cout: int, cin: int, ks: int):
+    """The front end of the four device packers: ``weight`` / ``bias`` (or None) checked as float32 CUDA tensors and
+    made contiguous, and the PackedConv of a [cout, cin, ks, ks] layer in ``mode`` with its buffers sized by the
+    library.  Returns (lib, weight, bias, layer); the caller launches its entry into ``layer.w`` / ``layer.b``."""
+    if not (weight.is_cuda and weight.dtype == torch.float32):
+        raise ValueError(f"{what}: expected a float32 CUDA weight")
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
+        raise ValueError(f"{what}: expected a float32 CUDA bias")
+    weight = weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    lib = L.lib()
+    wd = torch.empty(lib.stif_conv_weight_floats(cout, cin, ks, mode), dtype=torch.float32, device=weight.device)
+    bd = torch.empty(lib.stif_conv_bias_floats(cout, mode), dtype=torch.float32, device=weight.device)
+    return lib, weight, bias, PackedConv(wd, bd, cout, cin, ks, mode)
+
+
 def pack_conv_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mode: int = L.PACK_WINO, dgrad: bool = False,
                   status: Optional[torch.Tensor] = None) -> PackedConv:
     """The Winograd packing of a 64 -> 64 3x3 layer on the device (stif_pack_conv_weight_dev): ``weight`` [64,64,3,3]
     and ``bias`` [64] are device tensors and nothing passes through the host.  ``dgrad``: the data gradient's weight
     (transposed and rotated, zero bias; ``bias`` may be None).  With ``PACK_F16X3`` a weight outside the split-fp16
     range sets ``STATUS_PACK_RANGE`` in the int32 device word ``status`` (required then) instead of raising."""
-    if not (weight.is_cuda and weight.dtype == torch.float32):
-        raise ValueError("pack_conv_dev: expected a float32 CUDA weight")
-    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
-        raise ValueError("pack_conv_dev: expected a float32 CUDA bias")
     if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
         raise ValueError(f"pack_conv_dev: weight shape {tuple(weight.shape)} is not [cout, cin, k, k]")
-    weight = weight.detach().contiguous()
-    bias = None if bias is None else bias.detach().contiguous()
     cout, cin, ks, _ = weight.shape
-    lib = L.lib()
-    wd = torch.empty(lib.stif_conv_weight_floats(cout, cin, ks, mode), dtype=torch.float32, device=weight.device)
-    bd = torch.empty(lib.stif_conv_bias_floats(cout, mode), dtype=torch.float32, device=weight.device)
-    _launch("stif_pack_conv_weight_dev", None, lib.stif_pack_conv_weight_dev, _vp(weight), _vp(bias), cout, cin, ks,
-            mode, L.PACK_DGRAD if dgrad else 0, _vp(wd), _vp(bd), _vp(status), _stream())
-    return PackedConv(wd, bd, cin if dgrad else cout, cout if dgrad else cin, ks, mode)
+    lib, w, b, lay = _pack_dev("pack_conv_dev", weight, bias, mode, cin if dgrad else cout, cout if dgrad else cin, ks)
+    _launch("stif_pack_conv_weight_dev", None, lib.stif_pack_conv_weight_dev, _vp(w), _vp(b), cout, cin, ks, mode,
+            L.PACK_DGRAD if dgrad else 0, _vp(lay.w), _vp(lay.b), _vp(status), _stream())
+    return lay
 
 
-# stif_conv3x3_wgrad's workspace (the workgroups' partial sums): one buffer per (device, stream), grown on demand;
+# The weight gradients' workspace (the workgroups' partial sums): one buffer per (device, stream), grown on demand;
 # launches on one stream run in issue order, launches on different streams never share one
 _WGRAD_WS = {}
+
+
+def _wgrad_workspace(device, nbytes: int):
+    """The (device, stream) partial-sum buffer grown to ``nbytes``: every weight-gradient reduction shares it (each
+    finishes its reduce before the next launch on the stream starts)."""
+    s = torch.cuda.current_stream(device)
+    key = (s.device.index, s.cuda_stream)
+    ws = _WGRAD_WS.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _WGRAD_WS[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=device)
+    return ws, s.cuda_stream
+
+
+def _wgrad_call(entry: str, fn, nbytes: int, a, gy: torch.Tensor, gw_shape, trace):
+    """What the struct-taking weight-gradient wrappers share once their maps are checked and ``a`` (ConvWgradArgs or
+    ConvWgradCatArgs) holds the x maps, the item strides and the sizes: the workspace of ``nbytes``, gw [gw_shape] and
+    gb, the rest of ``a`` and the launch of the library entry ``fn``.  Returns (gw, gb)."""
+    ws, stream = _wgrad_workspace(gy.device, nbytes)
+    gw = torch.empty(gw_shape, dtype=torch.float32, device=gy.device)
+    gb = torch.empty(gw_shape[0], dtype=torch.float32, device=gy.device)
+    a.gy, a.gw, a.gb = _vp(gy), _vp(gw), _vp(gb)
+    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
+    _launch(entry, trace, fn, C.byref(a), stream)
+    return gw, gb
+
+
+def _wgrad64_args(what_x: str, what_gy: str, x, gy):
+    """ConvWgradArgs of a 64 -> 64 weight gradient: the maps' item strides (checked) and the sizes of ``x``."""
+    a = L.ConvWgradArgs()
+    a.x, a.x_item, a.gy_item = _vp(x), _item_stride([x], what_x), _item_stride([gy], what_gy)
+    a.n, a.H, a.W, a.cin, a.cout = x.shape[0], x.shape[1], x.shape[2], 64, 64
+    return a
+
+
+def _wgrad_cat_args(what_x: str, what_gy: str, xs, gy, cout: int):
+    """ConvWgradCatArgs of a weight gradient on one or two 64-channel x maps: item strides (checked) and sizes."""
+    a = L.ConvWgradCatArgs()
+    for i, x in enumerate(xs):
+        a.x[i], a.x_item[i] = _vp(x), _item_stride([x], what_x)
+    a.gy_item = _item_stride([gy], what_gy)
+    a.n, a.H, a.W, a.nx, a.gy_channels, a.cout = gy.shape[0], gy.shape[1], gy.shape[2], len(xs), gy.shape[3], cout
+    return a
 
 
 def conv3x3_wgrad(x: torch.Tensor, gy: torch.Tensor):
@@ -244,39 +294,12 @@ def conv3x3_wgrad(x: torch.Tensor, gy: torch.Tensor):
     identical bits (no atomics)."""
     if x.dim() != 4 or x.shape != gy.shape or x.shape[3] != 64:
         raise ValueError(f"conv3x3_wgrad: x {tuple(x.shape)} and gy {tuple(gy.shape)} must both be [n, H, W, 64]")
-    x_item = _item_stride([x], "conv3x3_wgrad x")
-    gy_item = _item_stride([gy], "conv3x3_wgrad gy")
     n, H, W, _ = x.shape
+    trace = None if TRACE is None else (("wgrad",), 2.0 * 64 * 64 * 9 * n * H * W, 4.0 * 2 * 64 * n * H * W)
     lib = L.lib()
-    nbytes = lib.stif_conv3x3_wgrad_workspace_size(n, H, W, 64, 64)
-    s = torch.cuda.current_stream(x.device)
-    key = (s.device.index, s.cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _WGRAD_WS[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
-    gw = torch.empty(64, 64, 3, 3, dtype=torch.float32, device=x.device)
-    gb = torch.empty(64, dtype=torch.float32, device=x.device)
-    a = L.ConvWgradArgs()
-    a.x, a.gy, a.gw, a.gb = _vp(x), _vp(gy), _vp(gw), _vp(gb)
-    a.x_item, a.gy_item = x_item, gy_item
-    a.n, a.H, a.W, a.cin, a.cout = n, H, W, 64, 64
-    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
-    trace = None
-    if TRACE is not None:
-        trace = (("wgrad",), 2.0 * 64 * 64 * 9 * n * H * W, 4.0 * 2 * 64 * n * H * W)
-    _launch("stif_conv3x3_wgrad", trace, lib.stif_conv3x3_wgrad, C.byref(a), s.cuda_stream)
-    return gw, gb
-
-
-def _wgrad_workspace(device, nbytes: int):
-    """The (device, stream) partial-sum buffer conv3x3_wgrad uses, grown to ``nbytes``: the three weight-gradient
-    reductions share it (each finishes its reduce before the next launch on the stream starts)."""
-    s = torch.cuda.current_stream(device)
-    key = (s.device.index, s.cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _WGRAD_WS[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=device)
-    return ws, s.cuda_stream
+    a = _wgrad64_args("conv3x3_wgrad x", "conv3x3_wgrad gy", x, gy)
+    return _wgrad_call("stif_conv3x3_wgrad", lib.stif_conv3x3_wgrad,
+                       lib.stif_conv3x3_wgrad_workspace_size(n, H, W, 64, 64), a, gy, (64, 64, 3, 3), trace)
 
 
 def conv3x3s2_wgrad(x: torch.Tensor, gy: torch.Tensor):
@@ -288,23 +311,12 @@ def conv3x3s2_wgrad(x: torch.Tensor, gy: torch.Tensor):
     n, H, W, _ = x.shape
     if tuple(gy.shape) != (n, (H + 1) // 2, (W + 1) // 2, 64):
         raise ValueError(f"conv3x3s2_wgrad: gy {tuple(gy.shape)} is not the stride-2 output of x {tuple(x.shape)}")
-    x_item = _item_stride([x], "conv3x3s2_wgrad x")
-    gy_item = _item_stride([gy], "conv3x3s2_wgrad gy")
+    px = n * gy.shape[1] * gy.shape[2]
+    trace = None if TRACE is None else (("wgrad_s2",), 2.0 * 64 * 64 * 9 * px, 4.0 * 64 * (n * H * W + px))
     lib = L.lib()
-    ws, stream = _wgrad_workspace(x.device, lib.stif_conv3x3s2_wgrad_workspace_size(n, H, W, 64, 64))
-    gw = torch.empty(64, 64, 3, 3, dtype=torch.float32, device=x.device)
-    gb = torch.empty(64, dtype=torch.float32, device=x.device)
-    a = L.ConvWgradArgs()
-    a.x, a.gy, a.gw, a.gb = _vp(x), _vp(gy), _vp(gw), _vp(gb)
-    a.x_item, a.gy_item = x_item, gy_item
-    a.n, a.H, a.W, a.cin, a.cout = n, H, W, 64, 64
-    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
-    trace = None
-    if TRACE is not None:
-        px = n * gy.shape[1] * gy.shape[2]
-        trace = (("wgrad_s2",), 2.0 * 64 * 64 * 9 * px, 4.0 * 64 * (n * H * W + px))
-    _launch("stif_conv3x3s2_wgrad", trace, lib.stif_conv3x3s2_wgrad, C.byref(a), stream)
-    return gw, gb
+    a = _wgrad64_args("conv3x3s2_wgrad x", "conv3x3s2_wgrad gy", x, gy)
+    return _wgrad_call("stif_conv3x3s2_wgrad", lib.stif_conv3x3s2_wgrad,
+                       lib.stif_conv3x3s2_wgrad_workspace_size(n, H, W, 64, 64), a, gy, (64, 64, 3, 3), trace)
 
 
 def conv3x3s2_dgrad(gy: torch.Tensor, weight: torch.Tensor, H: int, W: int) -> torch.Tensor:
@@ -343,9 +355,8 @@ def conv_first_wgrad(x_nchw: torch.Tensor, gy: torch.Tensor):
     ws, stream = _wgrad_workspace(gy.device, lib.stif_conv_first_wgrad_workspace_size(n, h, w))
     gw = torch.empty(64, 3, 3, 3, dtype=torch.float32, device=gy.device)
     gb = torch.empty(64, dtype=torch.float32, device=gy.device)
-    trace = None
-    if TRACE is not None:
-        trace = (("cf_wgrad",), 2.0 * 64 * 28 * n * h * w, 4.0 * (64 + 3) * n * h * w)
+    trace = None if TRACE is None else (("cf_wgrad",), 2.0 * 64 * 28 * n * h * w, 4.0 * (64 + 3) * n * h * w)
+    # the one entry without an argument struct (NCHW frames, no x stride): it shares the workspace only
     _launch("stif_conv_first_wgrad", trace, lib.stif_conv_first_wgrad, _vp(x_nchw), _vp(gy), _vp(gw), _vp(gb), gy_item,
             n, h, w, _vp(ws), ws.numel() * 4, stream)
     return gw, gb
@@ -354,21 +365,13 @@ def conv_first_wgrad(x_nchw: torch.Tensor, gy: torch.Tensor):
 def pack_conv_plain_dev(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> PackedConv:
     """The fp32 direct-conv (PACK_PLAIN) packing of a 64 -> 64 3x3 layer on the device (stif_pack_conv_plain_dev):
     the bytes ops.pack_conv writes, with nothing passing through the host -- the layer ops.conv2d(stride=2) reads."""
-    if not (weight.is_cuda and weight.dtype == torch.float32):
-        raise ValueError("pack_conv_plain_dev: expected a float32 CUDA weight")
-    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
-        raise ValueError("pack_conv_plain_dev: expected a float32 CUDA bias")
     if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
         raise ValueError(f"pack_conv_plain_dev: weight shape {tuple(weight.shape)} is not [cout, cin, k, k]")
-    weight = weight.detach().contiguous()
-    bias = None if bias is None else bias.detach().contiguous()
     cout, cin, ks, _ = weight.shape
-    lib = L.lib()
-    wd = torch.empty(lib.stif_conv_weight_floats(cout, cin, ks, L.PACK_PLAIN), dtype=torch.float32, device=weight.device)
-    bd = torch.empty(lib.stif_conv_bias_floats(cout, L.PACK_PLAIN), dtype=torch.float32, device=weight.device)
-    _launch("stif_pack_conv_plain_dev", None, lib.stif_pack_conv_plain_dev, _vp(weight), _vp(bias), cout, cin, ks,
-            _vp(wd), _vp(bd), _stream())
-    return PackedConv(wd, bd, cout, cin, ks, L.PACK_PLAIN)
+    lib, w, b, lay = _pack_dev("pack_conv_plain_dev", weight, bias, L.PACK_PLAIN, cout, cin, ks)
+    _launch("stif_pack_conv_plain_dev", None, lib.stif_pack_conv_plain_dev, _vp(w), _vp(b), cout, cin, ks,
+            _vp(lay.w), _vp(lay.b), _stream())
+    return lay
 
 
 def upsample2x(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0):
@@ -414,23 +417,30 @@ def conv3x3_wgrad_cat(xs, gy: torch.Tensor, cout: int):
     nx = len(xs)
     if (nx, gc, cout) not in ((2, 64, 64), (1, 256, 216), (1, 64, 64), (2, 256, 256)):
         raise ValueError(f"conv3x3_wgrad_cat: unsupported channel counts (nx, gy channels, cout) = {(nx, gc, cout)}")
-    lib = L.lib()
-    a = L.ConvWgradCatArgs()
-    for i, x in enumerate(xs):
-        a.x[i], a.x_item[i] = _vp(x), _item_stride([x], "conv3x3_wgrad_cat x")
-    gy_item = _item_stride([gy], "conv3x3_wgrad_cat gy")
-    ws, stream = _wgrad_workspace(gy.device, lib.stif_conv3x3_wgrad_cat_workspace_size(n, H, W, nx, gc, cout))
-    gw = torch.empty(cout, 64 * nx, 3, 3, dtype=torch.float32, device=gy.device)
-    gb = torch.empty(cout, dtype=torch.float32, device=gy.device)
-    a.gy, a.gw, a.gb, a.gy_item = _vp(gy), _vp(gw), _vp(gb), gy_item
-    a.n, a.H, a.W, a.nx, a.gy_channels, a.cout = n, H, W, nx, gc, cout
-    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
     trace = None
     if TRACE is not None:
         blocks = nx * ((cout + 63) // 64)
         trace = (("wgrad_cat", nx, cout), 2.0 * cout * 64 * nx * 9 * n * H * W, 4.0 * (64 * blocks + cout) * n * H * W)
-    _launch("stif_conv3x3_wgrad_cat", trace, lib.stif_conv3x3_wgrad_cat, C.byref(a), stream)
-    return gw, gb
+    lib = L.lib()
+    a = _wgrad_cat_args("conv3x3_wgrad_cat x", "conv3x3_wgrad_cat gy", xs, gy, cout)
+    return _wgrad_call("stif_conv3x3_wgrad_cat", lib.stif_conv3x3_wgrad_cat,
+                       lib.stif_conv3x3_wgrad_cat_workspace_size(n, H, W, nx, gc, cout), a, gy, (cout, 64 * nx, 3, 3),
+                       trace)
+
+
+# pack_conv_blocks_dev's forms: (weight [cout, cin], dgrad, half) -> (the PackedConv's cout and cin, the (co0, ci0)
+# of its 64 x 64 blocks in buffer order)
+_ROWS4 = tuple(64 * s for s in range(4))
+_BLOCK_FORMS = {
+    ((64, 128), False, None): (64, 128, ((0, 0), (0, 64))),
+    ((216, 64), False, None): (256, 64, tuple((r, 0) for r in _ROWS4)),
+    ((216, 64), True, None): (64, 256, tuple((r, 0) for r in _ROWS4)),
+    ((64, 128), True, 0): (64, 64, ((0, 0),)),
+    ((64, 128), True, 1): (64, 64, ((0, 64),)),
+    ((256, 128), False, None): (256, 128, tuple((r, c) for r in _ROWS4 for c in (0, 64))),
+    ((256, 128), True, 0): (64, 256, tuple((r, 0) for r in _ROWS4)),
+    ((256, 128), True, 1): (64, 256, tuple((r, 64) for r in _ROWS4)),
+}
 
 
 def pack_conv_blocks_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mode: int = L.PACK_WINO,
@@ -450,37 +460,19 @@ def pack_conv_blocks_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mod
       DGRAD row blocks.
 
     ``bias`` may be None with ``dgrad`` (the bias is zero then); ``status`` as ops.pack_conv_dev."""
-    if not (weight.is_cuda and weight.dtype == torch.float32):
-        raise ValueError("pack_conv_blocks_dev: expected a float32 CUDA weight")
-    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
-        raise ValueError("pack_conv_blocks_dev: expected a float32 CUDA bias")
     shape = tuple(weight.shape)
-    if shape == (64, 128, 3, 3) and not dgrad and half is None:
-        blocks, cout, cin = [(0, 0), (0, 64)], 64, 128
-    elif shape == (216, 64, 3, 3) and half is None:
-        blocks = [(64 * s, 0) for s in range(4)]
-        cout, cin = (64, 256) if dgrad else (256, 64)
-    elif shape == (64, 128, 3, 3) and dgrad and half in (0, 1):
-        blocks, cout, cin = [(0, 64 * half)], 64, 64
-    elif shape == (256, 128, 3, 3) and not dgrad and half is None:
-        blocks, cout, cin = [(64 * s, 64 * c) for s in range(4) for c in range(2)], 256, 128
-    elif shape == (256, 128, 3, 3) and dgrad and half in (0, 1):
-        blocks, cout, cin = [(64 * s, 64 * half) for s in range(4)], 64, 256
-    else:
+    form = _BLOCK_FORMS.get((shape[:2], bool(dgrad), half)) if shape[2:] == (3, 3) else None
+    if form is None:
         raise ValueError(f"pack_conv_blocks_dev: no block form for weight {shape}, dgrad={dgrad}, half={half}")
-    weight = weight.detach().contiguous()
-    bias = None if bias is None else bias.detach().contiguous()
-    lib = L.lib()
-    per = lib.stif_conv_weight_floats(64, 64, 3, mode)
-    wd = torch.empty(per * len(blocks), dtype=torch.float32, device=weight.device)
-    bd = torch.empty(lib.stif_conv_bias_floats(cout, mode), dtype=torch.float32, device=weight.device)
+    cout, cin, blocks = form
+    lib, w, b, lay = _pack_dev("pack_conv_blocks_dev", weight, bias, mode, cout, cin, 3)
+    per = lay.w.numel() // len(blocks)
     for i, (co0, ci0) in enumerate(blocks):
         # the blocks of one cout slice share its 64 biases; a row block has its own
-        bi = bd[co0:co0 + 64] if cout == 256 else bd
-        _launch("stif_pack_conv_block_dev", None, lib.stif_pack_conv_block_dev, _vp(weight), _vp(bias), shape[0],
-                shape[1], co0, ci0, mode, L.PACK_DGRAD if dgrad else 0, _vp(wd[i * per:]), _vp(bi), _vp(status),
-                _stream())
-    return PackedConv(wd, bd, cout, cin, 3, mode)
+        bi = lay.b[co0:co0 + 64] if cout == 256 else lay.b
+        _launch("stif_pack_conv_block_dev", None, lib.stif_pack_conv_block_dev, _vp(w), _vp(b), shape[0], shape[1],
+                co0, ci0, mode, L.PACK_DGRAD if dgrad else 0, _vp(lay.w[i * per:]), _vp(bi), _vp(status), _stream())
+    return lay
 
 
 def conv1x1_wgrad(xs, gy: torch.Tensor):
@@ -494,22 +486,12 @@ def conv1x1_wgrad(xs, gy: torch.Tensor):
                          f"{[tuple(x.shape) for x in xs]} and {tuple(gy.shape)}")
     n, H, W, _ = gy.shape
     nx = len(xs)
+    trace = None if TRACE is None else (("wgrad_1x1", nx), 2.0 * 64 * 64 * nx * n * H * W,
+                                        4.0 * 64 * (1 + nx) * n * H * W)
     lib = L.lib()
-    a = L.ConvWgradCatArgs()
-    for i, x in enumerate(xs):
-        a.x[i], a.x_item[i] = _vp(x), _item_stride([x], "conv1x1_wgrad x")
-    gy_item = _item_stride([gy], "conv1x1_wgrad gy")
-    ws, stream = _wgrad_workspace(gy.device, lib.stif_conv1x1_wgrad_workspace_size(n, H, W, nx))
-    gw = torch.empty(64, 64 * nx, 1, 1, dtype=torch.float32, device=gy.device)
-    gb = torch.empty(64, dtype=torch.float32, device=gy.device)
-    a.gy, a.gw, a.gb, a.gy_item = _vp(gy), _vp(gw), _vp(gb), gy_item
-    a.n, a.H, a.W, a.nx, a.gy_channels, a.cout = n, H, W, nx, 64, 64
-    a.workspace, a.workspace_bytes = _vp(ws), ws.numel() * 4
-    trace = None
-    if TRACE is not None:
-        trace = (("wgrad_1x1", nx), 2.0 * 64 * 64 * nx * n * H * W, 4.0 * 64 * (1 + nx) * n * H * W)
-    _launch("stif_conv1x1_wgrad", trace, lib.stif_conv1x1_wgrad, C.byref(a), stream)
-    return gw, gb
+    a = _wgrad_cat_args("conv1x1_wgrad x", "conv1x1_wgrad gy", xs, gy, 64)
+    return _wgrad_call("stif_conv1x1_wgrad", lib.stif_conv1x1_wgrad, lib.stif_conv1x1_wgrad_workspace_size(n, H, W, nx),
+                       a, gy, (64, 64 * nx, 1, 1), trace)
 
 
 def pack_conv1x1_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mode: int = L.PACK_PLAIN, dgrad: bool = False,
@@ -518,21 +500,13 @@ def pack_conv1x1_dev(weight: torch.Tensor, bias: Optional[torch.Tensor], mode: i
     ``mode`` PACK_PLAIN or PACK_PLAIN | PACK_F16X3 -- the bytes of ops.pack_conv, the layer ops.conv2d(in1_mode=1)
     reads.  ``dgrad`` with ``half`` = 0 or 1: the fp32 pack of the transposed 64 -> 64 layer of that input half (zero
     bias; ``bias`` may be None).  ``status`` as ops.pack_conv_dev."""
-    if not (weight.is_cuda and weight.dtype == torch.float32):
-        raise ValueError("pack_conv1x1_dev: expected a float32 CUDA weight")
-    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32):
-        raise ValueError("pack_conv1x1_dev: expected a float32 CUDA bias")
     if tuple(weight.shape) != (64, 128, 1, 1) or (half is not None) != dgrad or half not in (None, 0, 1):
         raise ValueError(f"pack_conv1x1_dev: no form for weight {tuple(weight.shape)}, dgrad={dgrad}, half={half}")
-    weight = weight.detach().contiguous()
-    bias = None if bias is None else bias.detach().contiguous()
-    cin = 64 if dgrad else 128
-    lib = L.lib()
-    wd = torch.empty(lib.stif_conv_weight_floats(64, cin, 1, mode), dtype=torch.float32, device=weight.device)
-    bd = torch.empty(lib.stif_conv_bias_floats(64, mode), dtype=torch.float32, device=weight.device)
-    _launch("stif_pack_conv1x1_dev", None, lib.stif_pack_conv1x1_dev, _vp(weight), _vp(bias), 64, 128,
-            64 * half if dgrad else 0, mode, L.PACK_DGRAD if dgrad else 0, _vp(wd), _vp(bd), _vp(status), _stream())
-    return PackedConv(wd, bd, 64, cin, 1, mode)
+    lib, w, b, lay = _pack_dev("pack_conv1x1_dev", weight, bias, mode, 64, 64 if dgrad else 128, 1)
+    _launch("stif_pack_conv1x1_dev", None, lib.stif_pack_conv1x1_dev, _vp(w), _vp(b), 64, 128,
+            64 * half if dgrad else 0, mode, L.PACK_DGRAD if dgrad else 0, _vp(lay.w), _vp(lay.b), _vp(status),
+            _stream())
+    return lay
 
 
 def _lstm_maps(what, pre, maps):

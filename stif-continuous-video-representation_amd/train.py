@@ -219,10 +219,12 @@ _STATUS = {}   # device index -> the int32 status word every module on that devi
 
 
 def _status_word(device) -> torch.Tensor:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    s = _STATUS.get(idx)
+    s = _STATUS.get(device.index)     # a tensor's device carries its index: one lookup per conv
     if s is None:
-        s = _STATUS[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        s = _STATUS.get(idx)
+        if s is None:
+            s = _STATUS[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
     return s
 
 
@@ -238,12 +240,19 @@ def range_status(device=None) -> int:
     return bits
 
 
+def _need_cuda(who: str, *tensors) -> None:
+    """The one refusal of CPU tensors, before any launch."""
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
+                               "(move the module and its input to the GPU)")
+
+
 def _nhwc(t: torch.Tensor, what: str, channels=64) -> torch.Tensor:
     """The NHWC buffer of a logical NCHW tensor: a ``channels_last`` tensor is used in place (its memory is
     NHWC), anything else is converted once.  ``channels`` None: any positive multiple of 4."""
     if not t.is_cuda:
-        raise RuntimeError(f"{what}: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
-                           "(move the module and its input to the GPU)")
+        _need_cuda(what, t)
     if channels is None and (t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] % 4 or t.shape[1] < 4):
         raise RuntimeError(f"{what}: expected a float32 [n, 4k, H, W] tensor, got {t.dtype} {tuple(t.shape)}")
     if channels is not None and (t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != channels):
@@ -252,41 +261,129 @@ def _nhwc(t: torch.Tensor, what: str, channels=64) -> torch.Tensor:
     return v if v.is_contiguous() else v.contiguous()
 
 
-def _wino(x, weight, bias, mode, epi=L.EPI_NONE, res=None, dgrad=False):
-    """stif_conv3x3_wino of NHWC ``x`` with ``weight`` packed on the device for this call (``dgrad``: the data
-    gradient's packing, so ``x`` is a grad_output and the result a grad_input); returns a new NHWC tensor."""
+def _nchw(t):
+    """The logical NCHW view of an NHWC buffer (``channels_last`` memory); None stays None."""
+    return None if t is None else t.permute(0, 3, 1, 2)
+
+
+def _same_shape(who: str, first, *others) -> None:
+    """The inputs of a node (logical NCHW) must have one shape."""
+    for m in others:
+        if m.shape != first.shape:
+            raise RuntimeError(f"{who}: the inputs differ in shape: "
+                               + ", ".join(str(tuple(t.shape)) for t in (first,) + others))
+
+
+def _act_grad(g, out, act):
+    """The gradient before a fused activation from the gradient after it and the activation's saved output: both
+    activations keep the sign of their argument."""
+    if act == "relu":
+        return g * (out > 0)
+    if act == "lrelu":
+        return torch.where(out > 0, g, g * 0.1)
+    return g
+
+
+def _grads(needs, *values) -> tuple:
+    """A backward's result: ``values[i]`` where input i needs a gradient, None where it does not and for every input
+    past the values (the options)."""
+    out = [None] * len(needs)
+    for i, v in enumerate(values):
+        if needs[i]:
+            out[i] = v
+    return tuple(out)
+
+
+def _wino(x, weight, bias, mode, epi=L.EPI_NONE, res=None):
+    """stif_conv3x3_wino of NHWC ``x`` with the 64 -> 64 ``weight`` packed on the device for this call; returns a new
+    NHWC tensor."""
     status = _status_word(x.device)
-    lay = ops.pack_conv_dev(weight, bias, mode, dgrad=dgrad, status=status)
+    lay = ops.pack_conv_dev(weight, bias, mode, status=status)
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     ops.conv2d([dict(layer=lay, in0=x, out=out, res=res)], epi=epi, status=status)
     return out
 
 
-class _Conv3x3Fn(torch.autograd.Function):
+def _conv_dgrad(g, weight, mode, *, half=None, res=None, epi=L.EPI_NONE):
+    """The data gradient of a stride-1 conv as a conv of NHWC ``g`` (the gradient of its output) with ``weight``
+    packed on the device in its data-gradient form; returns a new NHWC [n, H, W, 64] tensor.  The form follows the
+    weight: [64, 64, 3, 3] (64 -> 64), [64, 128, 3, 3] ((64 | 64) -> 64), [216, 64, 3, 3] (g the zero-padded 256-channel
+    map) and [256, 128, 3, 3] ((64 | 64) -> 256) on stif_conv3x3_wino in ``mode``, [64, 128, 1, 1] as an fp32 1x1 conv
+    without a status word (the split-fp16 1x1 kernel takes the (64 | 64) and 200-channel inputs only).  ``half``: which
+    input of a two-input conv; ``res`` / ``epi``: the conv's epilogue."""
+    if weight.shape[2] == 1:
+        status, lay = None, ops.pack_conv1x1_dev(weight, None, L.PACK_PLAIN, dgrad=True, half=half)
+    else:
+        status = _status_word(g.device)
+        if tuple(weight.shape[:2]) == (64, 64):
+            lay = ops.pack_conv_dev(weight, None, mode, dgrad=True, status=status)
+        else:
+            lay = ops.pack_conv_blocks_dev(weight, None, mode, dgrad=True, half=half, status=status)
+    gx = torch.empty(tuple(g.shape[:3]) + (64,), dtype=torch.float32, device=g.device)
+    ops.conv2d([dict(layer=lay, in0=g, out=gx, res=res)], epi=epi, status=status)
+    return gx
+
+
+def _conv2d_params(cout, cin, ks, init="conv2d"):
+    """``weight`` [cout, cin, ks, ks] and ``bias`` [cout] of an nn.Conv2d as parameters, with its default
+    initialisation (the weight is drawn first) or, ``init="zeros"``, zeros."""
+    if init == "zeros":
+        return nn.Parameter(torch.zeros(cout, cin, ks, ks)), nn.Parameter(torch.zeros(cout))
+    weight, bias = nn.Parameter(torch.empty(cout, cin, ks, ks)), nn.Parameter(torch.empty(cout))
+    nn.init.kaiming_uniform_(weight, a=math.sqrt(5))
+    bound = 1.0 / math.sqrt(cin * ks * ks)
+    nn.init.uniform_(bias, -bound, bound)
+    return weight, bias
+
+
+class _RangeStatus:
+    """``module.range_status()``: ``train.range_status`` of the device of the module's first parameter."""
+
+    def range_status(self) -> int:
+        return range_status(next(self.parameters()).device)
+
+
+class _ConvFn(torch.autograd.Function):
+    """The stride-1 conv of one or two 64-channel inputs (``b`` None: one) to 64 channels with an optional fused
+    activation.  The kernel size and the packing follow the weight: [64, 64, 3, 3] and [64, 128, 3, 3] run on
+    stif_conv3x3_wino, [64, 128, 1, 1] on stif_conv2d_nhwc.  ``who`` names the module in messages."""
+
     @staticmethod
-    def forward(ctx, x, weight, bias, act, mode):
-        xh = _nhwc(x, "Conv3x3")
-        out = _wino(xh, weight, bias, mode, _EPI[act])
-        ctx.act, ctx.mode = act, mode
-        ctx.save_for_backward(xh, weight, out if act else None)
+    def forward(ctx, who, a, b, weight, bias, act, mode):
+        ah = _nhwc(a, who)
+        status = _status_word(ah.device)
+        out = torch.empty(ah.shape, dtype=torch.float32, device=ah.device)
+        if b is None:
+            lay = ops.pack_conv_dev(weight, bias, mode, status=status)
+            ops.conv2d([dict(layer=lay, in0=ah, out=out)], epi=_EPI[act], status=status)
+            ctx.save_for_backward(weight, out if act else None, ah)
+        else:
+            bh = _nhwc(b, who)
+            _same_shape(who, a, b)
+            pack = ops.pack_conv1x1_dev if weight.shape[2] == 1 else ops.pack_conv_blocks_dev
+            lay = pack(weight, bias, mode, status=status)
+            ops.conv2d([dict(layer=lay, in0=ah, in1=bh, out=out)], epi=_EPI[act], in1_mode=1, status=status)
+            ctx.save_for_backward(weight, out if act else None, ah, bh)
+        ctx.who, ctx.act, ctx.mode = who, act, mode
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, grad_out):
-        xh, weight, out = ctx.saved_tensors
-        g = _nhwc(grad_out, "Conv3x3 backward")
-        # the activation's derivative from its output: both activations keep the sign of their argument
-        if ctx.act == "relu":
-            g = g * (out > 0)
-        elif ctx.act == "lrelu":
-            g = torch.where(out > 0, g, g * 0.1)
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        gx = gw = gb = None
-        if need_w or need_b:
-            gw, gb = ops.conv3x3_wgrad(xh, g)
-        if need_x:
-            gx = _wino(g, weight, None, ctx.mode, dgrad=True).permute(0, 3, 1, 2)
-        return gx, gw if need_w else None, gb if need_b else None, None, None
+        weight, out, *xs = ctx.saved_tensors
+        g = _act_grad(_nhwc(grad_out, ctx.who + " backward"), out, ctx.act)
+        needs = ctx.needs_input_grad
+        gw = gb = None
+        if needs[3] or needs[4]:
+            if weight.shape[2] == 1:
+                gw, gb = ops.conv1x1_wgrad(xs, g)
+            elif len(xs) == 1:
+                gw, gb = ops.conv3x3_wgrad(xs[0], g)
+            else:
+                gw, gb = ops.conv3x3_wgrad_cat(xs, g, 64)
+        two = len(xs) == 2
+        ga = _nchw(_conv_dgrad(g, weight, ctx.mode, half=0 if two else None)) if needs[1] else None
+        gb2 = _nchw(_conv_dgrad(g, weight, ctx.mode, half=1)) if two and needs[2] else None
+        return _grads(needs, None, ga, gb2, gw, gb)
 
 
 class _ResBlockFn(torch.autograd.Function):
@@ -300,7 +397,7 @@ class _ResBlockFn(torch.autograd.Function):
         out = _wino(t, w2, b2, mode, L.EPI_RES, res=xh)
         ctx.mode = mode
         ctx.save_for_backward(xh, t, w1, w2)
-        return out.permute(0, 3, 1, 2)
+        return _nchw(out)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -311,13 +408,12 @@ class _ResBlockFn(torch.autograd.Function):
         if need_w2 or need_b2:
             gw2, gb2 = ops.conv3x3_wgrad(t, g)
         if need_x or need_w1 or need_b1:
-            gt = _wino(g, w2, None, ctx.mode, dgrad=True) * (t > 0)
+            gt = _act_grad(_conv_dgrad(g, w2, ctx.mode), t, "relu")
             if need_w1 or need_b1:
                 gw1, gb1 = ops.conv3x3_wgrad(xh, gt)
             if need_x:
-                gx = _wino(gt, w1, None, ctx.mode, L.EPI_RES, res=g, dgrad=True).permute(0, 3, 1, 2)
-        return (gx, gw1 if need_w1 else None, gb1 if need_b1 else None, gw2 if need_w2 else None,
-                gb2 if need_b2 else None, None)
+                gx = _nchw(_conv_dgrad(gt, w1, ctx.mode, res=g, epi=L.EPI_RES))
+        return _grads(ctx.needs_input_grad, gx, gw1, gb1, gw2, gb2)
 
 
 def _check_choice(nf, act, mfma):
@@ -329,7 +425,7 @@ def _check_choice(nf, act, mfma):
         raise ValueError(f"mfma must be 'f16x3' or 'f32', got {mfma!r}")
 
 
-class Conv3x3(nn.Module):
+class Conv3x3(_RangeStatus, nn.Module):
     """nn.Conv2d(64, 64, 3, 1, 1) with an optional fused ReLU / LeakyReLU(0.1), forward and backward on the HIP
     kernels.  ``weight`` [64, 64, 3, 3] and ``bias`` [64] carry nn.Conv2d's names, shapes and default
     initialisation.  Input and output are logical NCHW; the output is ``channels_last``, and a ``channels_last``
@@ -339,23 +435,16 @@ class Conv3x3(nn.Module):
         super().__init__()
         _check_choice(nf, act, mfma)
         self.act, self.mfma = act, mfma
-        self.weight = nn.Parameter(torch.empty(nf, nf, 3, 3))
-        self.bias = nn.Parameter(torch.empty(nf))
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(nf * 9)
-        nn.init.uniform_(self.bias, -bound, bound)
+        self.weight, self.bias = _conv2d_params(nf, nf, 3)
 
     def forward(self, x):
-        return _Conv3x3Fn.apply(x, self.weight, self.bias, self.act, _PACK[self.mfma])
-
-    def range_status(self) -> int:
-        return range_status(self.weight.device)
+        return _ConvFn.apply("Conv3x3", x, None, self.weight, self.bias, self.act, _PACK[self.mfma])
 
     def extra_repr(self):
         return f"64, 64, kernel_size=(3, 3), padding=1, act={self.act}, mfma={self.mfma}"
 
 
-class ResidualBlock_noBN(nn.Module):
+class ResidualBlock_noBN(_RangeStatus, nn.Module):
     """module_util.py:34-52: identity + conv2(relu(conv1(x))), submodules ``conv1`` / ``conv2`` as in the
     reference (kaiming-normal weights scaled by 0.1, zero biases), one autograd node on the HIP kernels."""
 
@@ -374,9 +463,6 @@ class ResidualBlock_noBN(nn.Module):
     def forward(self, x):
         return _ResBlockFn.apply(x, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
                                  _PACK[self.mfma])
-
-    def range_status(self) -> int:
-        return range_status(self.conv1.weight.device)
 
 
 def make_trunk(n_blocks: int, nf: int = 64, mfma: str = "f16x3") -> nn.Sequential:
@@ -400,21 +486,16 @@ class _ConvDownFn(torch.autograd.Function):
         ops.conv2d([dict(layer=ops.pack_conv_plain_dev(weight, bias), in0=xh, out=out)], epi=_DOWN_EPI[act], stride=2)
         ctx.act = act
         ctx.save_for_backward(xh, weight, out if act else None)
-        return out.permute(0, 3, 1, 2)
+        return _nchw(out)
 
     @staticmethod
     def backward(ctx, grad_out):
         xh, weight, out = ctx.saved_tensors
-        g = _nhwc(grad_out, "ConvDown backward")
-        if ctx.act == "lrelu":
-            g = torch.where(out > 0, g, g * 0.1)
+        g = _act_grad(_nhwc(grad_out, "ConvDown backward"), out, ctx.act)
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        gx = gw = gb = None
-        if need_w or need_b:
-            gw, gb = ops.conv3x3s2_wgrad(xh, g)
-        if need_x:
-            gx = ops.conv3x3s2_dgrad(g, weight, xh.shape[1], xh.shape[2]).permute(0, 3, 1, 2)
-        return gx, gw if need_w else None, gb if need_b else None, None
+        gw, gb = ops.conv3x3s2_wgrad(xh, g) if need_w or need_b else (None, None)
+        gx = _nchw(ops.conv3x3s2_dgrad(g, weight, xh.shape[1], xh.shape[2])) if need_x else None
+        return _grads(ctx.needs_input_grad, gx, gw, gb)
 
 
 class ConvDown(nn.Module):
@@ -430,11 +511,7 @@ class ConvDown(nn.Module):
         if act not in _DOWN_EPI:
             raise ValueError(f"act must be None or 'lrelu' (the stride-2 forward kernel's epilogues), got {act!r}")
         self.act = act
-        self.weight = nn.Parameter(torch.empty(nf, nf, 3, 3))
-        self.bias = nn.Parameter(torch.empty(nf))
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(nf * 9)
-        nn.init.uniform_(self.bias, -bound, bound)
+        self.weight, self.bias = _conv2d_params(nf, nf, 3)
 
     def forward(self, x):
         return _ConvDownFn.apply(x, self.weight, self.bias, self.act)
@@ -450,18 +527,15 @@ class _ConvFirstFn(torch.autograd.Function):
         out = torch.empty(n, H, W, 64, dtype=torch.float32, device=frames.device)
         ops.conv_first(frames, weight.detach().contiguous(), bias.detach().contiguous(), out)
         ctx.save_for_backward(frames, out)
-        return out.permute(0, 3, 1, 2)
+        return _nchw(out)
 
     @staticmethod
     def backward(ctx, grad_out):
         frames, out = ctx.saved_tensors
-        g = _nhwc(grad_out, "ConvFirst backward")
-        g = torch.where(out > 0, g, g * 0.1)
+        g = _act_grad(_nhwc(grad_out, "ConvFirst backward"), out, "lrelu")
         need_w, need_b = ctx.needs_input_grad[1:3]
-        gw = gb = None
-        if need_w or need_b:
-            gw, gb = ops.conv_first_wgrad(frames, g)
-        return None, gw if need_w else None, gb if need_b else None
+        gw, gb = ops.conv_first_wgrad(frames, g) if need_w or need_b else (None, None)
+        return _grads(ctx.needs_input_grad, None, gw, gb)
 
 
 class ConvFirst(nn.Module):
@@ -471,19 +545,13 @@ class ConvFirst(nn.Module):
 
     def __init__(self):
         super().__init__()
-        self.weight = nn.Parameter(torch.empty(64, 3, 3, 3))
-        self.bias = nn.Parameter(torch.empty(64))
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(27)
-        nn.init.uniform_(self.bias, -bound, bound)
+        self.weight, self.bias = _conv2d_params(64, 3, 3)
 
     def forward(self, frames):
         if frames.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("ConvFirst: the gradient with respect to the input frames is not built "
                                       "(pass frames that do not require grad)")
-        if not frames.is_cuda:
-            raise RuntimeError(f"ConvFirst: the HIP convolution kernels need a CUDA tensor, got one on {frames.device} "
-                               "(move the module and its input to the GPU)")
+        _need_cuda("ConvFirst", frames)
         if frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 3:
             raise RuntimeError(f"ConvFirst: expected a float32 [n, 3, H, W] tensor, got {frames.dtype} "
                                f"{tuple(frames.shape)}")
@@ -493,7 +561,21 @@ class ConvFirst(nn.Module):
         return "3, 64, kernel_size=(3, 3), padding=1, act=lrelu"
 
 
-class FrameFeatures(nn.Module):
+def _add_pyramid(mod: nn.Module, mfma: str) -> None:
+    """Register the reference's four pyramid convs on ``mod`` under their names, in its order."""
+    mod.fea_L2_conv1 = ConvDown(64, "lrelu")
+    mod.fea_L2_conv2 = Conv3x3(64, "lrelu", mfma)
+    mod.fea_L3_conv1 = ConvDown(64, "lrelu")
+    mod.fea_L3_conv2 = Conv3x3(64, "lrelu", mfma)
+
+
+def _pyramid(mod: nn.Module, L1):
+    """(L2, L3) of L1 through ``mod``'s pyramid convs."""
+    L2 = mod.fea_L2_conv2(mod.fea_L2_conv1(L1))
+    return L2, mod.fea_L3_conv2(mod.fea_L3_conv1(L2))
+
+
+class FrameFeatures(_RangeStatus, nn.Module):
     """The reference's per-frame encoder (Sakuya_arch_test.py:282-287, :318-325) with its parameter names, so the
     ``conv_first.*``, ``feature_extraction.*`` and ``fea_L*_conv*`` slices of a LunaTokis state dict load with
     ``strict=True``: frames [n, 3, H, W] -> (L1, L2, L3), every conv forward and backward on the HIP kernels.
@@ -504,19 +586,11 @@ class FrameFeatures(nn.Module):
         _check_choice(64, "lrelu", mfma)
         self.conv_first = ConvFirst()
         self.feature_extraction = make_trunk(front_RBs, 64, mfma)
-        self.fea_L2_conv1 = ConvDown(64, "lrelu")
-        self.fea_L2_conv2 = Conv3x3(64, "lrelu", mfma)
-        self.fea_L3_conv1 = ConvDown(64, "lrelu")
-        self.fea_L3_conv2 = Conv3x3(64, "lrelu", mfma)
+        _add_pyramid(self, mfma)
 
     def forward(self, frames):
         L1 = self.feature_extraction(self.conv_first(frames))
-        L2 = self.fea_L2_conv2(self.fea_L2_conv1(L1))
-        L3 = self.fea_L3_conv2(self.fea_L3_conv1(L2))
-        return L1, L2, L3
-
-    def range_status(self) -> int:
-        return range_status(self.conv_first.weight.device)
+        return (L1, *_pyramid(self, L1))
 
 
 # ---- PCD_Align: the concatenation convs, the x2 upsample, DCN_sep (Sakuya_arch_test.py:20-130, dcn_v2.py:110-140) ----
@@ -529,11 +603,11 @@ class _Upsample2xFn(torch.autograd.Function):
         out = torch.empty(n, 2 * h, 2 * w, c, dtype=torch.float32, device=xh.device)
         ops.upsample2x(xh, out, scale)
         ctx.scale = scale
-        return out.permute(0, 3, 1, 2)
+        return _nchw(out)
 
     @staticmethod
     def backward(ctx, grad_out):
-        return ops.upsample2x_bwd(_nhwc(grad_out, "Upsample2x backward", None), ctx.scale).permute(0, 3, 1, 2), None
+        return _nchw(ops.upsample2x_bwd(_nhwc(grad_out, "Upsample2x backward", None), ctx.scale)), None
 
 
 class Upsample2x(nn.Module):
@@ -552,44 +626,7 @@ class Upsample2x(nn.Module):
         return f"scale={self.scale}"
 
 
-class _Conv3x3CatFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b, weight, bias, act, mode):
-        ah, bh = _nhwc(a, "Conv3x3Cat"), _nhwc(b, "Conv3x3Cat")
-        if ah.shape != bh.shape:
-            raise RuntimeError(f"Conv3x3Cat: the two inputs differ in shape, {tuple(a.shape)} and {tuple(b.shape)}")
-        status = _status_word(ah.device)
-        lay = ops.pack_conv_blocks_dev(weight, bias, mode, status=status)
-        out = torch.empty(ah.shape, dtype=torch.float32, device=ah.device)
-        ops.conv2d([dict(layer=lay, in0=ah, in1=bh, out=out)], epi=_EPI[act], in1_mode=1, status=status)
-        ctx.act, ctx.mode = act, mode
-        ctx.save_for_backward(ah, bh, weight, out if act else None)
-        return out.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ah, bh, weight, out = ctx.saved_tensors
-        g = _nhwc(grad_out, "Conv3x3Cat backward")
-        if ctx.act == "relu":
-            g = g * (out > 0)
-        elif ctx.act == "lrelu":
-            g = torch.where(out > 0, g, g * 0.1)
-        need_a, need_b, need_w, need_bias = ctx.needs_input_grad[:4]
-        gw = gb = None
-        if need_w or need_bias:
-            gw, gb = ops.conv3x3_wgrad_cat([ah, bh], g, 64)
-        gin = [None, None]
-        status = _status_word(g.device)
-        for half, need in enumerate((need_a, need_b)):
-            if need:
-                lay = ops.pack_conv_blocks_dev(weight, None, ctx.mode, dgrad=True, half=half, status=status)
-                gx = torch.empty(g.shape, dtype=torch.float32, device=g.device)
-                ops.conv2d([dict(layer=lay, in0=g, out=gx)], status=status)
-                gin[half] = gx.permute(0, 3, 1, 2)
-        return gin[0], gin[1], gw if need_w else None, gb if need_bias else None, None, None
-
-
-class Conv3x3Cat(nn.Module):
+class Conv3x3Cat(_RangeStatus, nn.Module):
     """nn.Conv2d(128, 64, 3, 1, 1) applied to torch.cat([a, b], 1) with an optional fused ReLU / LeakyReLU(0.1),
     without the concatenation: the forward is one stif_conv3x3_wino launch with two inputs, the backward
     stif_conv3x3_wgrad_cat and one 64 -> 64 Winograd data-gradient conv per input that needs one.  ``weight``
@@ -599,17 +636,10 @@ class Conv3x3Cat(nn.Module):
         super().__init__()
         _check_choice(64, act, mfma)
         self.act, self.mfma = act, mfma
-        self.weight = nn.Parameter(torch.empty(64, 128, 3, 3))
-        self.bias = nn.Parameter(torch.empty(64))
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(128 * 9)
-        nn.init.uniform_(self.bias, -bound, bound)
+        self.weight, self.bias = _conv2d_params(64, 128, 3)
 
     def forward(self, a, b):
-        return _Conv3x3CatFn.apply(a, b, self.weight, self.bias, self.act, _PACK[self.mfma])
-
-    def range_status(self) -> int:
-        return range_status(self.weight.device)
+        return _ConvFn.apply("Conv3x3Cat", a, b, self.weight, self.bias, self.act, _PACK[self.mfma])
 
     def extra_repr(self):
         return f"128, 64, kernel_size=(3, 3), padding=1, act={self.act}, mfma={self.mfma}"
@@ -624,8 +654,7 @@ class _DCNSepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, fea, weight, bias, om_weight, om_bias, act, mode):
         feah, xh = _nhwc(fea, "DCN_sep"), _nhwc(inp, "DCN_sep")
-        if xh.shape != feah.shape:
-            raise RuntimeError(f"DCN_sep: input {tuple(inp.shape)} and fea {tuple(fea.shape)} differ in shape")
+        _same_shape("DCN_sep", inp, fea)
         status = _status_word(feah.device)
         n, H, W, _ = feah.shape
         om = torch.empty(n, H, W, 256, dtype=torch.float32, device=feah.device)
@@ -636,44 +665,33 @@ class _DCNSepFn(torch.autograd.Function):
         ops.dcn([dict(layer=ops.pack_conv_plain_dev(weight, bias), inp=xh, offmask=offmask, out=out)], epi=_EPI[act])
         ctx.act, ctx.mode = act, mode
         ctx.save_for_backward(xh, offmask, feah, weight, om_weight, out if act else None)
-        return out.permute(0, 3, 1, 2)
+        return _nchw(out)
 
     @staticmethod
     def backward(ctx, grad_out):
         xh, offmask, feah, weight, om_weight, out = ctx.saved_tensors
-        if not grad_out.is_cuda:
-            raise RuntimeError("DCN_sep backward: the HIP kernels need a CUDA tensor")
         g = _nhwc(grad_out, "DCN_sep backward")
         need_in, need_fea, need_w, need_b, need_omw, need_omb = ctx.needs_input_grad[:6]
         need = (need_in, need_fea or need_omw or need_omb, need_w or need_b)
-        g_in = g_fea = g_w = g_b = g_omw = g_omb = None
+        g_in = g_om = g_w = g_b = None
         if any(need):
             g_in, g_om, g_w, g_b = ops.dcn_bwd(xh, offmask, weight, g, out=out, epi=_EPI[ctx.act], need=need,
                                                deterministic=_DETERMINISTIC)
-        if need_in:
-            g_in = g_in.permute(0, 3, 1, 2)
-        if need_omw or need_omb:
-            g_omw, g_omb = ops.conv3x3_wgrad_cat([feah], g_om, 216)
-        if need_fea:
-            status = _status_word(feah.device)
-            lay = ops.pack_conv_blocks_dev(om_weight, None, ctx.mode, dgrad=True, status=status)
-            gf = torch.empty(feah.shape, dtype=torch.float32, device=feah.device)
-            ops.conv2d([dict(layer=lay, in0=g_om, out=gf)], status=status)
-            g_fea = gf.permute(0, 3, 1, 2)
-        return (g_in, g_fea, g_w if need_w else None, g_b if need_b else None,
-                g_omw if need_omw else None, g_omb if need_omb else None, None, None)
+        g_omw, g_omb = ops.conv3x3_wgrad_cat([feah], g_om, 216) if need_omw or need_omb else (None, None)
+        g_fea = _conv_dgrad(g_om, om_weight, ctx.mode) if need_fea else None
+        return _grads(ctx.needs_input_grad, _nchw(g_in), _nchw(g_fea), g_w, g_b, g_omw, g_omb)
 
 
 class _ConvParams(nn.Module):
-    """The parameters of an nn.Conv2d (``weight``, ``bias``) under its names, with no forward of its own."""
+    """The parameters of an nn.Conv2d(cin, cout, 3) (``weight``, ``bias``) under its names, with no forward of its own;
+    ``init`` as _conv2d_params."""
 
-    def __init__(self, cout, cin):
+    def __init__(self, cout, cin, init="conv2d"):
         super().__init__()
-        self.weight = nn.Parameter(torch.zeros(cout, cin, 3, 3))
-        self.bias = nn.Parameter(torch.zeros(cout))
+        self.weight, self.bias = _conv2d_params(cout, cin, 3, init)
 
 
-class DCN_sep(nn.Module):
+class DCN_sep(_RangeStatus, nn.Module):
     """dcn_v2.py:110-140 for 64 -> 64 channels, 3x3, 8 deformable groups, trainable on the engine: ``forward(input,
     fea)`` = the modulated deformable conv of ``input`` with offsets and masks from ``conv_offset_mask(fea)``,
     optionally followed by LeakyReLU(0.1).  Parameters under the reference's names -- ``weight``, ``bias``,
@@ -692,20 +710,17 @@ class DCN_sep(nn.Module):
         self.bias = nn.Parameter(torch.zeros(64))
         stdv = 1.0 / math.sqrt(64 * 9)
         nn.init.uniform_(self.weight, -stdv, stdv)
-        self.conv_offset_mask = _ConvParams(216, 64)
+        self.conv_offset_mask = _ConvParams(216, 64, "zeros")
 
     def forward(self, input, fea):
         return _DCNSepFn.apply(input, fea, self.weight, self.bias, self.conv_offset_mask.weight,
                                self.conv_offset_mask.bias, self.act, _PACK[self.mfma])
 
-    def range_status(self) -> int:
-        return range_status(self.weight.device)
-
     def extra_repr(self):
         return f"64, 64, kernel_size=(3, 3), padding=1, deformable_groups=8, act={self.act}, mfma={self.mfma}"
 
 
-class PCD_Align(nn.Module):
+class PCD_Align(_RangeStatus, nn.Module):
     """Sakuya_arch_test.py:20-130 with the reference's submodule names and registration order, so the ``pcd_align.*``
     slice of a LunaTokis state dict (and ``ConvBLSTM.forward_net.pcd_h.pcd_align.*`` / ``...pcd_c.pcd_align.*``) loads
     with ``strict=True``: ``forward(fea1, fea2)`` takes two lists [L1, L2, L3] of logical-NCHW 64-channel maps and
@@ -754,17 +769,11 @@ class PCD_Align(nn.Module):
             if tuple(fea1[lv].shape) != want or tuple(fea2[lv].shape) != want:
                 raise ValueError(f"PCD_Align: level L{lv + 1} must be {want}, got {tuple(fea1[lv].shape)} and "
                                  f"{tuple(fea2[lv].shape)}")
-        for t in fea1 + fea2:     # a CPU tensor is refused before any launch
-            if not t.is_cuda:
-                raise RuntimeError(f"PCD_Align: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
-                                   "(move the module and its input to the GPU)")
+        _need_cuda("PCD_Align", *fea1, *fea2)     # a CPU tensor is refused before any launch
         return self._branch("_1", fea1, fea2), self._branch("_2", fea2, fea1)
 
     def forward(self, fea1, fea2):
         return torch.cat(self.branches(fea1, fea2), dim=1)
-
-    def range_status(self) -> int:
-        return range_status(self.L3_dcnpack_1.weight.device)
 
 
 # ---- Easy_PCD, the ConvLSTM cell, BiDeformableConvLSTM, gen_feat (Sakuya_arch_test.py:132-266, :313-362) ----
@@ -772,38 +781,7 @@ class PCD_Align(nn.Module):
 _PACK1 = {"f16x3": L.PACK_PLAIN | L.PACK_F16X3, "f32": L.PACK_PLAIN}   # the 1x1 layers' packings
 
 
-class _Conv1x1CatFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b, weight, bias, mode):
-        ah, bh = _nhwc(a, "Conv1x1Cat"), _nhwc(b, "Conv1x1Cat")
-        if ah.shape != bh.shape:
-            raise RuntimeError(f"Conv1x1Cat: the two inputs differ in shape, {tuple(a.shape)} and {tuple(b.shape)}")
-        status = _status_word(ah.device)
-        lay = ops.pack_conv1x1_dev(weight, bias, mode, status=status)
-        out = torch.empty(ah.shape, dtype=torch.float32, device=ah.device)
-        ops.conv2d([dict(layer=lay, in0=ah, in1=bh, out=out)], in1_mode=1, status=status)
-        ctx.save_for_backward(ah, bh, weight)
-        return out.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ah, bh, weight = ctx.saved_tensors
-        g = _nhwc(grad_out, "Conv1x1Cat backward")
-        need_a, need_b, need_w, need_bias = ctx.needs_input_grad[:4]
-        gw = gb = None
-        if need_w or need_bias:
-            gw, gb = ops.conv1x1_wgrad([ah, bh], g)
-        gin = [None, None]
-        for half, need in enumerate((need_a, need_b)):
-            if need:   # fp32 in both modes: the split-fp16 1x1 kernel takes the (64 | 64) and 200-channel inputs only
-                lay = ops.pack_conv1x1_dev(weight, None, L.PACK_PLAIN, dgrad=True, half=half)
-                gx = torch.empty(g.shape, dtype=torch.float32, device=g.device)
-                ops.conv2d([dict(layer=lay, in0=g, out=gx)])
-                gin[half] = gx.permute(0, 3, 1, 2)
-        return gin[0], gin[1], gw if need_w else None, gb if need_bias else None, None
-
-
-class Conv1x1Cat(nn.Module):
+class Conv1x1Cat(_RangeStatus, nn.Module):
     """nn.Conv2d(128, 64, 1) applied to torch.cat([a, b], 1) without the concatenation (``fusion``,
     ``Easy_PCD.fusion``, ``ConvBLSTM.conv_1x1``): the forward is stif_conv2d_nhwc with two inputs on the weight packed
     by stif_pack_conv1x1_dev, the backward stif_conv1x1_wgrad and one fp32 1x1 64 -> 64 conv per input that needs a
@@ -813,17 +791,10 @@ class Conv1x1Cat(nn.Module):
         super().__init__()
         _check_choice(64, None, mfma)
         self.mfma = mfma
-        self.weight = nn.Parameter(torch.empty(64, 128, 1, 1))
-        self.bias = nn.Parameter(torch.empty(64))
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(128)
-        nn.init.uniform_(self.bias, -bound, bound)
+        self.weight, self.bias = _conv2d_params(64, 128, 1)
 
     def forward(self, a, b):
-        return _Conv1x1CatFn.apply(a, b, self.weight, self.bias, _PACK1[self.mfma])
-
-    def range_status(self) -> int:
-        return range_status(self.weight.device)
+        return _ConvFn.apply("Conv1x1Cat", a, b, self.weight, self.bias, None, _PACK1[self.mfma])
 
     def extra_repr(self):
         return f"128, 64, kernel_size=(1, 1), mfma={self.mfma}"
@@ -837,9 +808,7 @@ class _ConvLSTMCellFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, h, c, weight, bias, mode):
         xh, hh, ch = (_nhwc(t, "ConvLSTMCell") for t in (x, h, c))
-        if xh.shape != hh.shape or xh.shape != ch.shape:
-            raise RuntimeError(f"ConvLSTMCell: input {tuple(x.shape)}, h {tuple(h.shape)} and c {tuple(c.shape)} "
-                               "differ in shape")
+        _same_shape("ConvLSTMCell", x, h, c)
         status = _status_word(xh.device)
         n, H, W, _ = xh.shape
         pre = torch.empty(n, H, W, 256, dtype=torch.float32, device=xh.device)
@@ -849,7 +818,7 @@ class _ConvLSTMCellFn(torch.autograd.Function):
         ctx.mode = mode
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(xh, hh, ch, pre, weight)
-        return h_next.permute(0, 3, 1, 2), c_next.permute(0, 3, 1, 2)
+        return _nchw(h_next), _nchw(c_next)
 
     @staticmethod
     def backward(ctx, g_h, g_c):
@@ -860,34 +829,13 @@ class _ConvLSTMCellFn(torch.autograd.Function):
         g_c = None if g_c is None else _nhwc(g_c, "ConvLSTMCell backward")
         need_x, need_h, need_c, need_w, need_b = ctx.needs_input_grad[:5]
         g_pre, g_cc = ops.lstm_gates_bwd(pre, ch, g_h, g_c, need_c=need_c)
-        gw = gb = None
-        if need_w or need_b:
-            gw, gb = ops.conv3x3_wgrad_cat([xh, hh], g_pre, 256)
-        gin = [None, None]
-        status = _status_word(pre.device)
-        for half, need in enumerate((need_x, need_h)):
-            if need:
-                lay = ops.pack_conv_blocks_dev(weight, None, ctx.mode, dgrad=True, half=half, status=status)
-                gx = torch.empty(xh.shape, dtype=torch.float32, device=pre.device)
-                ops.conv2d([dict(layer=lay, in0=g_pre, out=gx)], status=status)
-                gin[half] = gx.permute(0, 3, 1, 2)
-        return (gin[0], gin[1], g_cc.permute(0, 3, 1, 2) if need_c else None, gw if need_w else None,
-                gb if need_b else None, None)
+        gw, gb = ops.conv3x3_wgrad_cat([xh, hh], g_pre, 256) if need_w or need_b else (None, None)
+        gin = [_nchw(_conv_dgrad(g_pre, weight, ctx.mode, half=half)) if need else None
+               for half, need in enumerate((need_x, need_h))]
+        return _grads(ctx.needs_input_grad, gin[0], gin[1], _nchw(g_cc), gw, gb)
 
 
-class _Conv2dParams(nn.Module):
-    """``weight`` / ``bias`` of an nn.Conv2d(cin, cout, 3) with its default initialisation, no forward of its own."""
-
-    def __init__(self, cout, cin):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(cout, cin, 3, 3))
-        self.bias = nn.Parameter(torch.empty(cout))
-        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        bound = 1.0 / math.sqrt(cin * 9)
-        nn.init.uniform_(self.bias, -bound, bound)
-
-
-class ConvLSTMCell(nn.Module):
+class ConvLSTMCell(_RangeStatus, nn.Module):
     """convlstm.py:8-58 for 64 input and 64 hidden channels, 3x3: ``forward(x, (h, c)) -> (h_next, c_next)`` with
     ``conv.weight`` [256, 128, 3, 3] / ``conv.bias`` [256] under the reference's names (rows: gates i, f, o, g of 64
     hidden channels each).  One autograd node: forward stif_conv3x3_wino on (x | h) and stif_lstm_gates_nhwc; backward
@@ -898,14 +846,11 @@ class ConvLSTMCell(nn.Module):
         super().__init__()
         _check_choice(64, None, mfma)
         self.mfma = mfma
-        self.conv = _Conv2dParams(256, 128)
+        self.conv = _ConvParams(256, 128)
 
     def forward(self, x, state):
         h, c = state
         return _ConvLSTMCellFn.apply(x, h, c, self.conv.weight, self.conv.bias, _PACK[self.mfma])
-
-    def range_status(self) -> int:
-        return range_status(self.conv.weight.device)
 
 
 def _check_maps(who, maps, what="[B, 64, H, W]"):
@@ -917,13 +862,10 @@ def _check_maps(who, maps, what="[B, 64, H, W]"):
     if first.shape[2] % 4 or first.shape[3] % 4:
         raise ValueError(f"{who}: H and W must be multiples of 4 (three pyramid levels), got "
                          f"{first.shape[2]} x {first.shape[3]}")
-    for t in maps:
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: the HIP convolution kernels need a CUDA tensor, got one on {t.device} "
-                               "(move the module and its input to the GPU)")
+    _need_cuda(who, *maps)
 
 
-class Easy_PCD(nn.Module):
+class Easy_PCD(_RangeStatus, nn.Module):
     """Sakuya_arch_test.py:132-166 with the reference's submodule names and registration order: the two-level pyramid
     of both inputs (one pass over the 2B stacked items), ``pcd_align`` and the 1x1 ``fusion`` on its two halves.
     ``forward(f1, f2)``: [B, 64, H, W] each -> [B, 64, H, W], H and W multiples of 4."""
@@ -931,24 +873,16 @@ class Easy_PCD(nn.Module):
     def __init__(self, mfma: str = "f16x3"):
         super().__init__()
         _check_choice(64, None, mfma)
-        self.fea_L2_conv1 = ConvDown(64, "lrelu")
-        self.fea_L2_conv2 = Conv3x3(64, "lrelu", mfma)
-        self.fea_L3_conv1 = ConvDown(64, "lrelu")
-        self.fea_L3_conv2 = Conv3x3(64, "lrelu", mfma)
+        _add_pyramid(self, mfma)
         self.pcd_align = PCD_Align(mfma)
         self.fusion = Conv1x1Cat(mfma)
 
     def forward(self, f1, f2):
         _check_maps("Easy_PCD", [f1, f2])
         B = f1.shape[0]
-        L1 = torch.cat([f1, f2], dim=0)     # the reference stacks on dim 1; the convs are per item
-        L2 = self.fea_L2_conv2(self.fea_L2_conv1(L1))
-        L3 = self.fea_L3_conv2(self.fea_L3_conv1(L2))
+        L2, L3 = _pyramid(self, torch.cat([f1, f2], dim=0))     # the reference stacks on dim 1; the convs are per item
         a, b = self.pcd_align.branches([f1, L2[:B], L3[:B]], [f2, L2[B:], L3[B:]])
         return self.fusion(a, b)
-
-    def range_status(self) -> int:
-        return range_status(self.fusion.weight.device)
 
 
 class DeformableConvLSTM(nn.Module):
@@ -976,7 +910,7 @@ class DeformableConvLSTM(nn.Module):
         return torch.stack(outs, dim=1)
 
 
-class BiDeformableConvLSTM(nn.Module):
+class BiDeformableConvLSTM(_RangeStatus, nn.Module):
     """Sakuya_arch_test.py:247-266: ``forward_net`` over the sequence and over its reverse (the same weights),
     ``conv_1x1`` on (out_fwd[t] | out_rev[T - 1 - t]).  [B, T, 64, H, W] -> [B, T, 64, H, W], H and W multiples of 4;
     the ``ConvBLSTM.*`` slice of a LunaTokis state dict loads with ``strict=True``."""
@@ -997,9 +931,6 @@ class BiDeformableConvLSTM(nn.Module):
         out = self.conv_1x1(fwd.reshape(B * T, C, H, W), rev.reshape(B * T, C, H, W))
         return out.reshape(B, T, C, H, W)
 
-    def range_status(self) -> int:
-        return range_status(self.conv_1x1.weight.device)
-
 
 _NOT_GEN_FEAT = ("feat_imnet.", "flow_imnet.", "encode_imnet.", "upconv1.", "upconv2.", "HRconv.", "conv_last.")
 
@@ -1010,7 +941,7 @@ def gen_feat_state_dict(sd) -> dict:
     return {k: torch.as_tensor(v) for k, v in sd.items() if not k.startswith(_NOT_GEN_FEAT)}
 
 
-class GenFeat(nn.Module):
+class GenFeat(_RangeStatus, nn.Module):
     """LunaTokis.gen_feat (Sakuya_arch_test.py:313-362), everything before the decoder, trainable on the engine with
     the parameters under the reference's top-level names: frames [B, N, 3, H, W] -> features [B, 2N - 1, 64, H, W],
     H and W multiples of 4.  ``gen_feat_state_dict(sd)`` loads with ``strict=True``."""
@@ -1020,10 +951,7 @@ class GenFeat(nn.Module):
         _check_choice(64, None, mfma)
         self.conv_first = ConvFirst()
         self.feature_extraction = make_trunk(front_RBs, 64, mfma)
-        self.fea_L2_conv1 = ConvDown(64, "lrelu")
-        self.fea_L2_conv2 = Conv3x3(64, "lrelu", mfma)
-        self.fea_L3_conv1 = ConvDown(64, "lrelu")
-        self.fea_L3_conv2 = Conv3x3(64, "lrelu", mfma)
+        _add_pyramid(self, mfma)
         self.pcd_align = PCD_Align(mfma)
         self.fusion = Conv1x1Cat(mfma)
         self.ConvBLSTM = BiDeformableConvLSTM(mfma)
@@ -1036,9 +964,7 @@ class GenFeat(nn.Module):
         if H % 4 or W % 4:
             raise ValueError(f"GenFeat: H and W must be multiples of 4 (three pyramid levels), got {H} x {W}")
         L1 = self.feature_extraction(self.conv_first(x.reshape(B * N, 3, H, W)))
-        L2 = self.fea_L2_conv2(self.fea_L2_conv1(L1))
-        L3 = self.fea_L3_conv2(self.fea_L3_conv1(L2))
-        lv = [t.reshape(B, N, 64, t.shape[2], t.shape[3]) for t in (L1, L2, L3)]
+        lv = [t.reshape(B, N, 64, t.shape[2], t.shape[3]) for t in (L1, *_pyramid(self, L1))]
         seq = [lv[0][:, 0]]
         for i in range(N - 1):
             a, b = self.pcd_align.branches([t[:, i] for t in lv], [t[:, i + 1] for t in lv])
@@ -1046,9 +972,6 @@ class GenFeat(nn.Module):
         feats = self.ConvBLSTM(torch.stack(seq, dim=1))
         T = feats.shape[1]
         return self.recon_trunk(feats.reshape(B * T, 64, H, W)).reshape(B, T, 64, H, W)
-
-    def range_status(self) -> int:
-        return range_status(self.conv_first.weight.device)
 
 
 # ---- the SIREN decoder and the whole model (SIREN.py:27-79, Sakuya_arch_test.py:304-311, :364-459, :1222-1231) ----
@@ -1265,10 +1188,10 @@ class LunaTokis(GenFeat):
 
     def __init__(self, front_RBs: int = 5, back_RBs: int = 40, mfma: str = "f16x3"):
         super().__init__(front_RBs, back_RBs, mfma)
-        self.upconv1 = _Conv2dParams(256, 64)
-        self.upconv2 = _Conv2dParams(256, 64)
-        self.HRconv = _Conv2dParams(64, 64)
-        self.conv_last = _Conv2dParams(3, 64)
+        self.upconv1 = _ConvParams(256, 64)
+        self.upconv2 = _ConvParams(256, 64)
+        self.HRconv = _ConvParams(64, 64)
+        self.conv_last = _ConvParams(3, 64)
         _make_imnets(self)
 
     def forward(self, x, times, scale=None):
